@@ -27,6 +27,11 @@ apart so that every frame culls against the HZB of a *different* previous frame 
 
 value = triangles of the clusters submitted to the rasterizer per frame (post-cull, the unit of
 SURVEY §8d) x steps / wall time of the timed region, max over ranks.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps frames and prints the line (plus its triangle counts, which the value needs).  Everything
+else it can measure takes --full: the stamped frames behind gpu_ms / roofline / kernel_launches, the moving camera path, the CPU
+baseline, and for N > 1 the default-map figure, the pipelined protocol, the timed single-GPU reference, the peer-copy transport and
+`also`.  --dump-outputs DIR writes what the last timed step computed (the image and the frame's counts: write_outputs) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -99,6 +104,9 @@ def main():
     ap.add_argument("--no-path", action="store_true", help="N = 1: do not also time the moving camera path (`moving_path`)")
     ap.add_argument("--path-views", type=int, default=64, help="distinct views of the moving camera path (even)")
     ap.add_argument("--tile-schedule-keep", type=int, default=-1, help="frames a tile schedule is kept for (chordvis_set_tile_schedule_keep; -1: the library's default -- measurement runs only: the line says what ran)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure (stamped per-kernel times and roofline, moving path, "
+                                                         "CPU baseline; N > 1: default map, pipelined protocol, timed single-GPU reference, peer-copy transport, `also`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -135,11 +143,11 @@ def main():
     line = measure(args, args.workload, env)
     # (CHORDVIS_BENCH_ALSO: test hook -- a small second workload for the one-GPU protocol tests)
     also_wl = os.environ.get("CHORDVIS_BENCH_ALSO") or ("street_x64_4k_hzb" if args.workload == "auto" else None)
-    if world > 1 and also_wl and not args.no_also:
+    if world > 1 and also_wl and args.full and not args.no_also:
         # (the second measurement must not cost the first its line: a failure here -- on any rank; the others leave their
         # collectives when the control plane times out -- is reported inside `also` instead)
         try:
-            also = measure(args, also_wl, env)
+            also = measure(argparse.Namespace(**dict(vars(args), dump_outputs=None)), also_wl, env)
             if line is not None and also is not None:
                 line["also"] = {k: also[k] for k in ("config", "value", "unit", "ms_per_step", "steps", "timed_region_s", "exchange", "pipelined", "tile_map", "exchange_fallbacks", "default_map",
                                                        "exchange_gbs", "rccl_schedule_ok", "group_transport", "bound", "cull",
@@ -391,10 +399,11 @@ def measure(args, workload, env):
         imb_before = 1.0
         if not args.no_rebalance:
             # the same frames under the DEFAULT map first (compact regions of equal area): the re-balanced map below is made from the
-            # loads of exactly the two views the timed region renders, which a moving camera would not grant it
-            nd = max(2, min(args.steps, 20)) & ~1
-            _, dm = timed(nd)
-            default_map = {"steps": nd, "ms_per_step": round(dm / nd * 1e3, 4)}
+            # loads of exactly the two views the timed region renders, which a moving camera would not grant it (--full)
+            if args.full:
+                nd = max(2, min(args.steps, 20)) & ~1
+                _, dm = timed(nd)
+                default_map = {"steps": nd, "ms_per_step": round(dm / nd * 1e3, 4)}
             imb_before = r.rebalance()
             if ex is not None:
                 ex.remap()
@@ -433,7 +442,9 @@ def measure(args, workload, env):
     stamped_in_region = (args.steps + 7) // 8 if stamp_inside else 0
     extra = 0
     st = r.stats()                                  # per-frame GPU timestamps averaged over the stamped steps of the timed region
-    if stamped_in_region < 8 and world == 1 and not args.no_stamps:
+    # (what the last timed step computed, read before any other frame replaces it; written at the end)
+    outputs = read_outputs(r) if (args.dump_outputs and rank == 0) else None
+    if args.full and stamped_in_region < 8 and world == 1 and not args.no_stamps:
         r.enable_timers(2, period=1)                # (restarts the accumulation)
         extra = (16 if args.steps >= 64 else 8) - stamped_in_region
         for i in range(extra):
@@ -448,7 +459,7 @@ def measure(args, workload, env):
     ms_per_step = elapsed / args.steps * 1e3
     # launches of a frame between two tile schedules and of a frame that makes them (two consecutive frames, outside the clock)
     launches_seen = [st["kernelLaunches"]]
-    if world == 1:
+    if world == 1 and args.full:
         for i in range(2):
             frame(args.steps + extra + i)
             torch.cuda.synchronize(dev)
@@ -459,7 +470,7 @@ def measure(args, workload, env):
     # ---- N = 1: the same metric along a MOVING camera (the two-view loop re-makes the kept tile schedule on the same view every time and
     #      renders it on views the schedule was made for or next to: as favourable as a kept schedule gets)
     moving = None
-    if world == 1 and not args.no_path and wl.startswith("street") and not args.debug_flags:
+    if world == 1 and args.full and not args.no_path and wl.startswith("street") and not args.debug_flags:
         moving = moving_path(args, r, scene, cam_a, flags, dev)
         if moving:
             moving["ratio_to_two_view"] = round(moving["value"] / (tris_per_pair / 2.0 / (ms_per_step * 1e-3) / 1e9), 4)
@@ -467,7 +478,7 @@ def measure(args, workload, env):
     # ---- N > 1, library-run exchange: the PIPELINED protocol on the same frames (second communicator: the image of frame i travels
     #      beside frame i + 1; the history HZB waits only for the small end-of-frame exchange) -- DESIGN.md 6
     pipe = None
-    if world > 1 and not args.no_pipelined:
+    if world > 1 and args.full and not args.no_pipelined:
         if exchange == "lib":
             from chord_amd.renderer import comm_unique_id
             try:
@@ -615,14 +626,15 @@ def measure(args, workload, env):
                 r1.set_view(v, iv, flags)
                 r1.render_frame()
             n1 = max(8, min(args.steps, 100)) & ~1
-            for i in range(8):
-                frame1(i)
-            torch.cuda.synchronize(dev)
-            s0 = time.perf_counter()
-            for i in range(n1):
-                frame1(i)
-            torch.cuda.synchronize(dev)
-            s1 = time.perf_counter()
+            if args.full:                                # (timed: --full; a plain run takes only the counts below)
+                for i in range(8):
+                    frame1(i)
+                torch.cuda.synchronize(dev)
+                s0 = time.perf_counter()
+                for i in range(n1):
+                    frame1(i)
+                torch.cuda.synchronize(dev)
+                s1 = time.perf_counter()
             # the unit of the metric -- triangles of the clusters submitted to the rasterizer -- is the FRAME's: a rank of a
             # sharded frame culls and counts only the clusters that touch its rows, so the count comes from this run
             ref_view = [None, None]
@@ -630,9 +642,11 @@ def measure(args, workload, env):
                 frame1(i)
                 ref_view[i & 1] = r1.stats()
             tris_per_pair = ref_view[0]["trianglesSubmitted"] + ref_view[1]["trianglesSubmitted"]
-            single_ref = {"workload": wl, "n_gpus": 1, "steps": n1, "ms_per_step": round((s1 - s0) / n1 * 1e3, 4),
-                          "value": round(tris_per_pair * (n1 // 2) / (s1 - s0) / 1e9, 4), "unit": "Gtri/s",
+            single_ref = {"workload": wl, "n_gpus": 1,
                           "triangles_submitted_view_a": ref_view[0]["trianglesSubmitted"], "triangles_submitted_view_b": ref_view[1]["trianglesSubmitted"]}
+            if args.full:
+                single_ref.update({"steps": n1, "ms_per_step": round((s1 - s0) / n1 * 1e3, 4),
+                                   "value": round(tris_per_pair * (n1 // 2) / (s1 - s0) / 1e9, 4), "unit": "Gtri/s"})
             r1.close()
         dist.barrier()
     tris_view_a = (single_ref["triangles_submitted_view_a"] if single_ref else per_view[0]["trianglesSubmitted"])
@@ -655,7 +669,7 @@ def measure(args, workload, env):
 
     # ---- CPU baseline: the oracle replaying the same frame on the host (rank 0, N = 1) ----------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline_frames > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline_frames > 0:
         import orc
         prev = orc.frame(scene_with(scene, obj_b), view_b0, L.make_views(cam_b)[1], flags)   # history for view A
         sc_a = scene_with(scene, obj_a)
@@ -701,24 +715,28 @@ def measure(args, workload, env):
             # end to end over ALL scene triangles (LOD 0), i.e. including what culling removed
             "scene_gtri_per_s": round(scene.triangle_count_lod0() / (ms_per_step * 1e-3) / 1e9, 3),
             "clusters_rastered_per_step": clusters_per_frame, "triangle_records_per_step": recs, "bin_entries_per_step": bins, "pixel_blocks_per_step": blocks, "pixel_block_bytes_per_step": block_bytes,
-            "gpu_ms": {k: round(st[k], 4) for k in ("msClear", "msInstanceCulling", "msStage0", "msHzbStage0", "msStage1",
-                                                     "msHzbFinal", "msFrame", "msRasterCluster", "msRasterClip", "msRasterChunk")},
-            "kernel_launches": st["kernelLaunches"], "kernel_launches_schedule_frame": max(launches_seen),
             # frames a pass's tile schedule is reused for (chordvis_set_tile_schedule_keep; the library's default unless --tile-schedule-keep):
             # `kernel_launches` is a frame between two schedules, `kernel_launches_schedule_frame` one that makes them (every (this + 1)-th)
             "tile_schedule_keep_frames": r.tile_schedule_keep(),
             "tiles_touched_view_a": per_view[0]["tilesTouched"], "tiles_total": ((W + 63) // 64) * ((H + 63) // 64),
             "counts_view_a": {k: per_view[0][k] for k in ("countInstanceCulled", "countStage0Visible", "countStage0Rejected", "countStage1Visible", "trianglesSubmitted", "binEntries")},
             "counts_view_b": {k: per_view[1][k] for k in ("countInstanceCulled", "countStage0Visible", "countStage0Rejected", "countStage1Visible", "trianglesSubmitted", "binEntries")},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            # the same metric over `views` DISTINCT views along the street (0.5 m steps, two 180-degree cuts per loop), every frame culled
-            # against the HZB of the view before it; None where it does not apply (N > 1, the sub-pixel workloads, --no-path)
-            "moving_path": moving,
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "gpu_ms": {k: round(st[k], 4) for k in ("msClear", "msInstanceCulling", "msStage0", "msHzbStage0", "msStage1",
+                                                         "msHzbFinal", "msFrame", "msRasterCluster", "msRasterClip", "msRasterChunk")},
+                "kernel_launches": st["kernelLaunches"], "kernel_launches_schedule_frame": max(launches_seen),
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                # the same metric over `views` DISTINCT views along the street (0.5 m steps, two 180-degree cuts per loop), every frame culled
+                # against the HZB of the view before it; None where it does not apply (N > 1, the sub-pixel workloads, --no-path)
+                "moving_path": moving,
+            })
         if world > 1:
             line["exchange"] = exchange
-            one = single_ref["ms_per_step"] if single_ref else None
+            one = single_ref.get("ms_per_step") if single_ref else None
             if pipe and "ms_per_step" in pipe:
                 pipe["value"] = round(tris_per_pair / 2.0 / (pipe["ms_per_step"] * 1e-3) / 1e9, 4)
                 pipe["speedup_vs_single"] = round(one / pipe["ms_per_step"], 4) if one else None
@@ -734,7 +752,8 @@ def measure(args, workload, env):
                 if not ts or not chunk_bytes:
                     return None
                 return {"bytes_per_rank_in": int((world - 1) * chunk_bytes), "ms_min_over_ranks": round(min(ts), 4), "ms_max_over_ranks": round(max(ts), 4),
-                        "gbs": round((world - 1) * chunk_bytes / (min(ts) * 1e-3) / 1e9, 2)}
+                        # (4 significant digits: a small chunk over host-staged test collectives is well under 0.01 GB/s)
+                        "gbs": float("%.4g" % ((world - 1) * chunk_bytes / (min(ts) * 1e-3) / 1e9))}
             both_end = exchange != "lib"                   # (host-driven phases: one stamp covers the small end-of-frame exchange AND the image)
             line["exchange_gbs"] = {"cull": gbs("exchange_cull", chunks["cull"]), "hzb_mid": gbs("exchange_hzb", chunks["hzb_mid"]),
                                     "final": gbs("exchange_final", chunks["final"]),
@@ -755,13 +774,15 @@ def measure(args, workload, env):
             line["rccl_ranks"] = comm["ranks"] if (comm and exchange == "lib") else (dist.get_world_size() if backend == "nccl" else 0)
             line["rccl_version"] = (comm["nccl_version_code"] if comm else (_torch_nccl_version() if backend == "nccl" else None))
             line["collective_backend"] = backend
-        if single_ref is not None:
+        if single_ref is not None and args.full:
             line["single_gpu_same_workload"] = single_ref
             line["speedup_vs_single"] = round(single_ref["ms_per_step"] / ms_per_step, 4)
     r.close()
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     # ---- the RCCL image gather stayed under 250 GB/s into a rank (a ring schedule over xGMI: SURVEY 5): the peer-copy transport --
     #      n - 1 concurrent direct copies per rank -- measured in this same run, its line attached
-    if world > 1 and exchange == "lib" and not args.no_group_fallback:
+    if world > 1 and exchange == "lib" and args.full and not args.no_group_fallback:
         need = [bool(line is not None and line.get("rccl_schedule_ok") is False)]
         dist.broadcast_object_list(need, src=0)
         if need[0]:
@@ -892,8 +913,9 @@ def run_group(args, wl, scene, views, objs, flags, W, H, world, rank, dev, strea
         elapsed = time.perf_counter() - t0
         enq = g.enqueue_ms()
         sts = [r_.stats() for r_ in g.ranks]
+        outputs = read_outputs(g.ranks[0]) if args.dump_outputs else None
         pipe = None
-        if not args.no_pipelined:
+        if args.full and not args.no_pipelined:
             # the pipelined protocol on the same frames: the image of frame i travels (on its own copy streams) beside frame i + 1
             for r_ in g.ranks:
                 r_.enable_timers(0)
@@ -921,14 +943,15 @@ def run_group(args, wl, scene, views, objs, flags, W, H, world, rank, dev, strea
             r1.set_view(views[i & 1][0], views[i & 1][1], flags)
             r1.render_frame()
         n1 = max(8, min(args.steps, 100)) & ~1
-        for i in range(8):
-            frame1(i)
-        r1.sync()
-        s0 = time.perf_counter()
-        for i in range(n1):
-            frame1(i)
-        r1.sync()
-        s1 = time.perf_counter()
+        if args.full:                                    # (timed: --full; a plain run takes only the counts below)
+            for i in range(8):
+                frame1(i)
+            r1.sync()
+            s0 = time.perf_counter()
+            for i in range(n1):
+                frame1(i)
+            r1.sync()
+            s1 = time.perf_counter()
         ref_view = [None, None]
         for i in range(2):
             frame1(i)
@@ -938,7 +961,7 @@ def run_group(args, wl, scene, views, objs, flags, W, H, world, rank, dev, strea
         tris_total = tris_per_pair * (args.steps // 2) + (ref_view[0]["trianglesSubmitted"] if args.steps & 1 else 0)
         ms = elapsed / args.steps * 1e3
         single = {"workload": wl, "n_gpus": 1, "steps": n1, "ms_per_step": round((s1 - s0) / n1 * 1e3, 4),
-                  "value": round(tris_per_pair * (n1 // 2) / (s1 - s0) / 1e9, 4), "unit": "Gtri/s"}
+                  "value": round(tris_per_pair * (n1 // 2) / (s1 - s0) / 1e9, 4), "unit": "Gtri/s"} if args.full else None
         line = {"metric": "Gtri/s into 4K 64-bit visbuffer", "value": round(tris_total / elapsed / 1e9, 4), "unit": "Gtri/s",
                 "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 4) + (0 if args.no_rebalance else 4), "warmup_requested": args.warmup, "ms_per_step": round(ms, 4), "timed_region_s": round(elapsed, 6),
                 "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32+u64", "data": "synthetic",
@@ -954,8 +977,11 @@ def run_group(args, wl, scene, views, objs, flags, W, H, world, rank, dev, strea
                                "exchange_cull": round(st["msExchangeCull"], 4), "exchange_final": round(st["msExchangeFinal"], 4), "kernel_launches": st["kernelLaunches"],
                                "setup_kernels": round(st["msRasterCluster"], 4), "tile_kernels": round(st["msRasterChunk"], 4),
                                "host_enqueue_ms": round(enq[k], 4)} for k, st in enumerate(sts)],
-                "roofline": None, "cpu_baseline": None,
-                "single_gpu_same_workload": single, "speedup_vs_single": round(single["ms_per_step"] / ms, 4)}
+                "roofline": None, "cpu_baseline": None, "full": args.full}
+        if single is not None:
+            line.update({"single_gpu_same_workload": single, "speedup_vs_single": round(single["ms_per_step"] / ms, 4)})
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
     dist.barrier()
     return line
 
@@ -981,6 +1007,44 @@ def self_spawn(n):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
+
+
+DUMP_SAMPLE_PIXELS = 1 << 21       # --dump-outputs: an image of more pixels is written as a fixed sample of this many (20 B each: 40 MB)
+DUMP_SAMPLE_SEED = 0
+DUMP_COUNTS = ("countInstanceCulled", "countStage0Visible", "countStage0Rejected", "countStage1Visible", "trianglesSubmitted",
+               "triangleRecords", "triangleRecordsCompact", "binEntries", "pixelBlocks", "pixelBlockBytes", "overflow")
+
+
+def read_outputs(r):
+    """What a caller of the frame receives: the row-major visibility image (uint64 per pixel) and the frame's counters."""
+    st = r.stats()
+    return {"vis": r.read_visibility().reshape(r.height, r.width), "counts": [st[k] for k in DUMP_COUNTS]}
+
+
+def write_outputs(d, out):
+    """--dump-outputs: the last timed step's outputs as float32 / float64 .npy files, every value exact.
+
+    visibility_row_sums       (H, 2) float64  per image row, the sums of the words' high halves (depth bits) and low halves (cluster
+                                              slot + 1 << 8 | triangle): every pixel, < 2^44 per row
+    visibility_sample_index   (S,) float64    a fixed sample of pixels (row-major index; every pixel when the image has <= 2^21)
+    visibility_depth_sample   (S,) float32    their depth (the high half of the word as float32)
+    visibility_id_sample      (S,) float64    their low half
+    frame_counts              (len(DUMP_COUNTS),) float64   the frame's counters, in the order of DUMP_COUNTS"""
+    os.makedirs(d, exist_ok=True)
+    vis = out["vis"]
+    hi = (vis >> np.uint64(32)).astype(np.uint32)
+    lo = (vis & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    np.save(os.path.join(d, "visibility_row_sums.npy"),
+            np.stack([hi.sum(axis=1, dtype=np.uint64), lo.sum(axis=1, dtype=np.uint64)], axis=1).astype(np.float64))
+    n = vis.size
+    if n <= DUMP_SAMPLE_PIXELS:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(d, "visibility_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "visibility_depth_sample.npy"), hi.reshape(-1)[idx].view(np.float32))
+    np.save(os.path.join(d, "visibility_id_sample.npy"), lo.reshape(-1)[idx].astype(np.float64))
+    np.save(os.path.join(d, "frame_counts.npy"), np.array(out["counts"], dtype=np.float64))
 
 
 def scene_with(scene, objects):

@@ -278,7 +278,7 @@ def test_bench_two_ranks_self_spawned_on_one_device(gpu):
     """`python bench.py --gpus 2` with no launcher: re-executes itself under torch.distributed.run, two ranks on device 0
     (gloo, host-staged all-gathers: a one-GPU box cannot host two RCCL ranks), the N > 1 control flow of the bench --
     explicit stream, phases, both exchanges, the same-workload single-GPU reference and the speed-up field."""
-    line = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb"],
+    line = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--full"],
                       {"CHORDVIS_BENCH_BACKEND": "gloo", "CHORDVIS_BENCH_ONE_DEVICE": "1", "CHORDVIS_BENCH_ALSO": "street_x64_720p_hzb"})
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["exchange"] == "torch"
     # the line explains both multi-GPU configurations: the second workload (on the driver's run: BASELINE config 4) rides in `also`
@@ -306,11 +306,14 @@ def test_bench_two_ranks_self_spawned_on_one_device(gpu):
     assert line["warmup"] >= line["warmup_requested"] == 4
 
 
-def test_bench_two_ranks_group_fallback_on_one_device(gpu):
+def test_bench_two_ranks_group_fallback_on_one_device(gpu, tmp_path):
     """`--exchange group`: the third way to a scaling curve when RCCL does not come up -- rank 0 drives every device through
     ChordGroup (peer copies), the other processes wait.  Two 'devices' = device 0 twice here."""
-    line = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--exchange", "group"],
+    line = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--exchange", "group", "--full",
+                       "--dump-outputs", str(tmp_path / "out")],
                       {"CHORDVIS_BENCH_BACKEND": "gloo", "CHORDVIS_BENCH_ONE_DEVICE": "1"})
+    # (--dump-outputs on this path too: rank 0's image of the last timed frame)
+    assert sorted(os.listdir(tmp_path / "out")) == DUMP_FILES
     assert line["n_gpus"] == 2 and line["exchange"] == "group" and line["value"] > 0 and line["speedup_vs_single"] > 0
     assert len(line["phases_ms"]) == 2 and all("exchange_vis" in p for p in line["phases_ms"])
     # what the one-process transport costs the host, worker by worker
@@ -320,8 +323,38 @@ def test_bench_two_ranks_group_fallback_on_one_device(gpu):
     assert all(p["exchange_final"] > 0 and p["exchange_cull"] > 0 for p in line["phases_ms"])
 
 
+DUMP_FILES = sorted(["frame_counts.npy", "visibility_depth_sample.npy", "visibility_id_sample.npy", "visibility_row_sums.npy", "visibility_sample_index.npy"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain run (no --full): exactly --steps timed frames and the headline fields, nothing that takes runs of its own; with
+    --dump-outputs DIR it writes what the last timed step computed, float32 / float64 only, the same in two runs of the same arguments."""
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        lines.append(_run_bench(["--steps", "7", "--warmup", "4", "--workload", "street_720p_hzb", "--dump-outputs", str(d)], {}))
+        assert sorted(os.listdir(d)) == DUMP_FILES
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in DUMP_FILES})
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in line, k
+    assert line["full"] is False and line["steps"] == 7 and line["n_gpus"] == 1 and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] * 7 - line["timed_region_s"] * 1e3) < 1e-3 * 7 + 1e-6
+    for k in ("cpu_baseline", "moving_path", "roofline", "gpu_ms"):
+        assert k not in line, k
+    # the last of 7 timed steps is a frame at view A (frames alternate A, B, ... from the first timed step)
+    assert dumps[0]["frame_counts"][4] == line["counts_view_a"]["trianglesSubmitted"]
+    W, H = line["config"]["resolution"]
+    a = dumps[0]
+    assert a["visibility_row_sums"].shape == (H, 2) and len(a["visibility_sample_index"]) == W * H
+    assert a["visibility_depth_sample"].dtype == np.float32 and all(v.dtype == np.float64 for k, v in a.items() if k != "visibility_depth_sample")
+    assert (a["visibility_id_sample"] > 0).any() and (a["visibility_depth_sample"] > 0).any()
+    for k in a:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 def test_bench_single_gpu_line_has_the_contract_fields(gpu):
-    line = _run_bench(["--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--cpu-baseline-frames", "2", "--path-views", "8"], {})
+    line = _run_bench(["--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--cpu-baseline-frames", "2", "--path-views", "8", "--full"], {})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -340,5 +373,5 @@ def test_bench_single_gpu_line_has_the_contract_fields(gpu):
 
 def test_bench_without_stamps_renders_only_product_frames(gpu):
     """`--no-stamps` (kernel traces: tools/trace.sh): no event record in the whole process -- the line says so and carries no stamped times."""
-    line = _run_bench(["--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--cpu-baseline-frames", "0", "--no-stamps", "--no-path"], {})
+    line = _run_bench(["--steps", "6", "--warmup", "4", "--workload", "street_720p_hzb", "--cpu-baseline-frames", "0", "--no-stamps", "--no-path", "--full"], {})
     assert line["roofline"]["stamped_frames"] == 0 and line["gpu_ms"]["msFrame"] == 0.0 and line["value"] > 0 and line["moving_path"] is None

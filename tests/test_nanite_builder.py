@@ -339,16 +339,15 @@ def test_gltf_binary_uncompressed_file_is_byte_identical_to_cereals(tmp_path):
     assert ra[16:24] != rb[16:24] and ra[24:n] == rb[24:n]         # (string length differs, version tag + positions identical)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/external/include/cereal"), reason="the reference (vendored cereal + LZ4) exists only in the build container")
 def test_gltf_binary_written_by_the_library_is_read_by_the_references_cereal_and_lz4(tmp_path):
-    """The other direction, where the reference's sources are at hand: files the LIBRARY writes (its own cereal layout, its own
-    LZ4 encoder) through loadAsset's sequence built from the vendored cereal + LZ4 (make_gltf_binary_fixture --check)."""
-    import subprocess
-    exe = str(tmp_path / "check")
-    ref = "/root/reference/external"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", ref + "/include", "-I", ref + "/lz4/lib", os.path.join(GLTF_FIX, "make_gltf_binary_fixture.cpp"),
-                    ref + "/lz4/lib/lz4.c", "-o", exe], check=True)
-    pos, idx, uv = scenes.bumpy_sphere_mesh(48, 3)
+    """The other direction: files the LIBRARY writes (its own cereal layout, its own LZ4 encoder) through loadAsset's sequence
+    built from the vendored cereal + LZ4 (make_gltf_binary_fixture --check).  That reader ran over the library's files of the
+    mesh in tests/golden/gltf_library_mesh.npz (make_gltf_library_fixture.py); gltf_library_check.json holds each file's size and
+    SHA-1 with what the reader reported.  The library must write exactly those bytes today, and the report must match its asset."""
+    import hashlib
+    fix = json.load(open(os.path.join(GLTF_FIX, "gltf_library_check.json")))
+    mesh = np.load(os.path.join(GLTF_FIX, fix["mesh"]))
+    pos, idx, uv = mesh["positions"], mesh["indices"], mesh["texcoords0"]
     h = L.nanite_build(pos, idx, uv, keep_handle=True)
     a = L.BuiltAsset(h)
     hh = 1469598103934665603
@@ -364,10 +363,13 @@ def test_gltf_binary_written_by_the_library_is_read_by_the_references_cereal_and
     for g in a.groups:
         mix(g["meshletOffset"]); mix(g["meshletCount"]); mix(np.float32(g["parentError"]).view(np.uint32))
     for v in a.group_indices: mix(v)
-    for lz4 in (0, 1):
+    for lz4, rec in zip((0, 1), fix["files"]):
+        assert rec["lz4"] == lz4
         path = str(tmp_path / ("w%d.bin" % lz4))
         assert L.lib.chordvis_save_gltf_binary(h, path.encode(), lz4) == L.OK
-        out = subprocess.run([exe, "--check", path], capture_output=True, text=True, check=True).stdout.split()
+        data = open(path, "rb").read()
+        assert len(data) == rec["bytes"] and hashlib.sha1(data).hexdigest() == rec["sha1"], "the library no longer writes the bytes the reference read"
+        out = rec["reference_check"].split()
         assert out[0] == "OK" and int(out[2]) == lz4, out
         kv = dict(zip(out[1::2], out[2::2]))
         assert int(kv["positions"]) == len(a.positions) and int(kv["texcoords0"]) == len(a.texcoord0) and int(kv["meshlets"]) == len(a.meshlets)

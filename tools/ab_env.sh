@@ -4,7 +4,7 @@
 TAG=$1; NAME=$2; WLS=$3; REPS=${4:-2}; SUITE=${5:-}
 cd $GRAFT_REPO_ROOT; O=gpurun_out/$TAG; mkdir -p $O
 for rep in $(seq 1 $REPS); do for e in 1 0; do for wl in $WLS; do
-  env $NAME=$e timeout 300 python bench.py --workload $wl --steps 200 --cpu-baseline-frames 0 2>/dev/null | python -c "
+  env $NAME=$e timeout 300 python bench.py --full --workload $wl --steps 200 --cpu-baseline-frames 0 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); m=d.get('moving_path') or {}; g=d['gpu_ms']

@@ -25,7 +25,7 @@ for tag in "" ${TAGS//,/ }; do
       [ -z "$tag" ] && [ $(( f & 32755 )) -ne 0 ] && continue       # (the product build refuses measurement switches)
       nohzb=""; [ "$f" != "0" ] && [ "$f" != "65536" ] && [ "$f" != "32768" ] && nohzb="--no-hzb"
       n=$OUT/b_${tag:-product}_${wl}_$f
-      CHORDVIS_LIB=$lib python bench.py --steps $STEPS --warmup 20 --workload $wl --cpu-baseline-frames 0 --debug-flags $f $nohzb $EXTRA > $n.json 2> $n.err
+      CHORDVIS_LIB=$lib python bench.py --full --steps $STEPS --warmup 20 --workload $wl --cpu-baseline-frames 0 --debug-flags $f $nohzb $EXTRA > $n.json 2> $n.err
       python3 - <<PY
 import json
 try:

@@ -38,14 +38,14 @@ for step in "$@"; do
     trace)
       bash tools/trace.sh $TAG/trace_${a1:-c3} ${a1:+--workload $a1} > $OUT/timeline_${a1:-c3}.txt 2>&1; cat $OUT/timeline_${a1:-c3}.txt | tail -30
       find gpurun_out/$TAG -name "r_kernel_trace.csv" -size +20M -delete;;
-    bench)   python bench.py ${a1//+/ } > $OUT/bench_$(echo "$a1" | tr -c 'a-zA-Z0-9_\n' '_').json 2> $OUT/bench.err; cat $OUT/bench_$(echo "$a1" | tr -c 'a-zA-Z0-9_\n' '_').json | line "$a1";;
-    bench20) python bench.py --steps 20 --warmup 5 > $OUT/bench_default_20steps.json 2> $OUT/bench20.err; cat $OUT/bench_default_20steps.json | line "default, 20 steps (driver form)";;
-    bench200) python bench.py > $OUT/bench_default.json 2> $OUT/bench200.err; cat $OUT/bench_default.json | line "default, 200 steps";;
+    bench)   python bench.py --full ${a1//+/ } > $OUT/bench_$(echo "$a1" | tr -c 'a-zA-Z0-9_\n' '_').json 2> $OUT/bench.err; cat $OUT/bench_$(echo "$a1" | tr -c 'a-zA-Z0-9_\n' '_').json | line "$a1";;
+    bench20) python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default_20steps.json 2> $OUT/bench20.err; cat $OUT/bench_default_20steps.json | line "default, 20 steps (driver form)";;
+    bench200) python bench.py --full > $OUT/bench_default.json 2> $OUT/bench200.err; cat $OUT/bench_default.json | line "default, 200 steps";;
     ab)
       for rep in $(seq 1 ${a4:-2}); do for tag in product ${a1//,/ }; do for wl in ${a2//,/ }; do
         lib=$GRAFT_REPO_ROOT/chord_amd/_build/libchordvis.so; ev=_CALL_NOENV=1
         case "$tag" in product) ;; *=*) ev=$tag;; *) lib=$GRAFT_REPO_ROOT/chord_amd/_build/libchordvis_$tag.so;; esac     # (TAG with '=': an environment switch of the product library)
-        env $ev CHORDVIS_LIB=$lib python bench.py --workload ${wl//+/ } --steps ${a3:-200} --cpu-baseline-frames 0 --no-path 2>/dev/null | tee $OUT/ab_${tag}_${wl}_$rep.json | line "[$tag] $wl rep $rep"
+        env $ev CHORDVIS_LIB=$lib python bench.py --full --workload ${wl//+/ } --steps ${a3:-200} --cpu-baseline-frames 0 --no-path 2>/dev/null | tee $OUT/ab_${tag}_${wl}_$rep.json | line "[$tag] $wl rep $rep"
       done; done; done;;
     rank)
       ( cd /tmp && export TMPDIR=/tmp && env FRAMES=40 ${a4//+/ } rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$OUT/rank_$a1 -o r -- python $GRAFT_REPO_ROOT/tools/shard_rank.py $a1 $a2 $a3 > $GRAFT_REPO_ROOT/$OUT/rank_$a1.log 2>&1 )

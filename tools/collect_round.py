@@ -73,7 +73,7 @@ def sq_table(dirs, out, title, note):
 
 c3 = sq_table(["%s_sq1" % R, "%s_sq2" % R, "%s_sq3" % R, "%s_sq4" % R, "%s_sq5" % R, "%s_sq6" % R], "%s_config3_4k_hzb_sq_counters.md" % R,
               "%s config 3 (street_4k_hzb) -- SQ counters per kernel launch" % R,
-              "Averages over `bench.py --steps 12 --warmup 4`, three separate `rocprofv3 --pmc` passes (tools/pmc.sh), the round's final kernels.")
+              "Averages over `bench.py --full --steps 12 --warmup 4`, three separate `rocprofv3 --pmc` passes (tools/pmc.sh), the round's final kernels.")
 c5 = sq_table(["%s_sq1_c5" % R, "%s_sq2_c5" % R], "%s_config5_sq_counters.md" % R,
               "%s block kernel -- SQ counters per launch on `subpixel_64m --debug-flags 65536` (config 5 at 1/16 size, block kernel forced: 524 288 clusters per launch)" % R,
               "Two separate `rocprofv3 --pmc` passes (tools/pmc.sh).")

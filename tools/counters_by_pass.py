@@ -26,7 +26,7 @@ for path in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", R + "_sq[0-9]", "r
             seen.add(r["Dispatch_Id"])
             dur[g].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 print("# %s config 3 (street_4k_hzb): `raster_tile_kernel` counters per launch, grouped by the launch's workgroups\n" % R)
-print("Source: the per-dispatch rows of the six `rocprofv3 --pmc` passes of `tools/round_profile.sh %s` (`bench.py --steps 12 --warmup 4`; tools/counters_by_pass.py)." % R)
+print("Source: the per-dispatch rows of the six `rocprofv3 --pmc` passes of `tools/round_profile.sh %s` (`bench.py --full --steps 12 --warmup 4`; tools/counters_by_pass.py)." % R)
 print("2 041 workgroups = a first pass under the schedule the same pass of the frame before made (one workgroup more: it makes the next one);")
 print("2 040 = a direct second pass, or a first pass under a schedule kernel's schedule (the bench's moving-path run with fresh schedules, a context's first frame).\n")
 names = sorted({c for g in agg for c in agg[g]})

@@ -1,6 +1,7 @@
 #!/bin/bash
 # SQ counter passes for bench.py (separate runs, counters only). Usage: tools/pmc.sh <tag> "<counters>" [bench args]
 TAG=$1; CNT=$2; shift 2
+set -- --full "$@"     # (the counters average over every launch of the process, the frames behind the timed region included)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc $CNT --output-format csv -d $OUT -o r -- python $GRAFT_REPO_ROOT/bench.py --steps 12 --warmup 4 --cpu-baseline-frames 0 $* > $OUT/log.txt 2>&1

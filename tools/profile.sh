@@ -7,7 +7,7 @@ TAG=${1:-prof}; shift || true
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 40 --warmup 4 --cpu-baseline-frames 0 $*"
+ARGS="--full --steps 40 --warmup 4 --cpu-baseline-frames 0 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- python $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/stats.log 2>&1
 if [ "${STATS_ONLY:-0}" != "1" ]; then
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o r -- python $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/pmc_fetch.log 2>&1

@@ -39,6 +39,8 @@ CHORDVIS_LIB=$GRAFT_REPO_ROOT/chord_amd/_build/libchordvis_prof.so python tools/
 CHORDVIS_LIB=$GRAFT_REPO_ROOT/chord_amd/_build/libchordvis_prof.so python tools/setup_profile.py subpixel_64m 65536 > gpurun_out/${R}_setup_profile_64m.txt 2>&1
 fi
 cd $GRAFT_REPO_ROOT
+# the bench.py lines below are full runs: collect_round.py reads their stamped kernel times, roofline and moving path
+python() { if [ "${1:-}" = bench.py ]; then shift; command python bench.py --full "$@"; else command python "$@"; fi; }
 python bench.py > gpurun_out/${R}_bench_default.json 2> gpurun_out/${R}_bench_default.err
 python bench.py --steps 20 --warmup 5 --cpu-baseline-frames 0 > gpurun_out/${R}_bench_default_20steps.json 2>/dev/null
 python bench.py --workload street_x64_4k_hzb --cpu-baseline-frames 0 > gpurun_out/${R}_bench_c4.json 2>/dev/null

@@ -7,7 +7,7 @@ IFS=';' read -ra SETS <<< "$*"
 i=0
 for a in "${SETS[@]}"; do
   [ -z "$a" ] && continue
-  python bench.py --steps 200 --warmup 20 --cpu-baseline-frames 0 $a > $OUT/bench_$i.json 2> $OUT/bench_$i.err
+  python bench.py --full --steps 200 --warmup 20 --cpu-baseline-frames 0 $a > $OUT/bench_$i.json 2> $OUT/bench_$i.err
   python - <<PY
 import json
 try:
