@@ -79,6 +79,7 @@ int alloc_hzb(ChordCtx* c, HzbBuffers& h)
 
 int configure_targets(ChordCtx* c, uint64_t* external)
 {
+    c->resolveFrame = false;
     // visibility words (sharded: rank-major tile slots, ranks * slotsPerRank * 64 * 64 words)
     const uint32_t N = c->shard.ranks;
     c->tilesX = (c->width + CHORD_TILE - 1) >> CHORD_TILE_SHIFT; c->tilesY = (c->height + CHORD_TILE - 1) >> CHORD_TILE_SHIFT;
@@ -236,6 +237,7 @@ int do_raster(ChordCtx* c, const CmdList& in)
     c->pendingClear = false;
     if (e != hipSuccess) return fail(c, CHORDVIS_E_HIP, "launch_raster", e);
     CHORD_HIP(c, hipGetLastError());
+    c->resolveFrame = true; c->resolveStale = false;   // the image now holds ids of this frame's objects and view (chordvis_resolve_attributes)
     return CHORDVIS_OK;
 }
 
@@ -406,10 +408,10 @@ int chordvis_destroy(ChordCtx* c)
     if (c->sharedScene) {       // a depth-view child: the scene buffers are the parent's
         c->dPrims = nullptr; c->dGroups = nullptr; c->dMeshlets = nullptr; c->dGroupIndices = nullptr; c->dMeshletData = nullptr;
         c->dPositions = nullptr; c->dObjStatic = nullptr; c->dGroupRefs = nullptr; c->dMaterials = nullptr; c->dTexAlpha = nullptr;
-        c->dTexcoords = nullptr; c->dBvhNodes = nullptr;
+        c->dTexcoords = nullptr; c->dBvhNodes = nullptr; c->dMeshletLod = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
-    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned);
+    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -470,6 +472,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     bool bvhComplete = nB.back() > 0;
 
     std::vector<DMeshlet> meshlets(nM);
+    std::vector<uint8_t> meshletLod(nM);
     std::vector<DGroup> groups(nG);
     std::vector<uint32_t> gidx(nI), mdata(nD);
     std::vector<float> pos((size_t)nV * 3);
@@ -489,6 +492,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
             }
             d.dataOffset = m.dataOffset + dB[a];
             d.vertexBase = 0xFFFFFFFFu;
+            meshletLod[mB[a] + i] = (uint8_t)std::min(m.lod, 255u);   // (the resolve's debug view clamps to the 12-entry palette)
         }
         for (uint32_t i = 0; i < as.meshletGroupCount; i++) {
             const ChordMeshletGroup& g = as.meshletGroups[i];
@@ -716,8 +720,13 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
             }
         }
     }
+    // texture coordinates: the masked buckets sample with them, chordvis_resolve_attributes interpolates them.  A scene without
+    // masked materials whose streams do not match its vertex counts was accepted before the resolve existed: it still is, without uvs.
     std::vector<float> uvs;
-    if (anyMasked) {
+    bool uvsUsable = true;
+    for (uint32_t a = 0; a < s->assetCount; a++)
+        if (s->assets[a].texcoord0 && s->assets[a].texcoord0Count && s->assets[a].texcoord0Count != s->assets[a].vertexCount) uvsUsable = false;
+    if (anyMasked || uvsUsable) {
         bool anyUv = false;
         for (uint32_t a = 0; a < s->assetCount; a++) anyUv = anyUv || (s->assets[a].texcoord0 && s->assets[a].texcoord0Count);
         if (anyUv) {
@@ -740,7 +749,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     if (!vec.empty()) CHORD_HIP(c, hipMemcpy(dst, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice));
     UP(c->dMeshlets, meshlets) UP(c->dGroups, groups) UP(c->dGroupIndices, gidx) UP(c->dMeshletData, mdata)
     UP(c->dPositions, pos) UP(c->dPrims, c->hPrims) UP(c->dObjStatic, c->hObjStatic) UP(c->dGroupRefs, refs)
-    UP(c->dMaterials, dmats)
+    UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod)
     if (!bvh.empty()) { UP(c->dBvhNodes, bvh) } else dfree(c->dBvhNodes);
     c->bvhComplete = bvhComplete;
     if (!alpha.empty()) { UP(c->dTexAlpha, alpha) } else dfree(c->dTexAlpha);
@@ -752,6 +761,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     CHORD_HIP(c, hipMemcpy(c->dObjectsOwned, s->objects, sizeof(ChordObject) * s->objectCount, hipMemcpyHostToDevice));
     c->dObjects = c->dObjectsOwned;
     c->sceneLoaded = true;
+    c->resolveFrame = false;
     c->historySlot = 0;
     c->pendingTailSlot = 0;
     if ((rc = chord::prepare_cull_exchange(c))) { c->sceneLoaded = false; return rc; }     // (a sharded context: the rank-mask exchange buffer of this scene)
@@ -764,6 +774,7 @@ int chordvis_update_objects(ChordCtx* c, const ChordObject* hostObjects, uint32_
     if (!c || !c->sceneLoaded || !hostObjects || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "update_objects: count must equal the uploaded scene's objectCount");
     CHORD_HIP(c, hipMemcpyAsync(c->dObjectsOwned, hostObjects, sizeof(ChordObject) * count, hipMemcpyHostToDevice, c->stream));
     c->dObjects = c->dObjectsOwned;
+    c->resolveStale = true;
     return CHORDVIS_OK;
 }
 
@@ -787,6 +798,7 @@ int chordvis_set_view(ChordCtx* c, const ChordCameraView* view, const ChordInsta
     // which publishes it for the later passes; see flush_view() for passes called out of frame order
     c->viewDirty = true;
     c->viewSet = true;
+    c->resolveStale = true;
     return CHORDVIS_OK;
 }
 
@@ -1396,6 +1408,30 @@ int chordvis_visibility_mark(ChordCtx* c, ChordCountAndCmd drawed, ChordTileMark
     out->markerDim[0] = mW; out->markerDim[1] = mH;
     return CHORDVIS_OK;
 }
+
+// ---------------------------------------------------------------- per-pixel attributes of the visible triangle --
+
+int chordvis_resolve_attributes(ChordCtx* c, ChordCountAndCmd drawed, const ChordResolveDesc* desc, const ChordResolveTargets* t)
+{
+    if (!c || !c->dVis || !c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no scene / gbuffer");
+    if (!c->resolveFrame) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no frame rendered yet");
+    if (c->resolveStale)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: chordvis_update_objects / chordvis_set_view came after the frame (the image's matrices are gone)");
+    if (!drawed.count || !drawed.cmds) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: null command list");
+    if (!t || !(t->barycentrics || t->baryDdx || t->baryDdy || t->uv || t->uvGrad || t->positionRS || t->motionVector || t->debugRGBA8))
+        return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no target");
+    const ChordResolveDesc d = desc ? *desc : ChordResolveDesc{};
+    if (t->debugRGBA8 && d.debugMode > CHORD_NANITE_DEBUG_BARYCENTRICS) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: debugMode beyond 4");
+    if (drawed.cmds == c->lists[0].cmds) { launch_full_list(c); CHORD_HIP(c, hipGetLastError()); }
+    const unsigned long long* vis = (const unsigned long long*)(c->shard.ranks > 1 ? c->dVisResolved : c->dVis);
+    // (pipelined group frames: the image is gathered and resolved beside the context's stream)
+    if (c->visReadyEvent[0]) CHORD_HIP(c, hipStreamWaitEvent(c->stream, c->visReadyEvent[0], 0));
+    chord::launch_resolve_attributes(c, vis, drawed.cmds, drawed.count, d, *t);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+void* chordvis_stream(ChordCtx* c) { return c ? (void*)c->stream : nullptr; }
 
 int chordvis_prepare_shading_tile_param(ChordCtx* c, uint32_t shadingType, const ChordTileMarker* marker, ChordShadingTiles* out)
 {

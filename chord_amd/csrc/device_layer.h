@@ -308,6 +308,7 @@ struct ChordCtx {
     chord::DMaterial* dMaterials = nullptr;   // per material: what the masked buckets sample
     uint8_t* dTexAlpha = nullptr;             // alpha channel of every level of every texture, back to back
     float* dTexcoords = nullptr;              // float2 per vertex (textureCoord0Buffer), or null
+    uint8_t* dMeshletLod = nullptr;           // per device meshlet: ChordMeshlet::lod (DMeshlet carries vertexBase instead; the resolve's debug view reads it)
     bool anyMasked = false;
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
     chord::DBVHNode* dBvhNodes = nullptr;   // every primitive's tree (or null: the scene came without)
@@ -427,6 +428,8 @@ struct ChordCtx {
     uint32_t binCap = 0, tilesX = 0, tilesY = 0;
     chord::ClipTri* dClipTris = nullptr;
     uint32_t clipTriCap = 0;
+    bool resolveFrame = false;         // a raster pass of the main view has written the image since the last upload / gbuffer (chordvis_resolve_attributes)
+    bool resolveStale = false;         // ... and chordvis_update_objects / chordvis_set_view came after it: the image's matrices are gone
     uint32_t* dTileMarker = nullptr;   // [markerDim.y][markerDim.x] uint4: shading types present per 8x8 pixels
     uint32_t* dShadingTiles = nullptr; // [markerDim.x * markerDim.y] uint2 + {count, pad, uint4 dispatch args} behind them
     uint32_t* dTileOrder = nullptr;    // [1 + tileItemCap]: item count, then work items heaviest first
@@ -510,6 +513,8 @@ int tile_layout(uint32_t tilesX, uint32_t tilesY, uint32_t ranks, const uint32_t
 int install_tile_owners(ChordCtx* c);                                     // chordvis_abi.cpp: c->tileOwners -> device tables
 void launch_visibility_mark(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount, uint32_t* marker);
 void launch_shading_tiles(ChordCtx* c, const uint32_t* marker, uint32_t shadingType, uint32_t* tiles, uint32_t* count, uint32_t* args);
+void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                               const ChordResolveDesc& desc, const ChordResolveTargets& targets);   // kernels_resolve.hip
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

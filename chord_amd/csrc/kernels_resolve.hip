@@ -1,0 +1,263 @@
+// chordvis — per-pixel attributes of the visible triangle (the visibility buffer's consumers' second step).
+// Reference: install/resource/shader/lighting.hlsl:278-371 (per-pixel triangle resolve), nanite_shared.hlsli:111-179
+// (getTriangleMiscInfo), material.hlsli:41-64 (uv, uv gradients, motion, positionRS), base.hlsli:457-495
+// (calculateTriangleBarycentrics) and nanite_debug.hlsl:30-43,104-130 (the debug colours).
+//
+//   resolve_attributes_kernel   a wave per 16 x 4 pixels.  Its lanes load their visibility words; a ballot loop names one
+//                               leader lane per distinct low word (slot | triangle) of the block; each leader fetches its
+//                               triangle (command -> object / meshlet -> index word -> three vertices) and forms the per-vertex
+//                               products (clip position, translated-world position, the two motion clip positions, uv); every
+//                               pixel reads its leader's values through ds_bpermute and finishes the per-pixel arithmetic.
+//                               Stores: 16 bytes per lane for the float4 images, 256 contiguous bytes per wave and row.
+//
+// The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
+// does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
+
+#include "device_layer.h"
+#include "device_math.h"
+
+namespace chord {
+
+// simpleHash / simpleHashColor -- base.hlsli:112-128
+__device__ __forceinline__ uint32_t simple_hash(uint32_t a)
+{
+    a = (a + 0x7ed55d16u) + (a << 12);
+    a = (a ^ 0xc761c23cu) ^ (a >> 19);
+    a = (a + 0x165667b1u) + (a << 5);
+    a = (a + 0xd3a2646cu) ^ (a << 9);
+    a = (a + 0xfd7046c5u) + (a << 3);
+    a = (a ^ 0xb55a4f09u) ^ (a >> 16);
+    return a;
+}
+__device__ __forceinline__ f3 simple_hash_color(uint32_t i)
+{
+    const uint32_t h = simple_hash(i);
+    return f3{(float)(h & 255u) / 255.0f, (float)((h >> 8) & 255u) / 255.0f, (float)((h >> 16) & 255u) / 255.0f};
+}
+
+// kLODDebugColor -- nanite_debug.hlsl:30-43 (kNaniteMaxLODCount = 12 entries)
+__constant__ float kLodDebugColor[12][3] = {
+    {1.0f, 0.0f, 0.0f}, {0.7f, 0.3f, 0.0f}, {0.4f, 0.6f, 0.0f}, {0.1f, 0.9f, 0.0f}, {0.0f, 1.0f, 0.2f}, {0.0f, 0.5f, 0.6f},
+    {0.0f, 0.1f, 0.8f}, {0.0f, 0.0f, 1.0f}, {0.1f, 0.1f, 0.8f}, {0.2f, 0.2f, 0.6f}, {0.0f, 0.4f, 0.7f}, {0.2f, 0.6f, 0.3f},
+};
+
+__device__ __forceinline__ uint32_t pack_unorm8(float c) { return (uint32_t)(saturatef(c) * 255.0f + 0.5f); }
+
+// (a0 * b.x + a1 * b.y) + a2 * b.z -- material.hlsli:52-61's interpolation, one component
+__device__ __forceinline__ float interp3(float a0, float a1, float a2, f3 b) { return (a0 * b.x + a1 * b.y) + a2 * b.z; }
+
+__device__ __forceinline__ float lane_read(float v, int src) { return __shfl(v, src, 64); }
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src, 64); }
+
+struct ResolveArgs {
+    const unsigned long long* vis;
+    const ChordDrawCmd* cmds;
+    const uint32_t* cmdCount;
+    const ChordObject* objects;
+    const DObjStatic* objStatic;
+    const DPrim* prims;
+    const DMeshlet* meshlets;
+    const uint8_t* meshletLod;
+    const uint32_t* meshletData;
+    const float* positions;
+    const float* texcoords;            // null: (0, 0)
+    const DView* view;
+    uint32_t W, H, blocksX, objectCount, meshletCount;
+    uint32_t useNoJitter, debugMode;
+    uint32_t want;                     // RESOLVE_* bits of the non-null targets
+    ChordMat4 vpNoJitter, vpLastNoJitter;
+    ChordResolveTargets t;
+};
+#define RESOLVE_BARY 1u
+#define RESOLVE_DDX 2u
+#define RESOLVE_DDY 4u
+#define RESOLVE_UV 8u
+#define RESOLVE_UVGRAD 16u
+#define RESOLVE_POS 32u
+#define RESOLVE_MOTION 64u
+#define RESOLVE_DEBUG 128u
+
+__global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t block = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t bx = block % a.blocksX, by = block / a.blocksX;
+    const uint32_t x = bx * 16u + (lane & 15u), y = by * 4u + (lane >> 4);
+    const bool inside = x < a.W && y < a.H;                          // (the grid's last workgroup may hold waves past the image)
+    const size_t pix = (size_t)y * a.W + x;
+    const uint32_t n = *a.cmdCount;
+    const uint32_t low = inside ? (uint32_t)a.vis[pix] : 0u;
+    const uint32_t slot = ((low >> 8) & CHORD_MAX_INSTANCE_ID) - 1u;   // base.hlsli:443-447
+    const bool covered = low != 0u && slot < n;
+
+    // one leader per distinct (slot, triangle) of the wave
+    int leader = (int)lane;
+    uint64_t pending = __ballot(covered);
+    while (pending) {
+        const int l = __ffsll((unsigned long long)pending) - 1;
+        const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)low, l);
+        const bool mine = covered && low == key;
+        if (mine) leader = l;
+        pending &= ~__ballot(mine);
+    }
+    const bool isLeader = covered && leader == (int)lane;
+
+    // ---- per-triangle set-up (leaders): getTriangleMiscInfo, nanite_shared.hlsli:111-179 --------------------------------
+    bool ok = false;
+    float phs[3][4] = {}, prs[3][3] = {}, cur[3][3] = {}, last[3][3] = {}, uvv[3][2] = {};
+    uint32_t meshletHashId = 0u, triWord = 0u, lod = 0u;
+    if (isLeader) {
+        const ChordDrawCmd cmd = a.cmds[slot];
+        const uint32_t tri = low & 0xFFu;
+        if (cmd.objectId < a.objectCount && cmd.meshletId < a.meshletCount) {
+            const DMeshlet& m = a.meshlets[cmd.meshletId];
+            const uint32_t V = m.vertexTriangleCount & 0xFFu, T = (m.vertexTriangleCount >> 8) & 0xFFu;
+            if (tri < T) {
+                ok = true;
+                const ChordObject& obj = a.objects[cmd.objectId];
+                const DView& dv = *a.view;
+                const Mat4 M = load_mat(obj.basicData.localToTranslatedWorld);
+                const Mat4 Ml = load_mat(obj.basicData.localToTranslatedWorldLastFrame);
+                const Mat4 mvp = mul_mm(load_mat(dv.iv.translatedWorldToClip), M);          // the raster's matrix (kernels_cull.hip obj_mvp)
+                const Mat4 mCur = a.useNoJitter ? mul_mm(load_mat(a.vpNoJitter), M) : mvp;
+                const Mat4 mLast = a.useNoJitter ? mul_mm(load_mat(a.vpLastNoJitter), Ml)
+                                                 : mul_mm(load_mat(dv.view.translatedWorldToClipLastFrame), Ml);   // obj_mvp_last
+                triWord = a.meshletData[m.dataOffset + V + tri];
+                meshletHashId = cmd.meshletId - a.prims[a.objStatic[cmd.objectId].prim].assetMeshletBase;   // the reference's cmd.y
+                lod = a.meshletLod[cmd.meshletId];
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const uint32_t vi = a.meshletData[m.dataOffset + ((triWord >> (8 * i)) & 0xFFu)] + m.vertexBase;
+                    const float px = a.positions[(size_t)vi * 3], py = a.positions[(size_t)vi * 3 + 1], pz = a.positions[(size_t)vi * 3 + 2];
+                    const f4 h = mul_mv(mvp, px, py, pz, 1.0f);
+                    phs[i][0] = h.x; phs[i][1] = h.y; phs[i][2] = h.z; phs[i][3] = h.w;
+                    const f4 r = mul_mv(M, px, py, pz, 1.0f);
+                    prs[i][0] = r.x; prs[i][1] = r.y; prs[i][2] = r.z;
+                    const f4 cc = mul_mv(mCur, px, py, pz, 1.0f);
+                    cur[i][0] = cc.x; cur[i][1] = cc.y; cur[i][2] = cc.w;
+                    const f4 ll = mul_mv(mLast, px, py, pz, 1.0f);
+                    last[i][0] = ll.x; last[i][1] = ll.y; last[i][2] = ll.w;
+                    if (a.texcoords) { uvv[i][0] = a.texcoords[(size_t)vi * 2]; uvv[i][1] = a.texcoords[(size_t)vi * 2 + 1]; }
+                }
+            }
+        }
+    }
+
+    // ---- per pixel ------------------------------------------------------------------------------------------------------
+    const bool hit = covered && lane_read((uint32_t)ok, leader) != 0u;
+    float P[3][4];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) P[i][k] = lane_read(phs[i][k], leader);
+
+    // screenUvToNdcUv((dispatchPos + 0.5) * texelSize) -- material.hlsli:38, base.hlsli:137-143
+    const DView& dv = *a.view;
+    const float invW = dv.view.renderDimension[2], invH = dv.view.renderDimension[3];
+    const float su = ((float)x + 0.5f) * invW, sv = ((float)y + 0.5f) * invH;
+    const float pcx = 2.0f * (su - 0.5f), pcy = 2.0f * (0.5f - sv);
+
+    // calculateTriangleBarycentrics -- base.hlsli:457-495, statement by statement
+    const f3 rcpW = {1.0f / P[0][3], 1.0f / P[1][3], 1.0f / P[2][3]};
+    const float p0x = P[0][0] * rcpW.x, p0y = P[0][1] * rcpW.x;
+    const float p1x = P[1][0] * rcpW.y, p1y = P[1][1] * rcpW.y;
+    const float p2x = P[2][0] * rcpW.z, p2y = P[2][1] * rcpW.z;
+    const f3 p120x = {p1x, p2x, p0x}, p120y = {p1y, p2y, p0y}, p201x = {p2x, p0x, p1x}, p201y = {p2y, p0y, p1y};
+    const f3 cdx = {p201y.x - p120y.x, p201y.y - p120y.y, p201y.z - p120y.z};
+    const f3 cdy = {p120x.x - p201x.x, p120x.y - p201x.y, p120x.z - p201x.z};
+    const f3 C = {cdx.x * (pcx - p120x.x) + cdy.x * (pcy - p120y.x),
+                  cdx.y * (pcx - p120x.y) + cdy.y * (pcy - p120y.y),
+                  cdx.z * (pcx - p120x.z) + cdy.z * (pcy - p120y.z)};
+    const f3 G = {C.x * rcpW.x, C.y * rcpW.y, C.z * rcpW.z};
+    const float Hs = dot3(C, rcpW);
+    const float rcpH = 1.0f / Hs;
+    const f3 bary = {G.x * rcpH, G.y * rcpH, G.z * rcpH};
+    const f3 gdx = {cdx.x * rcpW.x, cdx.y * rcpW.y, cdx.z * rcpW.z};
+    const f3 gdy = {cdy.x * rcpW.x, cdy.y * rcpW.y, cdy.z * rcpW.z};
+    const float hdx = dot3(cdx, rcpW), hdy = dot3(cdy, rcpW);
+    const float rcpH2 = rcpH * rcpH, sx = 2.0f * invW, sy = -2.0f * invH;
+    const f3 ddx = {((gdx.x * Hs - G.x * hdx) * rcpH2) * sx, ((gdx.y * Hs - G.y * hdx) * rcpH2) * sx, ((gdx.z * Hs - G.z * hdx) * rcpH2) * sx};
+    const f3 ddy = {((gdy.x * Hs - G.x * hdy) * rcpH2) * sy, ((gdy.y * Hs - G.y * hdy) * rcpH2) * sy, ((gdy.z * Hs - G.z * hdy) * rcpH2) * sy};
+
+    if (a.want & RESOLVE_BARY)
+        if (inside) reinterpret_cast<float4*>(a.t.barycentrics)[pix] = hit ? make_float4(bary.x, bary.y, bary.z, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (a.want & RESOLVE_DDX)
+        if (inside) reinterpret_cast<float4*>(a.t.baryDdx)[pix] = hit ? make_float4(ddx.x, ddx.y, ddx.z, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (a.want & RESOLVE_DDY)
+        if (inside) reinterpret_cast<float4*>(a.t.baryDdy)[pix] = hit ? make_float4(ddy.x, ddy.y, ddy.z, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (a.want & (RESOLVE_UV | RESOLVE_UVGRAD)) {
+        float U[3][2];
+#pragma unroll
+        for (int i = 0; i < 3; i++) { U[i][0] = lane_read(uvv[i][0], leader); U[i][1] = lane_read(uvv[i][1], leader); }
+        if (a.want & RESOLVE_UV) {
+            const float u = interp3(U[0][0], U[1][0], U[2][0], bary), v = interp3(U[0][1], U[1][1], U[2][1], bary);
+            if (inside) reinterpret_cast<float2*>(a.t.uv)[pix] = hit ? make_float2(u, v) : make_float2(0.0f, 0.0f);
+        }
+        if (a.want & RESOLVE_UVGRAD) {
+            const float4 g = make_float4(interp3(U[0][0], U[1][0], U[2][0], ddx), interp3(U[0][1], U[1][1], U[2][1], ddx),
+                                         interp3(U[0][0], U[1][0], U[2][0], ddy), interp3(U[0][1], U[1][1], U[2][1], ddy));
+            if (inside) reinterpret_cast<float4*>(a.t.uvGrad)[pix] = hit ? g : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    if (a.want & RESOLVE_POS) {
+        float R[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) R[i][k] = lane_read(prs[i][k], leader);
+        const float4 p = make_float4(interp3(R[0][0], R[1][0], R[2][0], bary), interp3(R[0][1], R[1][1], R[2][1], bary),
+                                     interp3(R[0][2], R[1][2], R[2][2], bary), 1.0f);
+        if (inside) reinterpret_cast<float4*>(a.t.positionRS)[pix] = hit ? p : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if (a.want & RESOLVE_MOTION) {
+        float Cc[3][3], Ll[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) { Cc[i][k] = lane_read(cur[i][k], leader); Ll[i][k] = lane_read(last[i][k], leader); }
+        const float cx = interp3(Cc[0][0], Cc[1][0], Cc[2][0], bary), cy = interp3(Cc[0][1], Cc[1][1], Cc[2][1], bary);
+        const float cz = interp3(Cc[0][2], Cc[1][2], Cc[2][2], bary);
+        const float lx = interp3(Ll[0][0], Ll[1][0], Ll[2][0], bary), ly = interp3(Ll[0][1], Ll[1][1], Ll[2][1], bary);
+        const float lz = interp3(Ll[0][2], Ll[1][2], Ll[2][2], bary);
+        // material.hlsli:59
+        const float mx = (lx / lz - cx / cz) * 0.5f, my = (ly / lz - cy / cz) * -0.5f;
+        if (inside) reinterpret_cast<float2*>(a.t.motionVector)[pix] = hit ? make_float2(mx, my) : make_float2(0.0f, 0.0f);
+    }
+    if (a.want & RESOLVE_DEBUG) {
+        const uint32_t mId = lane_read(meshletHashId, leader), tw = lane_read(triWord, leader);
+        const uint32_t lv = min(lane_read(lod, leader), 11u);
+        // nanite_debug.hlsl:104-130
+        const f3 lodColor = {kLodDebugColor[lv][0], kLodDebugColor[lv][1], kLodDebugColor[lv][2]};
+        f3 c;
+        if (a.debugMode == CHORD_NANITE_DEBUG_MESHLET) c = simple_hash_color(mId);
+        else if (a.debugMode == CHORD_NANITE_DEBUG_TRIANGLE) c = simple_hash_color(tw);
+        else if (a.debugMode == CHORD_NANITE_DEBUG_LOD) c = lodColor;
+        else if (a.debugMode == CHORD_NANITE_DEBUG_LOD_MESHLET) {
+            const f3 mc = simple_hash_color(mId);
+            c = f3{powf(mc.x, 0.5f) * lodColor.x, powf(mc.y, 0.5f) * lodColor.y, powf(mc.z, 0.5f) * lodColor.z};
+        } else c = bary;
+        const uint32_t rgba = pack_unorm8(c.x) | pack_unorm8(c.y) << 8 | pack_unorm8(c.z) << 16 | 0xFF000000u;
+        if (inside) a.t.debugRGBA8[pix] = hit ? rgba : 0xFF000000u;
+    }
+}
+
+void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                               const ChordResolveDesc& desc, const ChordResolveTargets& t)
+{
+    ResolveArgs a;
+    a.vis = vis; a.cmds = cmds; a.cmdCount = cmdCount;
+    a.objects = c->dObjects; a.objStatic = c->dObjStatic; a.prims = c->dPrims; a.meshlets = c->dMeshlets; a.meshletLod = c->dMeshletLod;
+    a.meshletData = c->dMeshletData; a.positions = c->dPositions; a.texcoords = c->dTexcoords; a.view = c->dView;
+    a.W = c->width; a.H = c->height; a.blocksX = (c->width + 15u) / 16u;
+    a.objectCount = c->objectCount; a.meshletCount = c->meshletCount;
+    a.useNoJitter = desc.useNoJitter; a.debugMode = desc.debugMode;
+    a.want = (t.barycentrics ? RESOLVE_BARY : 0u) | (t.baryDdx ? RESOLVE_DDX : 0u) | (t.baryDdy ? RESOLVE_DDY : 0u) | (t.uv ? RESOLVE_UV : 0u) |
+             (t.uvGrad ? RESOLVE_UVGRAD : 0u) | (t.positionRS ? RESOLVE_POS : 0u) | (t.motionVector ? RESOLVE_MOTION : 0u) |
+             (t.debugRGBA8 ? RESOLVE_DEBUG : 0u);
+    a.vpNoJitter = desc.translatedWorldToClipNoJitter; a.vpLastNoJitter = desc.translatedWorldToClipLastFrameNoJitter;
+    a.t = t;
+    const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
+    CHORD_LAUNCH(c, resolve_attributes_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+}
+
+} // namespace chord

@@ -36,6 +36,23 @@ class ShadingTiles(C.Structure):
     _fields_ = [("tileCmd", C.c_void_p), ("count", C.c_void_p), ("dispatchIndirect", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class ResolveDesc(C.Structure):
+    """ChordResolveDesc: matrices as 16 floats, glm column-major (the layout of ChordMat4)."""
+    _fields_ = [("translatedWorldToClipNoJitter", C.c_float * 16), ("translatedWorldToClipLastFrameNoJitter", C.c_float * 16),
+                ("useNoJitter", C.c_uint32), ("debugMode", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class ResolveTargets(C.Structure):
+    """ChordResolveTargets: device pointers, None = not written."""
+    _fields_ = [("barycentrics", C.c_void_p), ("baryDdx", C.c_void_p), ("baryDdy", C.c_void_p), ("uv", C.c_void_p),
+                ("uvGrad", C.c_void_p), ("positionRS", C.c_void_p), ("motionVector", C.c_void_p), ("debugRGBA8", C.c_void_p)]
+
+
+# name -> floats (or uint32 for debugRGBA8) per texel of each resolve target (include/chordvis.h ChordResolveTargets)
+RESOLVE_CHANNELS = {"barycentrics": 4, "baryDdx": 4, "baryDdy": 4, "uv": 2, "uvGrad": 4, "positionRS": 4, "motionVector": 2, "debugRGBA8": 1}
+DEBUG_MESHLET, DEBUG_TRIANGLE, DEBUG_LOD, DEBUG_LOD_MESHLET, DEBUG_BARYCENTRICS = 0, 1, 2, 3, 4
+
+
 class DepthTarget(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -179,6 +196,8 @@ def _load():
         "chordvis_visibility_mark": (i32, [vp, CountAndCmd, P(TileMarker)]),
         "chordvis_wait_visibility": (i32, [vp, vp]),
         "chordvis_prepare_shading_tile_param": (i32, [vp, u32, P(TileMarker), P(ShadingTiles)]),
+        "chordvis_resolve_attributes": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets)]),
+        "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),
         "chordvis_readback_shading_tiles": (i32, [vp, P(ShadingTiles), vp, u32, P(u32), vp]),
         "chordvis_comm_unique_id": (i32, [vp]),

@@ -26,6 +26,7 @@ class VisibilityRenderer:
             if rc != L.OK:
                 raise L.ChordvisError(
                     "chordvis_create(device=%d) failed with %d: no usable HIP device (the product path has no CPU fallback)" % (device, rc))
+        self.device = device
         self.width = self.height = 0
         self.scene = None
 
@@ -289,6 +290,47 @@ class VisibilityRenderer:
         """Orders `stream` (default: the context's) behind the completion of the last frame's resolved image."""
         self._check(L.lib.chordvis_wait_visibility(self._ctx, stream), "wait_visibility")
 
+    def stream(self):
+        """The hipStream_t (as an int) the context enqueues on."""
+        return L.lib.chordvis_stream(self._ctx) or 0
+
+    def resolve_attributes(self, names=None, desc=None, drawed_meshlet_cmd=None, out=None):
+        """Per-pixel attributes of the visible triangle (lighting.hlsl:278-371, material.hlsli:41-64, nanite_debug.hlsl) in ONE
+        launch: {name: tensor} for `names` (default: every target of L.RESOLVE_CHANNELS), each (height, width, channels) float32
+        ((height, width) int32 holding RGBA8 for "debugRGBA8") on the context's device.  desc: an L.ResolveDesc or None (all zero).
+        out: {name: tensor} to write into instead of fresh tensors.  The tensors are ordered against the context's stream
+        both ways: the resolve waits for the current torch stream, which in turn waits for the resolve."""
+        import torch
+        names = list(L.RESOLVE_CHANNELS) if names is None else list(names)
+        bad = [n for n in names if n not in L.RESOLVE_CHANNELS]
+        if bad or not names:
+            raise ValueError("resolve_attributes: unknown or no target names %r (known: %s)" % (bad, ", ".join(L.RESOLVE_CHANNELS)))
+        dev = torch.device("cuda", self.device)
+        mine = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        res = {}
+        for n in names:
+            if out is not None and n in out:
+                t = out[n]
+            else:
+                ch = L.RESOLVE_CHANNELS[n]
+                shape = (self.height, self.width) if ch == 1 else (self.height, self.width, ch)
+                with torch.cuda.device(dev):
+                    t = torch.empty(shape, dtype=torch.int32 if n == "debugRGBA8" else torch.float32, device=dev)
+            assert t.is_contiguous() and t.numel() == self.width * self.height * L.RESOLVE_CHANNELS[n], n
+            res[n] = t
+        targets = L.ResolveTargets(**{n: t.data_ptr() for n, t in res.items()})
+        cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
+        if mine.cuda_stream != cur.cuda_stream:
+            mine.wait_stream(cur)                      # (the allocator may hand out memory torch work on `cur` still uses)
+        self._check(L.lib.chordvis_resolve_attributes(self._ctx, cmd, C.byref(desc) if desc is not None else None, C.byref(targets)),
+                    "resolve_attributes")
+        if mine.cuda_stream != cur.cuda_stream:
+            cur.wait_stream(mine)
+            for t in res.values():
+                t.record_stream(mine)
+        return res
+
     def prepare_shading_tile_param(self, shading_type, marker):
         """prepareShadingTileParam (visibility_tile.cpp:59-110)."""
         out = L.ShadingTiles()
@@ -396,7 +438,7 @@ class VisibilityGroup:
         if rc != L.OK:
             raise L.ChordvisError("chordvis_create_group(%r) failed with %d" % (devices, rc))
         self.size = len(devices)
-        self.ranks = [VisibilityRenderer(_borrowed_ctx=L.lib.chordvis_group_ctx(self._g, r)) for r in range(self.size)]
+        self.ranks = [VisibilityRenderer(devices[r], _borrowed_ctx=L.lib.chordvis_group_ctx(self._g, r)) for r in range(self.size)]
 
     def _check(self, rc, what):
         if rc != L.OK:

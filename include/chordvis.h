@@ -220,7 +220,8 @@ int chordvis_upload_scene(ChordCtx* ctx, const ChordSceneDesc* scene);
 /* uploadBufferToGPU("GLTFObjectInfo", ...) renderer.cpp:229 — per-frame object records
  * (count must equal the uploaded scene's objectCount; primitive/material ids must not change). */
 int chordvis_update_objects(ChordCtx* ctx, const ChordObject* hostObjects, uint32_t count);
-/* Same, for a caller-owned DEVICE array (no copy; must stay valid while bound). */
+/* Same, for a caller-owned DEVICE array (no copy; must stay valid while bound, and unchanged from a frame until
+ * chordvis_resolve_attributes of that frame has run). */
 int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint32_t count);
 
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
@@ -491,6 +492,45 @@ int chordvis_visibility_mark(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, C
 int chordvis_wait_visibility(ChordCtx* ctx, void* hipStream);
 /* prepareShadingTileParam — visibility_tile.cpp:59-110 (tilePrepareCS + prepareTileParamCS, visibility_tile.hlsl:136-219) */
 int chordvis_prepare_shading_tile_param(ChordCtx* ctx, uint32_t shadingType, const ChordTileMarker* marker, ChordShadingTiles* out);
+
+/* ------------------------------------------------------------------ per-pixel attributes of the visible triangle */
+/* lighting.hlsl:278-371 (getTriangleMiscInfo, nanite_shared.hlsli:111-179) / material.hlsli:41-64 / nanite_debug.hlsl:
+ * pixel -> visibility word -> draw command -> object, meshlet, triangle -> three vertices -> perspective-correct barycentrics
+ * and their screen derivatives (calculateTriangleBarycentrics, base.hlsli:457-495) -> interpolated attributes. */
+#define CHORD_NANITE_DEBUG_MESHLET      0u   /* simpleHashColor(meshlet id)           nanite_debug.hlsl:6-10 */
+#define CHORD_NANITE_DEBUG_TRIANGLE     1u   /* simpleHashColor(triangle index word)  */
+#define CHORD_NANITE_DEBUG_LOD          2u   /* LOD palette                            */
+#define CHORD_NANITE_DEBUG_LOD_MESHLET  3u   /* pow(meshlet colour, 0.5) x LOD palette */
+#define CHORD_NANITE_DEBUG_BARYCENTRICS 4u
+typedef struct ChordResolveDesc {
+    ChordMat4 translatedWorldToClipNoJitter;           /* read when useNoJitter != 0 (motion vectors only)                           */
+    ChordMat4 translatedWorldToClipLastFrameNoJitter;
+    uint32_t  useNoJitter;     /* 0: motion from the frame's own VP and VP_last (== the reference when jitter is 0)                   */
+    uint32_t  debugMode;       /* CHORD_NANITE_DEBUG_*, for debugRGBA8                                                              */
+    uint32_t  pad[2];
+} ChordResolveDesc;
+/* Caller-owned DEVICE images of width x height texels, row-major; NULL = not written; at least one non-NULL.  An empty pixel (id 0)
+ * or one whose id is not below the list's count holds 0 in every image, and opaque black (0xFF000000) in debugRGBA8. */
+typedef struct ChordResolveTargets {
+    float*    barycentrics;   /* float4: interpolation.xyz, 0                   */
+    float*    baryDdx;        /* float4: ddx.xyz, 0                             */
+    float*    baryDdy;        /* float4: ddy.xyz, 0                             */
+    float*    uv;             /* float2: texcoord0 ((0, 0) when the scene has none) */
+    float*    uvGrad;         /* float4: du/dx, dv/dx, du/dy, dv/dy             */
+    float*    positionRS;     /* float4: translated-world position xyz, 1       */
+    float*    motionVector;   /* float2: material.hlsli:55-61                   */
+    uint32_t* debugRGBA8;     /* R in the low byte                              */
+} ChordResolveTargets;
+/* One launch on the context's stream over the image chordvis_visibility_mark reads (the resolved one of a sharded context), after
+ * the same wait for it.  drawedMeshletCmd = the list the ids index (chordvis_last_frame_cmds).  The matrices are the objects' and
+ * the view's of the frame that made the image: CHORDVIS_E_INVALID after chordvis_update_objects / chordvis_set_view until the next
+ * frame, and before the first one.  Objects bound with chordvis_bind_objects must stay unchanged until the resolve has run.
+ * desc NULL: all zero. */
+int chordvis_resolve_attributes(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
+                                const ChordResolveTargets* targets);
+/* The hipStream_t the context enqueues on (the one given to chordvis_create, or its own): a host that allocates targets on a
+ * stream of its own orders the two against each other. */
+void* chordvis_stream(ChordCtx* ctx);
 
 /* ------------------------------------------------------------------ readback / stats (synchronize) */
 
