@@ -67,7 +67,7 @@ int alloc_hzb(ChordCtx* c, HzbBuffers& h)
     ChordHZBDesc d;
     if (chordvis_hzb_desc(c->width, c->height, &d) != CHORDVIS_OK) return fail(c, CHORDVIS_E_INVALID, "render size unsupported for HZB");
     h.desc = d;
-    h.valid = false;
+    h.valid = false; h.uploaded = false;
     int rc;
     if ((rc = dalloc(c, &h.minTexels, d.totalTexels))) return rc;
     if ((rc = dalloc(c, &h.maxTexels, d.totalTexels))) return rc;
@@ -1182,6 +1182,7 @@ static int render_frame_impl(ChordCtx* c)
     // buildHZB(min,max,range) :343 -- mips 0..5 are written; the one-block tail (mips 6.., range) is carried by the next
     // frame's first kernel, or launched by whoever reads the chain first (flush_pending_tail)
     c->hzb[next].valid = true;
+    c->hzb[next].uploaded = false;                                                    // (the tile kernel wrote it: the library's own chain)
     c->pendingTailSlot = next;
     record(c, S_HZBF);
     c->historySlot = next;                                                            // :489
@@ -1527,6 +1528,7 @@ int chordvis_upload_history_hzb(ChordCtx* c, const uint16_t* hostMin)
     CHORD_HIP(c, hipStreamSynchronize(c->stream));
     CHORD_HIP(c, hipMemcpy(c->hzb[slot].minTexels, hostMin, sizeof(uint16_t) * c->hzb[slot].desc.totalTexels, hipMemcpyHostToDevice));
     c->hzb[slot].valid = true;
+    c->hzb[slot].uploaded = true;                        // (its levels 6.. are the host's: frame_cull_fused_kernel would reduce them from level 5)
     c->historySlot = slot;
     return CHORDVIS_OK;
 }

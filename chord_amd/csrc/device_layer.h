@@ -272,6 +272,7 @@ struct HzbBuffers {
     uint16_t* maxTexels = nullptr;
     uint32_t* validRange = nullptr;
     bool valid = false;
+    bool uploaded = false;         // the host wrote this chain (chordvis_upload_history_hzb): levels 6.. need not be the 2x2 min of level 5
     ChordHZB handle() const { return ChordHZB{desc, minTexels, maxTexels, validRange}; }
 };
 

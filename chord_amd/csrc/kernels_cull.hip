@@ -1609,10 +1609,15 @@ void launch_group_cull(ChordCtx* c, const CmdList& out)
     const HzbBuffers* fuseHzb = nullptr;
     bool fused = false;
     // (its own workgroup size: fblocks workgroups of FUSED_CULL_GROUPS group instances; a workgroup waits for those in front of it only,
-    // which were dispatched before it -- the bound on the grid is the look-back buffer and what a short scene is, not residency)
-    const uint32_t fblocks = (c->groupInstances + FUSED_CULL_GROUPS - 1u) / FUSED_CULL_GROUPS;
+    // which were dispatched before it -- the bound on the grid is the look-back buffer and what a short scene is, not residency).
+    // At least one: workgroup 0 zeroes the frame's counters and publishes the view, the last one writes the list counts -- a scene of
+    // no group instances still needs both.
+    const uint32_t fblocks = std::max(1u, (c->groupInstances + FUSED_CULL_GROUPS - 1u) / FUSED_CULL_GROUPS);
     const uint32_t fobj = (c->objectCount + FUSED_CULL_THREADS - 1u) / FUSED_CULL_THREADS;
-    if (CULL_FUSED && fusedOn && CULL_QUAD && !sh && !hier && c->inFrame && c->fuseCullFrame && out.cmds == c->lists[0].cmds && fblocks + 1u + fobj <= (uint32_t)c->numCUs * (1024u / FUSED_CULL_THREADS) && fblocks <= FUSED_CULL_MAX_BLOCKS && blocks <= 512u &&
+    // A history chain the host uploaded (chordvis_upload_history_hzb) keeps its own levels 6..; the fused kernel would reduce them from
+    // level 5 in LDS, so its frame takes the three launches, whose phase-0 cull reads the stored levels as the reference does.
+    const bool uploadedHist = c->fuseCullHzb && c->fuseCullHzb->uploaded;
+    if (CULL_FUSED && fusedOn && CULL_QUAD && !sh && !hier && c->inFrame && c->fuseCullFrame && !uploadedHist && out.cmds == c->lists[0].cmds && fblocks + 1u + fobj <= (uint32_t)c->numCUs * (1024u / FUSED_CULL_THREADS) && fblocks <= FUSED_CULL_MAX_BLOCKS && blocks <= 512u &&
         !(c->debugFlags & ~(32768u | 65536u | 262144u))) {
         uint32_t tailFloats = 0;
         const ChordHZBDesc& hd = c->hzb[0].desc;

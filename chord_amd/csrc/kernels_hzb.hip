@@ -232,7 +232,7 @@ void launch_hzb_build(ChordCtx* c, HzbBuffers& out, bool bMin, bool bMax, bool b
     const dim3 g1((vw + 31u) / 32u, (vh + 31u) / 32u);
     CHORD_LAUNCH(c, hzb_mips_kernel, g1, dim3(256), 0, c->stream, p, wantMax);
     if (p.desc.mipCount > 6 || wantRange) CHORD_LAUNCH(c, hzb_tail_kernel, dim3(1), dim3(256), 0, c->stream, p, wantMax, wantRange, 6u);
-    out.valid = true;
+    out.valid = true; out.uploaded = false;
 }
 
 // Sharded frames: the all-gathered tile slots of an exchange buffer -> mips 0..5 of `out` (the tail, mips 6.. and the valid
@@ -245,7 +245,7 @@ void launch_hzb_untile(ChordCtx* c, HzbBuffers& out, bool finalChain)
                                        out.minTexels, out.maxTexels, c->dTileRange, c->dTileLoads);
     else            CHORD_LAUNCH(c, hzb_untile_kernel<false>, g, dim3(256), 0, c->stream, (const uint16_t*)c->dHzbExchange, c->shard, out.desc,
                                        out.minTexels, (uint16_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-    out.valid = true;
+    out.valid = true; out.uploaded = false;
 }
 
 HzbParams make_hzb_tail_params(ChordCtx* c, HzbBuffers& out)
@@ -262,7 +262,7 @@ void launch_hzb_tail(ChordCtx* c, HzbBuffers& out, bool bMax, bool bValidRange)
     HzbParams p = make_hzb_tail_params(c, out);
     if (p.desc.mipCount > (uint32_t)CHORD_TILE_SHIFT || bValidRange)
         CHORD_LAUNCH(c, hzb_tail_kernel, dim3(1), dim3(256), 0, c->stream, p, bMax ? 1 : 0, bValidRange ? 1 : 0, (uint32_t)CHORD_TILE_SHIFT);
-    out.valid = true;
+    out.valid = true; out.uploaded = false;
 }
 
 __global__ __launch_bounds__(256) void depth_extract_kernel(const unsigned long long* __restrict__ vis, float* __restrict__ depth, size_t words)

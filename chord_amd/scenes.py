@@ -612,6 +612,37 @@ def small_test_scene(width=160, height=96, lods=3, seed=7, two_sided_every=3):
     return sb.build(), cam
 
 
+def group_count_scene(groups, width=320, height=180, shown=48, seed=1, panels=True):
+    """Exactly `groups` group instances (Scene.group_instances), for the cull paths chosen by the group-instance count: objects of a
+    one-group tile (2 x 2 patches, four meshlets: every lane of a quad) and, past 256 groups and unless `panels` is False, of a
+    64-group panel (16 x 16 patches) ahead of them.  At most `shown` objects, spread over the whole object order (first and last included), stand in three
+    staggered layers of 8 x 4 unit squares in front of the camera, each layer a wall that hides most of the next; the others are
+    behind the camera (culled by the object test)."""
+    sb = SceneBuilder("group_count_%d" % groups)
+    pb = PrimitiveBuilder()
+    pb.add_surface(plane_surface((-0.5, -0.5, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), seed, 0.05, 2.0), 16, 16, 1)
+    panel = sb.add_primitive(pb)
+    pb = PrimitiveBuilder()
+    pb.add_surface(plane_surface((-0.5, -0.5, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), seed + 1, 0.08, 1.5), 2, 2, 1)
+    tile = sb.add_primitive(pb)
+    prims = [panel] * (groups // 64) + [tile] * (groups % 64) if groups > 256 and panels else [tile] * groups
+    n = len(prims)
+    picked = set(np.linspace(0, n - 1, min(n, shown)).round().astype(np.int64).tolist()) if n else set()
+    j = 0
+    for k, prim in enumerate(prims):
+        if k in picked:
+            col, row, layer = j % 8, (j // 8) % 4, (j // 32) % 3
+            r = rand01(seed + 7, np.arange(3 * j, 3 * j + 3))
+            m = translate(col - 3.5 + 0.5 * layer, row - 1.5 + 0.3 * layer, -1.2 * layer - 0.2 * r[0]) @ rotate_y((r[1] - 0.5) * 0.4)
+            j += 1
+        else:
+            m = translate((k % 37) * 0.5, (k % 11) * 0.5, 40.0 + (k % 5))
+        sb.add_object(prim, m)
+    scene = sb.build()
+    assert scene.group_instances == groups
+    return scene, Camera((0.0, 0.0, 6.0), (0.0, 0.0, -1.0), width, height)
+
+
 def _alpha_textures(seed):
     """Three procedural RGBA8 textures whose alpha the masked materials test: a checker, an odd-sized noise, a disc."""
     yy, xx = np.mgrid[0:64, 0:64]

@@ -562,3 +562,64 @@ def test_all_cores_frame_replay_equals_orc_frame(name, builder, threads):
     f1 = orc.frame(scene, view1, iv1, flags, prev_hzb_min=f0["hzb_min"])
     _assert_same_frame(orc.frame_mt(scene, view1, iv1, flags, f0["hzb_min"], threads), f1, name + " two-pass")
     _assert_same_frame(orc.frame_mt(scene, view1, iv1, flags, f0["hzb_min"], 1), f1, name + " two-pass, one thread")
+
+
+# ------------------------------------------------------------------------ cull-path edges ---
+
+def test_phase0_cull_reads_the_stored_upper_levels_of_the_history_chain():
+    """hzb_mainview_culling.hlsl samples whatever the history chain holds at the level it picks; it never re-derives levels 6.. from
+    level 5.  A chain whose levels 6.. are NOT the 2x2 min of level 5 (all 1.0: nearer than anything) must give the oracle's
+    phase-0 lists of the numpy restatement on that very chain -- and other lists than the same chain with levels 6.. recomputed,
+    or the GPU tests built on it (tests/test_gpu_cull_paths.py) could not tell the two apart."""
+    import spec_np as S
+    scene, _ = scenes.group_count_scene(64, 640, 360)
+    chain, view, iv = HP.close_view_chain(scene)
+    desc = orc.hzb_desc(640, 360)
+    assert desc.mipCount > 6
+    odd = HP.hzb_with_upper_levels(desc, chain, 0x3C00)
+    redo = HP.hzb_with_upper_levels(desc, odd)
+    assert not np.array_equal(odd, redo)
+    cmds = orc.instance_culling(scene, view, iv, HP.ALL_FLAGS)
+    dims = [desc.mip_dims(l) for l in range(desc.mipCount)]
+    for c in (odd, redo, chain):
+        vis_o, rej_o = orc.hzb_culling(scene, view, HP.ALL_FLAGS, 0, desc, c, cmds)
+        keep = S.hzb_visible(scene, view, cmds, 0, HP.hzb_levels(desc, c), dims)
+        assert np.array_equal(cmds["slot"][keep], vis_o["slot"]) and np.array_equal(cmds["slot"][~keep], rej_o["slot"])
+    n_odd = len(orc.hzb_culling(scene, view, HP.ALL_FLAGS, 0, desc, odd, cmds)[0])
+    n_redo = len(orc.hzb_culling(scene, view, HP.ALL_FLAGS, 0, desc, redo, cmds)[0])
+    assert n_odd < n_redo, (n_odd, n_redo)
+    # ... and so do the frames' stage counts
+    a = orc.frame(scene, view, iv, HP.ALL_FLAGS, prev_hzb_min=odd)["counts"]
+    b = orc.frame(scene, view, iv, HP.ALL_FLAGS, prev_hzb_min=redo)["counts"]
+    assert a[0] == b[0] and a[1] != b[1], (a, b)
+
+
+def test_upper_levels_recomputed_from_level5_match_the_built_chain_where_sizes_are_even():
+    """HP.hzb_with_upper_levels(value=None) restates what a chain built from an image holds at levels 6..: on a target whose
+    level-5 extent is even in both directions, exactly the 2x2 min of level 5."""
+    scene, cam = scenes.group_count_scene(65, 1024, 512)
+    from chord_amd import lib as L
+    L.fill_objects(scene, cam)
+    view, iv = L.make_views(cam)
+    f = orc.frame(scene, view, iv, HP.ALL_FLAGS)
+    assert np.array_equal(HP.hzb_with_upper_levels(f["desc"], f["hzb_min"]), f["hzb_min"])
+
+
+@pytest.mark.parametrize("history", [False, True], ids=["frame0", "with_history"])
+def test_frame_of_a_scene_without_group_instances_is_empty(history):
+    """Every primitive with meshletGroupCount 0 (accepted by upload_scene): nothing is culled, nothing drawn, the image stays
+    cleared and the history chain is all far (0), also when a history chain with depth in it is handed in."""
+    from chord_amd import lib as L
+    full, cam = scenes.group_count_scene(65, 320, 180)
+    scene = HP.without_groups(full)
+    assert scene.group_instances == 0 and len(scene.objects) == len(full.objects)
+    L.fill_objects(scene, cam)
+    view, iv = L.make_views(cam)
+    prev = orc.frame(full, view, iv, HP.ALL_FLAGS)["hzb_min"] if history else None
+    if history:
+        assert prev.any()
+    f = orc.frame(scene, view, iv, HP.ALL_FLAGS, prev_hzb_min=prev)
+    assert not f["vis"].any()
+    assert len(f["cmds"]) == 0 and list(f["counts"]) == [0, 0, 0, 0]
+    assert f["stats"].trianglesSubmitted == 0
+    assert not f["hzb_min"].any()
