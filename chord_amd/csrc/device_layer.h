@@ -250,7 +250,13 @@ struct DeviceCounters {
 #define CHORD_BIN_CAP 8192u
 #endif
 static_assert(CHORD_BIN_CAP <= (1u << 20), "tile x bin capacity is formed with a 24-bit multiply in 32 bits (bin_put)");
+// tileTouched: one bit per tile and pass (pass p's words at p * CHORD_MAX_TILES / 32), set by the reservation that drew a tile's
+// bin slot 0 (bin_alloc) in a pass whose tile kernel takes only touched tiles (launch_raster: RasterParams::tileTouched).  Bits of
+// neighbouring tiles share a word: a pass sets at most one bit per tile, and only the light later passes set any (config 3: 436 of
+// 2 040 tiles on 4 lines), so the non-returning ORs stay far from the ~88 per microsecond a line retires.  First in the struct:
+// inside the bytes every frame zeroes (frameStateZeroBytes), with the 64-byte alignment of the lines behind it unchanged.
 struct FrameState {
+    uint32_t tileTouched[2 * CHORD_MAX_TILES / 32];
     DeviceCounters counters;
     uint32_t listCounts[8];        // [0..3] command lists of the frame, [4] this rank's share of list 0 (sharded: written by the group cull), [5] this rank's clusters of a foreign list (stripe filter), [6 + pass] clusters a dense launch's block kernel left over
     uint32_t tileCount[2 * CHORD_MAX_TILES * CHORD_TILECOUNT_STRIDE];   // pass p starts at p * tiles * stride

@@ -115,6 +115,8 @@ struct RasterParams {
                                                         // 2: no schedule at all (later passes of a frame: launch_raster TILE_DIRECT) -- work item i is tile i, whole; a tile without entries is left alone
     uint32_t* heavyHint;                                // host-visible words [0] / [2]: this pass's serial (binStamp) stored by whoever finds the pass HEAVY (a bin beyond tileSplitMin entries, more than
                                                         // TILE_DIRECT_MAX_CLUSTERS clusters) / LIGHT (launch_raster: only a pass that was light a moment ago runs without a schedule), or NULL
+    uint32_t* tileTouched;                              // direct passes that take only touched tiles (launch_raster TILE_TOUCHED): this pass's bits of FrameState::tileTouched,
+                                                        // set by bin_alloc for the slot 0 of a tile, read by the tile kernel (touched_tile); NULL: no bit is set or read
     uint32_t debug;                                     // ablation switches (chordvis_set_debug), 0 in production
 };
 // The per-phase clocks of the setup kernels (debug bit 512) and of the tile kernel (bit 16) exist only in a build with
@@ -324,6 +326,7 @@ struct RecordEmitParams {
     uint32_t* tileCount; uint32_t* tileBins; uint32_t binCap; uint32_t tilesX;
     uint32_t* binPool; uint32_t binPoolChunks; uint32_t* binPoolCount;
     unsigned long long* binChunkTab; uint32_t binStamp; uint32_t binMaxChunks;
+    uint32_t* tileTouched;
     ShardInfo shard;
 };
 __device__ __forceinline__ RecordEmitParams load_record_emit_params()
@@ -336,6 +339,7 @@ __device__ __forceinline__ RecordEmitParams load_record_emit_params()
     e.tileCount = scalar_load(&q->tileCount); e.tileBins = scalar_load(&q->tileBins); e.binCap = scalar_load(&q->binCap); e.tilesX = scalar_load(&q->tilesX);
     e.binPool = scalar_load(&q->binPool); e.binPoolChunks = scalar_load(&q->binPoolChunks); e.binPoolCount = scalar_load(&q->binPoolCount);
     e.binChunkTab = scalar_load(&q->binChunkTab); e.binStamp = scalar_load(&q->binStamp); e.binMaxChunks = scalar_load(&q->binMaxChunks);
+    e.tileTouched = scalar_load(&q->tileTouched);
     e.shard.ranks = scalar_load(&q->shard.ranks); e.shard.rank = scalar_load(&q->shard.rank); e.shard.slotsPerRank = 0u; e.shard.tilesX = 0u;
     e.shard.ownedRows = scalar_load(&q->shard.ownedRows); e.shard.tileSlot = nullptr;
     return e;
@@ -371,9 +375,12 @@ __device__ __forceinline__ BinElect wave_bin_elect(bool has, uint32_t tile, uint
 __device__ __forceinline__ uint32_t bin_capacity(const RasterParams& p) { return p.binCap + p.binMaxChunks * CHORD_BIN_CHUNK; }
 
 // step 1 of a bin write: the lane that drew the first slot of an overflow chunk allocates it and publishes it.  Never waits.
+// Every slot drawn goes through here, so the drawer of a tile's slot 0 -- exactly one reservation per tile and pass, whichever
+// binner made it -- also marks the tile touched (a non-returning OR: nothing waits for it).
 template <class P>
 __device__ __forceinline__ void bin_alloc(const P& p, uint32_t tile, uint32_t slot)
 {
+    if (slot == 0u && p.tileTouched) atomicOr(&p.tileTouched[tile >> 5], 1u << (tile & 31u));
 #ifdef EXP_NO_CHUNKS
     return;
 #endif
@@ -1066,6 +1073,7 @@ struct BlockEmitParams {
     unsigned long long* binChunkTab; uint32_t binStamp; uint32_t binMaxChunks;
     unsigned long long* blockPool; uint32_t blockCap;
     DeviceCounters* counters;
+    uint32_t* tileTouched;
 };
 __device__ __forceinline__ BlockEmitParams load_block_emit_params()
 {
@@ -1076,6 +1084,7 @@ __device__ __forceinline__ BlockEmitParams load_block_emit_params()
     e.binChunkTab = scalar_load(&q->binChunkTab); e.binStamp = scalar_load(&q->binStamp); e.binMaxChunks = scalar_load(&q->binMaxChunks);
     e.blockPool = scalar_load(&q->blockPool); e.blockCap = scalar_load(&q->blockCap);
     e.counters = scalar_load(&q->counters);
+    e.tileTouched = scalar_load(&q->tileTouched);
     return e;
 }
 
@@ -2721,6 +2730,37 @@ __device__ __forceinline__ void merge_blocks(unsigned long long* tile, const uns
 #ifndef TILE_DEEP_FETCH
 #define TILE_DEEP_FETCH 0               // 1: opaque instantiations fetch records two batches ahead (two register sets, batch loop unrolled by two) -- measured in round 5, no gain (profiles/r05_tile_kernel_experiments.txt item 9); 0: the round-2 form
 #endif
+// Direct passes that take only touched tiles (RasterParams::tileTouched): of the pass's mask, the tile of set bit k and the tile
+// behind set bit g - 1 (bits in tile order), and the number of set bits.  One 8-byte load per lane covers 4 096 tiles
+// (launch_raster takes this form for targets of at most that many); every wave of the workgroup works it out for itself -- no LDS,
+// no barrier.  Everything stays in vector registers up to the readlanes of the answers (the kernel sits at its scalar-register
+// limit).  A k or g - 1 beyond the set bits gives tile 0.
+__device__ __forceinline__ uint32_t touched_tile(const uint32_t* __restrict__ mask, uint32_t k, uint32_t g, uint32_t& total, uint32_t& tail)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint2 w = reinterpret_cast<const uint2*>(mask)[lane];
+    const uint32_t c = (uint32_t)(__popc(w.x) + __popc(w.y));
+    uint32_t incl = c;                                          // set bits in the words of lanes 0 .. lane
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) { const uint32_t t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+    total = bcast(incl, 63);
+    // the lane whose word holds set bit j finds the bit's place in the word
+    auto select = [&](uint32_t j) -> uint32_t {
+        uint32_t r = j - (incl - c), m = w.x, pos = 0u;
+        const uint32_t nLo = (uint32_t)__popc(w.x);
+        if (r >= nLo) { r -= nLo; m = w.y; pos = 32u; }
+#pragma unroll
+        for (uint32_t s = 16u; s != 0u; s >>= 1) {
+            const uint32_t n = (uint32_t)__popc(m & ((1u << s) - 1u));
+            if (r >= n) { r -= n; m >>= s; pos += s; }
+        }
+        const unsigned long long holder = __ballot(incl - c <= j && j < incl);
+        return holder ? bcast(lane * 64u + pos, (int)__ffsll((long long)holder) - 1) : 0u;
+    };
+    tail = select(g - 1u) + 1u;
+    return select(k);
+}
+
 #ifndef TILE_MIN_BLOCKS
 #define TILE_MIN_BLOCKS 4               // waves per SIMD the register allocation aims at (launch bounds: 4 -> 128 VGPRs, 6 -> 80)
 #endif
@@ -2767,6 +2807,19 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     uint2 firstItem = make_uint2(wg0, 0u);
     uint32_t active = tilesAll;
     if (!direct) { firstItem = p.tileOrder[1u + min(wg0, tilesAll - 1u)]; active = p.tileOrder[0].x; }
+    else if (p.tileTouched) {
+        // (a direct pass over the touched tiles only, G workgroups, one per tile slot of the device: workgroup w's first item is the
+        // w-th set bit of the mask -- the chain head is one round trip longer, the mask before the counter line; the 1 604 of config
+        // 3's 2 040 workgroups that found an empty counter line are not launched.  A pass that touched more than G tiles gives the
+        // tiles behind the G-th set bit to the items from G on, one each, as the direct form over every tile does -- tile
+        // oi + tilesAll - active, the untouched ones ending at their counter line -- so that no mask is searched in the loop)
+        // (G is gridDim.x: a direct pass has no schedule-making workgroup, and wgs would be two more scalar loads on the chain head)
+        uint32_t touched, tail;
+        firstItem.x = touched_tile(p.tileTouched, wg0, gridDim.x, touched, tail);
+        active = touched > gridDim.x ? gridDim.x + tilesAll - tail : touched;
+        // (the pass's cluster-count report is item 0's: a pass that touched no tile has no item 0, and workgroup 0 makes it here)
+        if (active == 0u && wg0 == 0u && threadIdx.x == 0u && p.heavyHint) p.heavyHint[*p.count > TILE_DIRECT_MAX_CLUSTERS ? 0 : 2] = p.binStamp;
+    }
     // (bit 31 of the loop's index: not the workgroup's first item -- asked of gridDim.x, "first" was a scalar load from the dispatch
     // packet and a wait at the top of every item)
     for (uint32_t oiw = wg0; (oiw & 0x7FFFFFFFu) < active; oiw = ((oiw & 0x7FFFFFFFu) + wgs) | 0x80000000u) {
@@ -2775,7 +2828,7 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     // item loop, and hoisted out of it those values -- offsets, masks, lane roles -- sat in registers across the whole kernel)
     uint32_t tix = threadIdx.x;
     asm volatile("" : "+v"(tix));
-    const uint2 itemCount = (oiw >> 31) == 0u ? firstItem : (direct ? make_uint2(oi, 0u) : p.tileOrder[1u + oi]);
+    const uint2 itemCount = (oiw >> 31) == 0u ? firstItem : (direct ? make_uint2(oi + tilesAll - active, 0u) : p.tileOrder[1u + oi]);   // (direct: oi when active is every tile)
     const uint32_t item = itemCount.x;
     const uint32_t tileId = item & 0xFFFu, slice = (item >> 12) & 0x3FFu, slices = (item >> 22) + 1u;
     // (kept order: the tile's counter line is read here, and -- the address needs the tile only -- a whole tile's first bin entries
@@ -3439,6 +3492,44 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
         p.leftCount = c->dCounts + 6 + pass; p.leftCmds = c->dLeftCmds;
         if (!c->inFrame || c->rasterCalls >= 2) LR_HIP(hipMemsetAsync(p.leftCount, 0, sizeof(uint32_t), c->stream));
     }
+    p.orderKept = 0u;
+    p.heavyHint = nullptr;
+    // LIGHT later passes of a frame (the read-modify-write passes behind the first: config 3's second pass is 205 clusters, 436 of its
+    // 2 040 tiles touched with 60 entries each) run WITHOUT a schedule: one workgroup per tile of the target, tile = workgroup index, a
+    // tile whose counter line says "no entries" ends after that one load.  What such a pass has no use for -- heaviest-first order,
+    // bins cut into slices -- is what the schedule kernel was there for (config 3 0.1792 -> 0.1759 ms, a 1080p frame 0.112 -> 0.109).
+    // A pass with work in every tile needs them (config 4's second pass: 57 -> 115 us of tile kernel without), so the pass says what
+    // it is in two host-visible words -- its serial under "heavy" when a bin is longer than tileSplitMin or it set up more than
+    // TILE_DIRECT_MAX_CLUSTERS clusters, under "light" otherwise; written by the schedule kernel, or by the tile kernel of a direct
+    // pass -- and runs direct while the latest report the host has seen says light.  A camera cut that sends the scene
+    // through the second pass costs that frame balance, never a pixel (-DTILE_DIRECT=0 compiles the path out; CHORDVIS_TILE_DIRECT=0
+    // turns it off at run time: A/B runs).
+    static const bool directOn = [] { const char* e = getenv("CHORDVIS_TILE_DIRECT"); return !e || atoi(e) != 0; }();
+    // (laterOk: a read-modify-write pass of a frame with the HZB fused into its tile-out -- what the direct form and the kept schedule of
+    // a later pass are written for)
+    const bool laterOk = c->inFrame && !clearTiles && p.hzbFused && !c->depthOnly && CHORD_MASKED_FUSED && c->dBinHint && !(c->debugFlags & ~(DBG_NO_BLOCKS | DBG_FORCE_BLOCKS | DBG_FORCE_HOT | 524288u));
+    if (laterOk) p.heavyHint = c->dBinHint + 4 + pass;
+    if (TILE_DIRECT && directOn && laterOk) {
+        const uint32_t heavySeen = c->hBinHint[4 + pass], lightSeen = c->hBinHint[6 + pass];
+        // (the host runs frames ahead of the device -- a bench loop enqueues hundreds: what it reads is the state of a pass long past,
+        // so the rule is "the latest report says light", not "a report of the last few frames"; a pass that reports both is heavy)
+        if (lightSeen != 0u && (heavySeen == 0u || (int32_t)(lightSeen - heavySeen) > 0)) {
+            p.orderKept = 2u;
+        }
+    }
+    // A light later pass takes only the tiles it touched: its reservations set a bit per tile (bin_alloc: whoever draws slot 0) and
+    // its tile kernel launches one workgroup per tile slot of the device, each taking the set bits w, w + G, ... (touched_tile) -- the
+    // workgroups of untouched tiles, which held a slot for one round trip each and queued the touched ones behind them, are not
+    // launched.  The bits must be set by the set-up kernels, so the choice is made before them.  Not in sharded frames (a rank's work
+    // items are its own tiles: those keep one workgroup each) nor above 4 096 tiles (touched_tile reads one 8-byte word per lane).
+    // CHORDVIS_TILE_TOUCHED=0: the direct form over every tile (A/B runs); a number above 1: at most that many workgroups (tests: a
+    // pass that touched more tiles than the grid has workgroups).
+    static const int touchedEnv = [] { const char* e = getenv("CHORDVIS_TILE_TOUCHED"); return e ? atoi(e) : 1; }();
+    p.tileTouched = nullptr;
+    if (p.orderKept == 2u && touchedEnv != 0 && c->shard.ranks <= 1 && tiles <= 64u * 64u) {
+        p.tileTouched = c->dFrameState->tileTouched + (size_t)pass * (CHORD_MAX_TILES / 32u);
+        if (!c->inFrame || c->rasterCalls >= 2) LR_HIP(hipMemsetAsync(p.tileTouched, 0, sizeof(uint32_t) * ((tiles + 31u) / 32u), c->stream));
+    }
     uint32_t blocks = (in.capacity + 3u) / 4u;
 #ifndef SETUP_GRID_MULT
 #define SETUP_GRID_MULT 1u
@@ -3465,32 +3556,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     // frames (chordvis_set_tile_schedule_keep, default 7; -DTILE_ORDER_KEEP=0 compiles the path out); in between the tile kernel takes items and order from the kept schedule and a tile's bin length and flags from the
     // counter line (RasterParams::orderKept) -- one launch less in most frames.  The image does not depend on order or cut.  (The
     // hints the schedule kernel leaves for the next frame -- longest bin, cluster count, hot tiles -- age with it.)
-    p.orderKept = 0u;
-    p.heavyHint = nullptr;
-    bool makeOrder = true;
-    // LIGHT later passes of a frame (the read-modify-write passes behind the first: config 3's second pass is 205 clusters, 436 of its
-    // 2 040 tiles touched with 60 entries each) run WITHOUT a schedule: one workgroup per tile of the target, tile = workgroup index, a
-    // tile whose counter line says "no entries" ends after that one load.  What such a pass has no use for -- heaviest-first order,
-    // bins cut into slices -- is what the schedule kernel was there for (config 3 0.1792 -> 0.1759 ms, a 1080p frame 0.112 -> 0.109).
-    // A pass with work in every tile needs them (config 4's second pass: 57 -> 115 us of tile kernel without), so the pass says what
-    // it is in two host-visible words -- its serial under "heavy" when a bin is longer than tileSplitMin or it set up more than
-    // TILE_DIRECT_MAX_CLUSTERS clusters, under "light" otherwise; written by the schedule kernel, or by the tile kernel of a direct
-    // pass -- and runs direct while the latest report the host has seen says light.  A camera cut that sends the scene
-    // through the second pass costs that frame balance, never a pixel (-DTILE_DIRECT=0 compiles the path out; CHORDVIS_TILE_DIRECT=0
-    // turns it off at run time: A/B runs).
-    static const bool directOn = [] { const char* e = getenv("CHORDVIS_TILE_DIRECT"); return !e || atoi(e) != 0; }();
-    // (laterOk: a read-modify-write pass of a frame with the HZB fused into its tile-out -- what the direct form and the kept schedule of
-    // a later pass are written for)
-    const bool laterOk = c->inFrame && !clearTiles && p.hzbFused && !c->depthOnly && CHORD_MASKED_FUSED && c->dBinHint && !(c->debugFlags & ~(DBG_NO_BLOCKS | DBG_FORCE_BLOCKS | DBG_FORCE_HOT | 524288u));
-    if (laterOk) p.heavyHint = c->dBinHint + 4 + pass;
-    if (TILE_DIRECT && directOn && laterOk) {
-        const uint32_t heavySeen = c->hBinHint[4 + pass], lightSeen = c->hBinHint[6 + pass];
-        // (the host runs frames ahead of the device -- a bench loop enqueues hundreds: what it reads is the state of a pass long past,
-        // so the rule is "the latest report says light", not "a report of the last few frames"; a pass that reports both is heavy)
-        if (lightSeen != 0u && (heavySeen == 0u || (int32_t)(lightSeen - heavySeen) > 0)) {
-            p.orderKept = 2u; makeOrder = false;
-        }
-    }
+    bool makeOrder = p.orderKept != 2u;
     // Kept schedules (chordvis_set_tile_schedule_keep != 0; sharded frames too: a rank's work items are its own tiles, and the map they
     // follow changes only through install_tile_owners, which invalidates the schedules).  Slot 0: the first pass of a frame, which writes
     // every tile -- its work items never change, only their order and the cut of long bins.  Slot 1: the second pass; its schedule lists
@@ -3550,7 +3616,9 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     // per block balances better than any static split)
     // (sharded frames: the work items are the rank's own tiles)
     // (a rank's slices: its bins are cut into about tileSlots shares when it owns fewer tiles than that; blocks beyond the item count leave at once)
-    const uint32_t tileBlocks = (p.tileOrderNext ? 1u : 0u) + ((clearTiles || p.orderKept == 2u || p.orderAll) ? ((sh && clearTiles) ? min(tiles, max(c->shard.slotsPerRank, p.tileSlots + p.tileSlots / 2u)) : tiles) : min(tiles, (uint32_t)c->numCUs * (CHORD_TILE_SHIFT == 6 ? 2u : 6u)));
+    const uint32_t slots = (uint32_t)c->numCUs * (CHORD_TILE_SHIFT == 6 ? 2u : 6u);
+    const uint32_t tileBlocks = (p.tileOrderNext ? 1u : 0u) + ((clearTiles || (p.orderKept == 2u && !p.tileTouched) || p.orderAll) ? ((sh && clearTiles) ? min(tiles, max(c->shard.slotsPerRank, p.tileSlots + p.tileSlots / 2u)) : tiles)
+                                                               : min(tiles, p.tileTouched && touchedEnv > 1 ? (uint32_t)touchedEnv : slots));
     // (the tile kernel's instantiations are the opaque ones: alpha-tested triangles were scan-converted by the masked pass above)
 #if CHORD_MASKED_FUSED
     if (c->anyMasked) {
