@@ -12,14 +12,15 @@
 //                         meshletData / position stream -> clip-space transform -> LDS (SoA x,y,w,u,v,depth) ->
 //                         per-triangle culls (mesh_raster.hlsl:143-179) -> snapped setup -> a 32-byte (vertices
 //                         at most 64 px apart) or 48-byte triangle record + one bin entry per 64x64 screen tile
-//                         touched; every reservation of a meshlet in one memory round trip
+//                         touched; every reservation of a meshlet in one memory round trip.  Records touching more than 2x2
+//                         tiles are binned by the same wave right after (wave_bin_large), and its clip triangles are clipped
+//                         and binned by it once its clusters are done (clip_entry)
 //   raster_setup_blocks_kernel  dense launches (a cluster per 16 pixels or more: sub-pixel geometry) run this one first: a
 //                         cluster that fits a 16x16-pixel window is resolved in LDS and leaves as a pixel block per
 //                         touched tile (one bin entry each) instead of a record per triangle; the clusters it cannot
 //                         take go to the record kernel through a leftover list.  <true>: bin slots of hot tiles drawn ahead
-//   raster_clip_and_bin_large_kernel  one launch, two roles: (a) homogeneous Sutherland-Hodgman clipper for
-//                         triangles touching the near / guard planes (rare; emits + bins its pieces itself),
-//                         (b) records touching more than 2x2 tiles: one wave per record, one lane per tile
+//   raster_clip_and_bin_large_kernel  only with CHORDVIS_BIN_IN_SETUP=0 (A/B runs): the same clipping and large-record
+//                         binning from the lists the setup kernel then writes, one launch
 //   raster_tile_order_kernel  work items of the tile kernel (tiles, or slices of tiles with long bins), heaviest first
 //   raster_tile_kernel    one 512-thread workgroup per work item: the tile's 4096 packed words live in LDS;
 //                         every binned triangle is scan-converted with ds_max_u64 (tiny: one lane per triangle;
@@ -85,7 +86,9 @@ struct RasterParams {
     unsigned long long* blockPool; uint32_t blockCap;   // pixel blocks of small clusters, granules of 16 bytes per list shard (0: path off)
     uint32_t blockForce;                                // debug: every launch takes the setup kernel's BLOCKS body
     ClipTri* clipTris; uint32_t clipTriCap; uint32_t pass;   // raster pass of the frame (0 / 1): clip / large count slot
-    uint32_t* largeList; uint32_t largeCap;                  // records touching more than 2x2 tiles (binned by raster_bin_large_kernel)
+    uint32_t* largeList; uint32_t largeCap;                  // records touching more than 2x2 tiles (binned by raster_clip_and_bin_large_kernel), without binInSetup
+    uint32_t binInSetup;                                // 1: the record kernel bins its large records and clips + bins its clip triangles itself (no lists, no
+                                                        // raster_clip_and_bin_large_kernel); 0: the lists and the binner launch (launch_raster: CHORDVIS_BIN_IN_SETUP)
     DeviceCounters* counters;
     uint2* tileOrder;                                   // [0].x = work item count, [1..] = {tile | slice << 12 | (slices-1) << 22, bin count}, heaviest first
     unsigned long long* tileSlabs;                      // one TILE x TILE accumulation slab per tile (all zero between uses)
@@ -327,6 +330,7 @@ struct RecordEmitParams {
     uint32_t* binPool; uint32_t binPoolChunks; uint32_t* binPoolCount;
     unsigned long long* binChunkTab; uint32_t binStamp; uint32_t binMaxChunks;
     uint32_t* tileTouched;
+    uint32_t binInSetup;
     ShardInfo shard;
 };
 __device__ __forceinline__ RecordEmitParams load_record_emit_params()
@@ -339,7 +343,7 @@ __device__ __forceinline__ RecordEmitParams load_record_emit_params()
     e.tileCount = scalar_load(&q->tileCount); e.tileBins = scalar_load(&q->tileBins); e.binCap = scalar_load(&q->binCap); e.tilesX = scalar_load(&q->tilesX);
     e.binPool = scalar_load(&q->binPool); e.binPoolChunks = scalar_load(&q->binPoolChunks); e.binPoolCount = scalar_load(&q->binPoolCount);
     e.binChunkTab = scalar_load(&q->binChunkTab); e.binStamp = scalar_load(&q->binStamp); e.binMaxChunks = scalar_load(&q->binMaxChunks);
-    e.tileTouched = scalar_load(&q->tileTouched);
+    e.tileTouched = scalar_load(&q->tileTouched); e.binInSetup = scalar_load(&q->binInSetup);
     e.shard.ranks = scalar_load(&q->shard.ranks); e.shard.rank = scalar_load(&q->shard.rank); e.shard.slotsPerRank = 0u; e.shard.tilesX = 0u;
     e.shard.ownedRows = scalar_load(&q->shard.ownedRows); e.shard.tileSlot = nullptr;
     return e;
@@ -422,7 +426,8 @@ __device__ __forceinline__ void bin_put(const P& p, uint32_t tile, uint32_t slot
 }
 
 // one slot drawn, written at once (the looped binners: a slot is drawn, allocated for and stored within one iteration)
-__device__ __forceinline__ void bin_store(const RasterParams& p, uint32_t tile, uint32_t slot, uint32_t gi)
+template <class P>
+__device__ __forceinline__ void bin_store(const P& p, uint32_t tile, uint32_t slot, uint32_t gi)
 {
     bin_alloc(p, tile, slot);
     bin_put(p, tile, slot, gi);
@@ -745,6 +750,295 @@ __device__ __forceinline__ void wave_sum2(uint32_t& a, uint32_t& b)
     a = (uint32_t)__builtin_amdgcn_readlane((int)a, 63); b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
 }
 
+// One lane bins one record into every tile its clamped bbox may touch (conservative edge test at the tile
+// corners).  Only the clipped pieces use it; the hot paths go through wave_bin_issue / wave_bin_large.
+template <class P>
+__device__ __forceinline__ void bin_record_tiles(const P& p, const TriSetup& ts, uint32_t gi)
+{
+    const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
+    const int32_t tx0 = ts.px0 >> TILE_SHIFT, tx1 = ts.px1 >> TILE_SHIFT;
+    const int32_t ty0 = ts.py0 >> TILE_SHIFT, ty1 = ts.py1 >> TILE_SHIFT;
+    for (int32_t ty = ty0; ty <= ty1; ty++)
+        for (int32_t tx = tx0; tx <= tx1; tx++) {
+            const int32_t rx0 = max(ts.px0, tx << TILE_SHIFT), rx1 = min(ts.px1, (tx << TILE_SHIFT) + TILE - 1);
+            const int32_t ry0 = max(ts.py0, ty << TILE_SHIFT), ry1 = min(ts.py1, (ty << TILE_SHIFT) + TILE - 1);
+            bool hit = owns_tile(p.shard, tx, ty);
+#pragma unroll
+            for (int i = 0; i < 3; i++) {                         // (unrolled, no early exit: the vertex arrays stay in registers)
+                const int64_t dxe = (int64_t)(ts.X[eb[i]] - ts.X[ea[i]]), dye = (int64_t)(ts.Y[eb[i]] - ts.Y[ea[i]]);
+                const int64_t a = -(int64_t)ts.s * dye, b = (int64_t)ts.s * dxe;
+                const int64_t bias = (a > 0 || (a == 0 && b > 0)) ? 0 : -1;
+                const int64_t cx = (int64_t)(a > 0 ? rx1 : rx0) * 256 + 128, cy = (int64_t)(b > 0 ? ry1 : ry0) * 256 + 128;
+                hit = hit && !((int64_t)ts.s * (dxe * (cy - ts.Y[ea[i]]) - dye * (cx - ts.X[ea[i]])) + bias < 0);
+            }
+            if (!hit) continue;
+            const uint32_t tile = (uint32_t)ty * p.tilesX + (uint32_t)tx;
+            const uint32_t slot = atomicAdd(&p.tileCount[(size_t)tile * TC_STRIDE], 1u);
+            bin_store(p, tile, slot, gi);
+            if ((gi & 0xE0000000u) == CHORD_REC_MASKED) p.tileCount[(size_t)tile * TC_STRIDE + TC_MASKED] = 1u;
+        }
+}
+
+// ---- large records: binned by the set-up wave that made them ----------------------------------------------------
+// A record whose bbox spans more than 2x2 tiles (touches_many_tiles) is binned into every tile that passes the conservative
+// corner test of bin_record_tiles.  The (record, candidate tile) pairs of ALL the wave's large records of a cluster are laid
+// end to end (lane order, A before B within a lane) and dealt out LARGE_ROUND per lane (64 pairs per round): a lane finds the record of its pair by a
+// binary search over the wave's prefix counts and tests the tile; every reservation of a round is issued before the first is
+// waited for, then every slot is allocated for before the first store (bin_put's contract).  The records wait in the wave's
+// slice of sVert (LargeLds: held in registers across the record stores and the small records' bin writes they cost the kernel
+// its occupancy), record k = lane (A) or 64 + lane (B).
+#define LARGE_ROUND 1           // (2 or more: the record kernel spills)
+struct LargeLds {
+    float* f[5];                                        // the wave's x, y, u, v, depth arrays: fields 2i and 2i + 1 in f[i]
+    __device__ __forceinline__ uint32_t& at(int field, uint32_t k) const { return reinterpret_cast<uint32_t*>(f[field >> 1])[(uint32_t)(field & 1) * 128u + k]; }
+};
+enum { LG_X0 = 0, LG_Y0 = 3, LG_S = 6, LG_BX = 7, LG_BY = 8, LG_GI = 9 };
+// (bbox packed in halves: the pixel coordinates of a clamped bbox fit 16 bits)
+__device__ __forceinline__ void large_put(const LargeLds& L, uint32_t k, const TriSetup& ts)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) { L.at(LG_X0 + i, k) = (uint32_t)ts.X[i]; L.at(LG_Y0 + i, k) = (uint32_t)ts.Y[i]; }
+    L.at(LG_S, k) = (uint32_t)ts.s;
+    L.at(LG_BX, k) = (uint32_t)ts.px0 | (uint32_t)ts.px1 << 16; L.at(LG_BY, k) = (uint32_t)ts.py0 | (uint32_t)ts.py1 << 16;
+}
+__device__ __forceinline__ uint32_t large_tiles(uint32_t bx, uint32_t by)
+{
+    return (((bx >> 16) >> TILE_SHIFT) - ((bx & 0xFFFFu) >> TILE_SHIFT) + 1u) * (((by >> 16) >> TILE_SHIFT) - ((by & 0xFFFFu) >> TILE_SHIFT) + 1u);
+}
+template <class P>
+__device__ __forceinline__ void wave_bin_large(const P& e, const LargeLds& L, bool hasA, bool hasB, uint32_t lane)
+{
+    const uint32_t nA = hasA ? large_tiles(L.at(LG_BX, lane), L.at(LG_BY, lane)) : 0u;
+    const uint32_t n = nA + (hasB ? large_tiles(L.at(LG_BX, 64u + lane), L.at(LG_BY, 64u + lane)) : 0u);
+    uint32_t incl = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t nb = (uint32_t)__shfl_up((int)incl, d, 64); if (lane >= (uint32_t)d) incl += nb; }
+    const uint32_t total = bcast(incl, 63), excl = incl - n;
+    for (uint32_t base = 0; base < total; base += 64u * LARGE_ROUND) {
+        uint32_t tile[LARGE_ROUND], slot[LARGE_ROUND], gi[LARGE_ROUND];
+        bool hit[LARGE_ROUND];
+#pragma unroll
+        for (int r = 0; r < LARGE_ROUND; r++) {
+            const uint32_t j = base + (uint32_t)r * 64u + lane, jj = min(j, total - 1u);   // (every lane shuffles: no lane is inactive)
+            int src = 0;                                                                // the first lane whose inclusive count exceeds jj
+#pragma unroll
+            for (int st = 32; st > 0; st >>= 1) if ((uint32_t)__shfl((int)incl, src + st - 1, 64) <= jj) src += st;
+            const uint32_t off = jj - (uint32_t)__shfl((int)excl, src, 64), offA = (uint32_t)__shfl((int)nA, src, 64);
+            const uint32_t k = (uint32_t)src + (off >= offA ? 64u : 0u), t = off >= offA ? off - offA : off;
+            TriSetup ts;
+#pragma unroll
+            for (int i = 0; i < 3; i++) { ts.X[i] = (int32_t)L.at(LG_X0 + i, k); ts.Y[i] = (int32_t)L.at(LG_Y0 + i, k); }
+            ts.s = (int32_t)L.at(LG_S, k);
+            const uint32_t bx = L.at(LG_BX, k), by = L.at(LG_BY, k);
+            gi[r] = L.at(LG_GI, k);
+            ts.px0 = (int32_t)(bx & 0xFFFFu); ts.px1 = (int32_t)(bx >> 16); ts.py0 = (int32_t)(by & 0xFFFFu); ts.py1 = (int32_t)(by >> 16);
+            const int32_t tx0 = ts.px0 >> TILE_SHIFT, ty0 = ts.py0 >> TILE_SHIFT;
+            const uint32_t tw = (uint32_t)((ts.px1 >> TILE_SHIFT) - tx0 + 1);
+            const int32_t tx = tx0 + (int32_t)(t % tw), ty = ty0 + (int32_t)(t / tw);
+            // pixel rectangle of this tile clipped to the triangle's bbox; conservative edge test at its corners (bin_record_tiles)
+            const int32_t rx0 = max(ts.px0, tx << TILE_SHIFT), rx1 = min(ts.px1, (tx << TILE_SHIFT) + TILE - 1);
+            const int32_t ry0 = max(ts.py0, ty << TILE_SHIFT), ry1 = min(ts.py1, (ty << TILE_SHIFT) + TILE - 1);
+            const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
+            bool h = j < total && owns_tile(e.shard, tx, ty);
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const int64_t dxe = (int64_t)(ts.X[eb[i]] - ts.X[ea[i]]), dye = (int64_t)(ts.Y[eb[i]] - ts.Y[ea[i]]);
+                const int64_t a = -(int64_t)ts.s * dye, b = (int64_t)ts.s * dxe;
+                const int64_t bias = (a > 0 || (a == 0 && b > 0)) ? 0 : -1;
+                const int64_t cx = (int64_t)(a > 0 ? rx1 : rx0) * 256 + 128, cy = (int64_t)(b > 0 ? ry1 : ry0) * 256 + 128;
+                h = h && !((int64_t)ts.s * (dxe * (cy - ts.Y[ea[i]]) - dye * (cx - ts.X[ea[i]])) + bias < 0);
+            }
+            hit[r] = h;
+            tile[r] = h ? (uint32_t)ty * e.tilesX + (uint32_t)tx : 0u;
+            slot[r] = h ? atomicAdd(&e.tileCount[(size_t)tile[r] * TC_STRIDE], 1u) : 0u;
+        }
+#pragma unroll
+        for (int r = 0; r < LARGE_ROUND; r++) if (hit[r]) bin_alloc(e, tile[r], slot[r]);
+#pragma unroll
+        for (int r = 0; r < LARGE_ROUND; r++) {
+            if (!hit[r]) continue;
+            bin_put(e, tile[r], slot[r], gi[r]);
+            if ((gi[r] & 0xE0000000u) == CHORD_REC_MASKED) e.tileCount[(size_t)tile[r] * TC_STRIDE + TC_MASKED] = 1u;
+        }
+    }
+}
+
+// ---- clipper kernel (rare path) ---------------------------------------------------------------
+__device__ __forceinline__ float clip_dist(const f4& v, int k)
+{
+    switch (k) {
+    case 0: return v.w - v.z;
+    case 1: return v.z;
+    case 2: return GUARD_BAND * v.w + v.x;
+    case 3: return GUARD_BAND * v.w - v.x;
+    case 4: return GUARD_BAND * v.w + v.y;
+    default: return GUARD_BAND * v.w - v.y;
+    }
+}
+
+__device__ __forceinline__ f4 clip_intersect(const f4& in, const f4& out, float din, float dout)
+{
+    const float t = din / (din - dout);
+    f4 r;
+    r.x = in.x + (out.x - in.x) * t;
+    r.y = in.y + (out.y - in.y) * t;
+    r.z = in.z + (out.z - in.z) * t;
+    r.w = in.w + (out.w - in.w) * t;
+    return r;
+}
+
+// The polygon being clipped (Sutherland-Hodgman ping-pong, <= 3 + 6 vertices) is indexed dynamically, which in registers means
+// scratch memory (round 2: 592 bytes per lane).  It lives in LDS instead, slot-major ([buffer][vertex][thread]: consecutive
+// threads in consecutive banks); one wave per clip block works, which bounds the arrays to 38 KB.
+#define CLIP_MAXV 10
+#define CLIP_THREADS 64u
+// LDS polygon storage of STRIDE threads (thread tl): two ping-pong buffers of clip-space vertices + texture coordinates, and
+// the projected vertices of the result
+template <uint32_t STRIDE>
+struct ClipLds {
+    float4* poly; float* pu; float* pv; int32_t* px; int32_t* py; float* pd; uint32_t tl;
+    __device__ __forceinline__ float4& P(int bf, int i) const { return poly[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
+    __device__ __forceinline__ float& U(int bf, int i) const { return pu[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
+    __device__ __forceinline__ float& V(int bf, int i) const { return pv[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
+    __device__ __forceinline__ int32_t& X(int i) const { return px[(uint32_t)i * STRIDE + tl]; }
+    __device__ __forceinline__ int32_t& Y(int i) const { return py[(uint32_t)i * STRIDE + tl]; }
+    __device__ __forceinline__ float& D(int i) const { return pd[(uint32_t)i * STRIDE + tl]; }
+};
+
+// One triangle of a cluster through the homogeneous clipper: its vertices are transformed again from the position stream (the
+// clip-space z is not kept by the setup kernels), clipped against near / far (unless depth-clamped) and the guard band, and
+// projected + snapped into L.X / L.Y / L.D.  Returns the vertex count of the resulting polygon (a fan around vertex 0), 0 when
+// nothing is left; `cur` is the buffer that holds its clip-space vertices and texture coordinates.
+template <uint32_t STRIDE, class Prm>
+__device__ __forceinline__ int clip_triangle(const Prm& p, const ClipLds<STRIDE>& L, uint32_t dataOffset, uint32_t vertexBase, uint32_t V, uint32_t tri,
+                                             const Mat4& mvp, bool masked, int& cur)
+{
+    const uint32_t packedIdx = p.meshletData[dataOffset + V + tri];
+    for (int i = 0; i < 3; i++) {
+        const uint32_t li = (packedIdx >> (8 * i)) & 0xFFu;
+        const uint32_t vi = p.meshletData[dataOffset + li] + vertexBase;
+        const float* pos = p.positions + (size_t)vi * 3;
+        const f4 h = mul_mv(mvp, pos[0], pos[1], pos[2], 1.0f);
+        L.P(0, i) = make_float4(h.x, h.y, h.z, h.w);
+        float u = 0.0f, v = 0.0f;
+        if (masked && p.texcoords) { u = p.texcoords[(size_t)vi * 2]; v = p.texcoords[(size_t)vi * 2 + 1]; }
+        L.U(0, i) = u; L.V(0, i) = v;
+    }
+    int np = 3;
+    cur = 0;
+    for (int pl = p.depthClamp ? 2 : 0; pl < 6 && np >= 3; pl++) {
+        int m2 = 0;
+        for (int i = 0; i < np; i++) {
+            const int j = (i + 1) % np;
+            const float4 Pv = L.P(cur, i), Qv = L.P(cur, j);
+            const f4 P = {Pv.x, Pv.y, Pv.z, Pv.w}, Q = {Qv.x, Qv.y, Qv.z, Qv.w};
+            const float pui = L.U(cur, i), pvi = L.V(cur, i), puj = L.U(cur, j), pvj = L.V(cur, j);
+            const float dp = clip_dist(P, pl), dq = clip_dist(Q, pl);
+            const bool pin = dp >= 0.0f, qin = dq >= 0.0f;
+            if (pin && m2 < CLIP_MAXV) { L.U(cur ^ 1, m2) = pui; L.V(cur ^ 1, m2) = pvi; L.P(cur ^ 1, m2) = Pv; m2++; }
+            if (pin && !qin && m2 < CLIP_MAXV) {
+                const float t = dp / (dp - dq);
+                L.U(cur ^ 1, m2) = pui + (puj - pui) * t; L.V(cur ^ 1, m2) = pvi + (pvj - pvi) * t;
+                const f4 x = clip_intersect(P, Q, dp, dq);
+                L.P(cur ^ 1, m2) = make_float4(x.x, x.y, x.z, x.w); m2++;
+            } else if (!pin && qin && m2 < CLIP_MAXV) {
+                const float t = dq / (dq - dp);
+                L.U(cur ^ 1, m2) = puj + (pui - puj) * t; L.V(cur ^ 1, m2) = pvj + (pvi - pvj) * t;
+                const f4 x = clip_intersect(Q, P, dq, dp);
+                L.P(cur ^ 1, m2) = make_float4(x.x, x.y, x.z, x.w); m2++;
+            }
+        }
+        np = m2; cur ^= 1;
+    }
+    if (np < 3) return 0;
+    for (int i = 0; i < np; i++) {
+        const float4 h = L.P(cur, i);
+        if (!(h.w > 0.0f)) return 0;
+        const float u = h.x / fabsf(h.w) * 0.5f + 0.5f;
+        const float v = h.y / fabsf(h.w) * -0.5f + 0.5f;
+        L.X(i) = (int32_t)rintf((u * p.W) * 256.0f);
+        L.Y(i) = (int32_t)rintf((v * p.H) * 256.0f);
+        L.D(i) = h.z / h.w;
+    }
+    return np;
+}
+
+// The pieces of a clipped polygon (a fan around its vertex 0, clip_triangle): set up, stored as 48-byte records (+ the mask
+// extension) and binned by the lane itself.  listShard: the record list shard the pieces go to.
+template <uint32_t STRIDE, class P>
+__device__ __forceinline__ void clip_emit(const P& p, const ClipLds<STRIDE>& L, int np, int cur, uint32_t payload, bool twoSided, bool masked,
+                                          uint32_t matFlags, uint32_t listShard)
+{
+    const uint32_t slots = masked ? 1u + CHORD_MASK_EXT_SLOTS : 1u;
+    for (int i = 1; i + 1 < np; i++) {
+        TriSetup ts;
+        ts.X[0] = L.X(0); ts.X[1] = L.X(i); ts.X[2] = L.X(i + 1);
+        ts.Y[0] = L.Y(0); ts.Y[1] = L.Y(i); ts.Y[2] = L.Y(i + 1);
+        float d[3] = {L.D(0), L.D(i), L.D(i + 1)};
+        ts.payload = payload;
+        if (!tri_setup(ts, twoSided, p.Wi, p.Hi) || !owns_rect(p.shard, ts.px0, ts.py0, ts.px1, ts.py1)) continue;
+        if (p.biasConst != 0.0f || p.biasSlope != 0.0f) { const float o = depth_bias(ts, d, p.biasConst, p.biasSlope); d[0] += o; d[1] += o; d[2] += o; }
+        const uint32_t li = atomicAdd(&p.counters->triCount[listShard * CHORD_SHARD_STRIDE], slots);
+        if (li + slots > p.triCap) { atomicOr(&p.counters->overflow, 1u); continue; }
+        const uint32_t gi = listShard * p.triCap + li;
+        write_record(&p.tris[gi], ts, d, twoSided, masked);
+        if (masked) {
+            const uint32_t material = CHORD_MATFLAG_MATERIAL(matFlags);
+            const float u3[3] = {L.U(cur, 0), L.U(cur, i), L.U(cur, i + 1)}, v3[3] = {L.V(cur, 0), L.V(cur, i), L.V(cur, i + 1)};
+            const float w3[3] = {L.P(cur, 0).w, L.P(cur, i).w, L.P(cur, i + 1).w};
+            write_mask_ext(&p.tris[gi + 1u], &p.materials[material], material, ts.area, u3, v3, w3);
+        }
+        // clipped pieces are rare: binned right here, one (scattered) atomic per tile they may touch
+        bin_record_tiles(p, ts, gi | (masked ? CHORD_REC_MASKED : CHORD_REC_WIDE));   // clipped pieces take the 48-byte form
+    }
+}
+
+// One entry of the clip list through the clipper: the cluster's records, matrix and flags, then clip_triangle + clip_emit.
+// MASKED = false: the scene has no alpha-tested material (the record kernel's plain instantiation).
+template <bool MASKED, uint32_t STRIDE, class P>
+__device__ __forceinline__ void clip_entry(const P& p, const ClipLds<STRIDE>& L, const ClipTri ct, uint32_t listShard)
+{
+    const DMeshlet& m = p.meshlets[ct.meshletId];
+    const uint32_t V = m.vertexTriangleCount & 0xFFu;
+    const uint32_t matFlags = p.objStatic[ct.objectId].matFlags;
+    const bool twoSided = (matFlags & CHORD_MATFLAG_TWO_SIDED) != 0u || p.depthOnly != 0u;
+    const bool masked = MASKED && CHORD_MATFLAG_ALPHA(matFlags) == CHORD_ALPHA_MASK;
+    const float* mv = p.objFrame[ct.objectId].mvp;
+    Mat4 mvp;
+    for (int r = 0; r < 4; r++) for (int cc = 0; cc < 4; cc++) mvp.r[r][cc] = mv[r * 4 + cc];
+    int cur;
+    const int np = clip_triangle(p, L, m.dataOffset, m.vertexBase, V, ct.tri, mvp, masked, cur);
+    if (np < 3) return;
+    const uint32_t payload = p.depthOnly ? 0u : encode_triangle_instance(ct.tri, ct.slot);
+    clip_emit(p, L, np, cur, payload, twoSided, masked, matFlags, listShard);
+}
+
+// What the set-up wave needs to clip and emit the clip triangles of its clusters (the record emission's parameters + the scene's),
+// read from the kernel-argument segment where it is used (RecordEmitParams)
+struct SetupClipParams : RecordEmitParams {
+    const DObjFrame* objFrame; const DObjStatic* objStatic; const DMeshlet* meshlets;
+    const uint32_t* meshletData; const float* positions; const float* texcoords; const DMaterial* materials;
+    uint32_t depthOnly; float W, H; int32_t Wi, Hi; uint32_t depthClamp; float biasConst, biasSlope;
+};
+__device__ __forceinline__ SetupClipParams load_setup_clip_params()
+{
+    const RasterParams* q = kernel_args();
+    SetupClipParams c;
+    static_cast<RecordEmitParams&>(c) = load_record_emit_params();
+    c.objFrame = scalar_load(&q->objFrame); c.objStatic = scalar_load(&q->objStatic); c.meshlets = scalar_load(&q->meshlets); c.depthOnly = scalar_load(&q->depthOnly);
+    c.meshletData = scalar_load(&q->meshletData); c.positions = scalar_load(&q->positions); c.texcoords = scalar_load(&q->texcoords);
+    c.materials = scalar_load(&q->materials);
+    c.W = scalar_load(&q->W); c.H = scalar_load(&q->H); c.Wi = scalar_load(&q->Wi); c.Hi = scalar_load(&q->Hi);
+    c.depthClamp = scalar_load(&q->depthClamp); c.biasConst = scalar_load(&q->biasConst); c.biasSlope = scalar_load(&q->biasSlope);
+    return c;
+}
+// clip triangles a set-up wave clips at once: one per lane, the polygons of CLIP_SETUP_LANES lanes in the wave's slice of sVert
+// (ClipLds: 80 floats of vertices per lane in one 256-float array, 20 + 20 of texture coordinates in the next, 3 x 10 in the third)
+#define CLIP_SETUP_LANES 3u
+#define CLIP_RANGES 255u           // clusters with clip triangles a set-up wave keeps for its end (more: overflow bit 2, as a full clip list)
+static_assert(2u * CLIP_MAXV * CLIP_SETUP_LANES * 4u <= LDS_VERTS && 4u * CLIP_MAXV * CLIP_SETUP_LANES <= LDS_VERTS && 3u * CLIP_MAXV * CLIP_SETUP_LANES <= LDS_VERTS,
+              "a set-up wave's clip polygons fit its slices of sVert");
+
 // ---- the per-cluster setup kernel -------------------------------------------------------------
 enum { K_NONE = 0, K_EMIT = 1, K_CLIP = 2 };
 #define WIN CHORD_BLOCK_WIN
@@ -757,7 +1051,7 @@ enum { K_NONE = 0, K_EMIT = 1, K_CLIP = 2 };
 // -- one round trip instead of two in front of everything else a wave does (a short list is one cluster per wave: the kernel is the
 // chain count -> command -> records -> indices -> positions -> matrix -> reservations, seven dependent round trips until round 6).
 template <bool MASKED>
-__device__ __forceinline__ void raster_setup_body(const RasterParams& p, const ChordDrawCmd* __restrict__ cmds, const uint32_t count, float (*sVert)[4][LDS_VERTS],
+__device__ __forceinline__ void raster_setup_body(const RasterParams& p, const ChordDrawCmd* __restrict__ cmds, const uint32_t count, float (*sVert)[4][LDS_VERTS], uint32_t* sClip,
                                                   const uint32_t firstCmd0, const uint32_t firstCmd1, const uint32_t firstCmd2, const bool firstCmdValid)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -837,6 +1131,7 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
     unsigned long long sph[5] = {0, 0, 0, 0, 0}, stp = sprof ? wall_clock64() : 0ull;
 #define SPHASE(i) do { if (sprof) { const unsigned long long tn = wall_clock64(); sph[i] += tn - stp; stp = tn; } } while (0)
     const uint32_t laneTop = lane;
+    if (lane == 0u) sClip[0] = 0u;
     for (; c < count; c += stride) {
         // (the lane index of this cluster goes through an empty asm: what the body derives from it is invariant over the cluster
         // loop and would otherwise be hoisted out of it and held in registers across the whole kernel -- raster_tile_kernel: 25 VGPRs)
@@ -980,8 +1275,18 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
             BinTicket ticket;
             if (emA | emB) wave_bin_issue(e, kindA == K_EMIT && !lgA, tsA, kindB == K_EMIT && !lgB, tsB, lane, ticket, MASKED && masked);
             cbase = bcast(cbase, 0); ebaseC = bcast(ebaseC, 0); ebaseW = bcast(ebaseW, 0); lbase = bcast(lbase, 0);
+            if (e.binInSetup && (lmA | lmB)) {
+                const LargeLds LL = {{lX, lY, lU, lV, lD}};
+                if (lgA) large_put(LL, lane, tsA);
+                if (lgB) large_put(LL, 64u + lane, tsB);
+            }
             SPHASE(3);
             mvpNext = mvp_of(hdrN.objectId);              // (the next cluster's matrix: on its way while this one's records are stored)
+            if (e.binInSetup && nClip && lane == 0u) {
+                // (the wave clips its clip triangles itself once its clusters are done: their ranges of the clip list wait in LDS)
+                const uint32_t r = sClip[0];
+                if (r < CLIP_RANGES) { sClip[1u + r] = cbase | (nClip - 1u) << 25; sClip[0] = r + 1u; } else atomicOr(&e.counters->overflow, 2u);
+            }
             if (kindA == K_CLIP) {
                 const uint32_t k = cbase + (uint32_t)__popcll(cmA & lt);
                 if (k < e.clipTriCap) { ClipTri ct; ct.objectId = hdr.objectId; ct.meshletId = hdr.meshletId; ct.slot = hdr.slot; ct.tri = lane; e.clipTris[k] = ct; }
@@ -1019,13 +1324,20 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
                     giB |= (MASKED && masked) ? CHORD_REC_MASKED : CHORD_REC_WIDE; okB = true;
                 } else atomicOr(&e.counters->overflow, 1u);
             }
-            // <= 2x2 tiles: straight into the bins; more: the large list
+            // <= 2x2 tiles: straight into the bins; more: a round of their own below (or the large list)
+            const LargeLds LL = {{lX, lY, lU, lV, lD}};
+            if (e.binInSetup && (lmA | lmB)) {
+                if (lgA && okA) LL.at(LG_GI, lane) = giA;
+                if (lgB && okB) LL.at(LG_GI, 64u + lane) = giB;
+            }
             if (emA | emB) wave_bin_commit(e, ticket, okA, giA, okB, giB);
-            if (lgA && okA) {
+            if (e.binInSetup) {
+                if (lmA | lmB) wave_bin_large(e, LL, lgA && okA, lgB && okB, lane);
+            } else if (lgA && okA) {
                 const uint32_t k = lbase + (uint32_t)__popcll(lmA & lt);
                 if (k < e.largeCap) e.largeList[(size_t)listShard * e.largeCap + k] = giA & CHORD_REC_WIDE_INDEX; else atomicOr(&e.counters->overflow, 1u);
             }
-            if (lgB && okB) {
+            if (lgB && okB && !e.binInSetup) {
                 const uint32_t k = lbase + (uint32_t)__popcll(lmA) + (uint32_t)__popcll(lmB & lt);
                 if (k < e.largeCap) e.largeList[(size_t)listShard * e.largeCap + k] = giB & CHORD_REC_WIDE_INDEX; else atomicOr(&e.counters->overflow, 1u);
             }
@@ -1040,6 +1352,22 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
         t0 = nt0; t1 = nt1;
         pax = nax; pay = nay; paz = naz; pbx = nbx; pby = nby; pbz = nbz;
         SPHASE(4);
+    }
+    // the clip triangles of the wave's clusters: clipped, emitted and binned now, CLIP_SETUP_LANES at a time in the wave's slice of sVert
+    // (in the loop, the clipper's registers came on top of the pipeline's: the kernel spilled)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (const uint32_t ranges = __builtin_amdgcn_readfirstlane(sClip[0])) {
+        const SetupClipParams q = load_setup_clip_params();
+        const ClipLds<CLIP_SETUP_LANES> L = {reinterpret_cast<float4*>(lX), lY, lY + 2u * CLIP_MAXV * CLIP_SETUP_LANES,
+                                             reinterpret_cast<int32_t*>(lW), reinterpret_cast<int32_t*>(lW) + CLIP_MAXV * CLIP_SETUP_LANES,
+                                             lW + 2u * CLIP_MAXV * CLIP_SETUP_LANES, lane};
+        for (uint32_t i = 0; i < ranges; i++) {
+            const uint32_t w = __builtin_amdgcn_readfirstlane(sClip[1u + i]), base = w & 0x1FFFFFFu, n = (w >> 25) + 1u;
+            for (uint32_t k0 = 0; k0 < n; k0 += CLIP_SETUP_LANES)
+                if (lane < CLIP_SETUP_LANES && k0 + lane < n && base + k0 + lane < q.clipTriCap) clip_entry<MASKED>(q, L, q.clipTris[base + k0 + lane], listShard);
+        }
     }
     if (sprof && lane == 0u) {
         const uint32_t w = blockIdx.x * 4u + wave;
@@ -1507,7 +1835,8 @@ __device__ __forceinline__ bool launch_is_dense(const RasterParams& p, uint32_t 
 template <bool MASKED>
 __global__ __launch_bounds__(256, MASKED ? SETUP_MASKED_WAVES : SETUP_MIN_WAVES) void raster_setup_kernel(RasterParams p)   // (masked: twelve more live registers, see uvA)
 {
-    __shared__ float sVert[6][4][LDS_VERTS];                   // x, y, w, u, v, depth of a wave's cluster (24 KB)
+    __shared__ __attribute__((aligned(16))) float sVert[6][4][LDS_VERTS];   // x, y, w, u, v, depth of a wave's cluster (24 KB; 16-byte aligned: ClipLds)
+    __shared__ uint32_t sClip[4][1 + CLIP_RANGES];             // a wave's ranges of the clip list (binInSetup: count, then base | (n - 1) << 25)
     // the wave's first command is asked for TOGETHER with the count (the list has room for the index whatever the count turns out to be)
     const uint32_t c0 = __builtin_amdgcn_readfirstlane(min(blockIdx.x * 4u + (threadIdx.x >> 6), p.cmdCap - 1u));
     const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(p.cmds + c0);
@@ -1516,7 +1845,7 @@ __global__ __launch_bounds__(256, MASKED ? SETUP_MASKED_WAVES : SETUP_MIN_WAVES)
     const ChordDrawCmd* cmds = p.cmds;
     bool firstValid = true;
     if (launch_is_dense(p, count)) { count = *p.leftCount; cmds = p.leftCmds; firstValid = false; }   // (what the block kernel left over: another list)
-    raster_setup_body<MASKED>(p, cmds, count, sVert, f0, f1, f2, firstValid);
+    raster_setup_body<MASKED>(p, cmds, count, sVert, sClip[threadIdx.x >> 6], f0, f1, f2, firstValid);
 }
 
 // HOT: the variant that draws bin slots ahead on hot tiles (above).  It costs the plain kernel's loop 3 % (registers: the loop
@@ -1534,134 +1863,6 @@ __global__ __launch_bounds__(256, BLOCKS_MIN_WAVES) void raster_setup_blocks_ker
     raster_setup_blocks_body<HOT>(p, count, sVert, sSnap, sWin, sSlots);
 }
 
-// One lane bins one record into every tile its clamped bbox may touch (conservative edge test at the tile
-// corners).  Only the clipper uses it; the hot paths go through wave_bin_small2 / raster_bin_large_kernel.
-__device__ void bin_record_tiles(const RasterParams& p, const TriSetup& ts, uint32_t gi)
-{
-    const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
-    const int32_t tx0 = ts.px0 >> TILE_SHIFT, tx1 = ts.px1 >> TILE_SHIFT;
-    const int32_t ty0 = ts.py0 >> TILE_SHIFT, ty1 = ts.py1 >> TILE_SHIFT;
-    for (int32_t ty = ty0; ty <= ty1; ty++)
-        for (int32_t tx = tx0; tx <= tx1; tx++) {
-            const int32_t rx0 = max(ts.px0, tx << TILE_SHIFT), rx1 = min(ts.px1, (tx << TILE_SHIFT) + TILE - 1);
-            const int32_t ry0 = max(ts.py0, ty << TILE_SHIFT), ry1 = min(ts.py1, (ty << TILE_SHIFT) + TILE - 1);
-            bool hit = owns_tile(p.shard, tx, ty);
-#pragma unroll
-            for (int i = 0; i < 3; i++) {                         // (unrolled, no early exit: the vertex arrays stay in registers)
-                const int64_t dxe = (int64_t)(ts.X[eb[i]] - ts.X[ea[i]]), dye = (int64_t)(ts.Y[eb[i]] - ts.Y[ea[i]]);
-                const int64_t a = -(int64_t)ts.s * dye, b = (int64_t)ts.s * dxe;
-                const int64_t bias = (a > 0 || (a == 0 && b > 0)) ? 0 : -1;
-                const int64_t cx = (int64_t)(a > 0 ? rx1 : rx0) * 256 + 128, cy = (int64_t)(b > 0 ? ry1 : ry0) * 256 + 128;
-                hit = hit && !((int64_t)ts.s * (dxe * (cy - ts.Y[ea[i]]) - dye * (cx - ts.X[ea[i]])) + bias < 0);
-            }
-            if (!hit) continue;
-            const uint32_t tile = (uint32_t)ty * p.tilesX + (uint32_t)tx;
-            const uint32_t slot = atomicAdd(&p.tileCount[(size_t)tile * TC_STRIDE], 1u);
-            bin_store(p, tile, slot, gi);
-            if ((gi & 0xE0000000u) == CHORD_REC_MASKED) p.tileCount[(size_t)tile * TC_STRIDE + TC_MASKED] = 1u;
-        }
-}
-
-// ---- clipper kernel (rare path) ---------------------------------------------------------------
-__device__ __forceinline__ float clip_dist(const f4& v, int k)
-{
-    switch (k) {
-    case 0: return v.w - v.z;
-    case 1: return v.z;
-    case 2: return GUARD_BAND * v.w + v.x;
-    case 3: return GUARD_BAND * v.w - v.x;
-    case 4: return GUARD_BAND * v.w + v.y;
-    default: return GUARD_BAND * v.w - v.y;
-    }
-}
-
-__device__ __forceinline__ f4 clip_intersect(const f4& in, const f4& out, float din, float dout)
-{
-    const float t = din / (din - dout);
-    f4 r;
-    r.x = in.x + (out.x - in.x) * t;
-    r.y = in.y + (out.y - in.y) * t;
-    r.z = in.z + (out.z - in.z) * t;
-    r.w = in.w + (out.w - in.w) * t;
-    return r;
-}
-
-// The polygon being clipped (Sutherland-Hodgman ping-pong, <= 3 + 6 vertices) is indexed dynamically, which in registers means
-// scratch memory (round 2: 592 bytes per lane).  It lives in LDS instead, slot-major ([buffer][vertex][thread]: consecutive
-// threads in consecutive banks); one wave per clip block works, which bounds the arrays to 38 KB.
-#define CLIP_MAXV 10
-#define CLIP_THREADS 64u
-// LDS polygon storage of STRIDE threads (thread tl): two ping-pong buffers of clip-space vertices + texture coordinates, and
-// the projected vertices of the result
-template <uint32_t STRIDE>
-struct ClipLds {
-    float4* poly; float* pu; float* pv; int32_t* px; int32_t* py; float* pd; uint32_t tl;
-    __device__ __forceinline__ float4& P(int bf, int i) const { return poly[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
-    __device__ __forceinline__ float& U(int bf, int i) const { return pu[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
-    __device__ __forceinline__ float& V(int bf, int i) const { return pv[((uint32_t)bf * CLIP_MAXV + (uint32_t)i) * STRIDE + tl]; }
-    __device__ __forceinline__ int32_t& X(int i) const { return px[(uint32_t)i * STRIDE + tl]; }
-    __device__ __forceinline__ int32_t& Y(int i) const { return py[(uint32_t)i * STRIDE + tl]; }
-    __device__ __forceinline__ float& D(int i) const { return pd[(uint32_t)i * STRIDE + tl]; }
-};
-
-// One triangle of a cluster through the homogeneous clipper: its vertices are transformed again from the position stream (the
-// clip-space z is not kept by the setup kernels), clipped against near / far (unless depth-clamped) and the guard band, and
-// projected + snapped into L.X / L.Y / L.D.  Returns the vertex count of the resulting polygon (a fan around vertex 0), 0 when
-// nothing is left; `cur` is the buffer that holds its clip-space vertices and texture coordinates.
-template <uint32_t STRIDE>
-__device__ __forceinline__ int clip_triangle(const RasterParams& p, const ClipLds<STRIDE>& L, const DMeshlet& m, uint32_t V, uint32_t tri,
-                                             const Mat4& mvp, bool masked, int& cur)
-{
-    const uint32_t packedIdx = p.meshletData[m.dataOffset + V + tri];
-    for (int i = 0; i < 3; i++) {
-        const uint32_t li = (packedIdx >> (8 * i)) & 0xFFu;
-        const uint32_t vi = p.meshletData[m.dataOffset + li] + m.vertexBase;
-        const float* pos = p.positions + (size_t)vi * 3;
-        const f4 h = mul_mv(mvp, pos[0], pos[1], pos[2], 1.0f);
-        L.P(0, i) = make_float4(h.x, h.y, h.z, h.w);
-        float u = 0.0f, v = 0.0f;
-        if (masked && p.texcoords) { u = p.texcoords[(size_t)vi * 2]; v = p.texcoords[(size_t)vi * 2 + 1]; }
-        L.U(0, i) = u; L.V(0, i) = v;
-    }
-    int np = 3;
-    cur = 0;
-    for (int pl = p.depthClamp ? 2 : 0; pl < 6 && np >= 3; pl++) {
-        int m2 = 0;
-        for (int i = 0; i < np; i++) {
-            const int j = (i + 1) % np;
-            const float4 Pv = L.P(cur, i), Qv = L.P(cur, j);
-            const f4 P = {Pv.x, Pv.y, Pv.z, Pv.w}, Q = {Qv.x, Qv.y, Qv.z, Qv.w};
-            const float pui = L.U(cur, i), pvi = L.V(cur, i), puj = L.U(cur, j), pvj = L.V(cur, j);
-            const float dp = clip_dist(P, pl), dq = clip_dist(Q, pl);
-            const bool pin = dp >= 0.0f, qin = dq >= 0.0f;
-            if (pin && m2 < CLIP_MAXV) { L.U(cur ^ 1, m2) = pui; L.V(cur ^ 1, m2) = pvi; L.P(cur ^ 1, m2) = Pv; m2++; }
-            if (pin && !qin && m2 < CLIP_MAXV) {
-                const float t = dp / (dp - dq);
-                L.U(cur ^ 1, m2) = pui + (puj - pui) * t; L.V(cur ^ 1, m2) = pvi + (pvj - pvi) * t;
-                const f4 x = clip_intersect(P, Q, dp, dq);
-                L.P(cur ^ 1, m2) = make_float4(x.x, x.y, x.z, x.w); m2++;
-            } else if (!pin && qin && m2 < CLIP_MAXV) {
-                const float t = dq / (dq - dp);
-                L.U(cur ^ 1, m2) = puj + (pui - puj) * t; L.V(cur ^ 1, m2) = pvj + (pvi - pvj) * t;
-                const f4 x = clip_intersect(Q, P, dq, dp);
-                L.P(cur ^ 1, m2) = make_float4(x.x, x.y, x.z, x.w); m2++;
-            }
-        }
-        np = m2; cur ^= 1;
-    }
-    if (np < 3) return 0;
-    for (int i = 0; i < np; i++) {
-        const float4 h = L.P(cur, i);
-        if (!(h.w > 0.0f)) return 0;
-        const float u = h.x / fabsf(h.w) * 0.5f + 0.5f;
-        const float v = h.y / fabsf(h.w) * -0.5f + 0.5f;
-        L.X(i) = (int32_t)rintf((u * p.W) * 256.0f);
-        L.Y(i) = (int32_t)rintf((v * p.H) * 256.0f);
-        L.D(i) = h.z / h.w;
-    }
-    return np;
-}
-
 __device__ void raster_clip_part(const RasterParams& p, uint32_t block, uint32_t blocks)
 {
     __shared__ float4 sPoly[2 * CLIP_MAXV * CLIP_THREADS];
@@ -1673,42 +1874,7 @@ __device__ void raster_clip_part(const RasterParams& p, uint32_t block, uint32_t
     const uint32_t n = min(p.counters->clipTriCount[p.pass], p.clipTriCap);
     const uint32_t listShard = block % CHORD_LIST_SHARDS;
     for (uint32_t k = block * CLIP_THREADS + threadIdx.x; k < n; k += blocks * CLIP_THREADS) {
-        const ClipTri ct = p.clipTris[k];
-        ChordDrawCmd cmd; cmd.objectId = ct.objectId; cmd.meshletId = ct.meshletId; cmd.slot = ct.slot;
-        const DMeshlet& m = p.meshlets[cmd.meshletId];
-        const uint32_t V = m.vertexTriangleCount & 0xFFu;
-        const uint32_t matFlags = p.objStatic[cmd.objectId].matFlags;
-        const bool twoSided = (matFlags & CHORD_MATFLAG_TWO_SIDED) != 0u || p.depthOnly != 0u;
-        const bool masked = CHORD_MATFLAG_ALPHA(matFlags) == CHORD_ALPHA_MASK;
-        const float* mv = p.objFrame[cmd.objectId].mvp;
-        Mat4 mvp;
-        for (int r = 0; r < 4; r++) for (int cc = 0; cc < 4; cc++) mvp.r[r][cc] = mv[r * 4 + cc];
-        int cur;
-        const int np = clip_triangle(p, L, m, V, ct.tri, mvp, masked, cur);
-        if (np < 3) continue;
-        const uint32_t payload = p.depthOnly ? 0u : encode_triangle_instance(ct.tri, cmd.slot);
-        const uint32_t slots = masked ? 1u + CHORD_MASK_EXT_SLOTS : 1u;
-        for (int i = 1; i + 1 < np; i++) {
-            TriSetup ts;
-            ts.X[0] = L.X(0); ts.X[1] = L.X(i); ts.X[2] = L.X(i + 1);
-            ts.Y[0] = L.Y(0); ts.Y[1] = L.Y(i); ts.Y[2] = L.Y(i + 1);
-            float d[3] = {L.D(0), L.D(i), L.D(i + 1)};
-            ts.payload = payload;
-            if (!tri_setup(ts, twoSided, p.Wi, p.Hi) || !owns_rect(p.shard, ts.px0, ts.py0, ts.px1, ts.py1)) continue;
-            if (p.biasConst != 0.0f || p.biasSlope != 0.0f) { const float o = depth_bias(ts, d, p.biasConst, p.biasSlope); d[0] += o; d[1] += o; d[2] += o; }
-            const uint32_t li = atomicAdd(&p.counters->triCount[listShard * CHORD_SHARD_STRIDE], slots);
-            if (li + slots > p.triCap) { atomicOr(&p.counters->overflow, 1u); continue; }
-            const uint32_t gi = listShard * p.triCap + li;
-            write_record(&p.tris[gi], ts, d, twoSided, masked);
-            if (masked) {
-                const uint32_t material = CHORD_MATFLAG_MATERIAL(matFlags);
-                const float u3[3] = {L.U(cur, 0), L.U(cur, i), L.U(cur, i + 1)}, v3[3] = {L.V(cur, 0), L.V(cur, i), L.V(cur, i + 1)};
-                const float w3[3] = {L.P(cur, 0).w, L.P(cur, i).w, L.P(cur, i + 1).w};
-                write_mask_ext(&p.tris[gi + 1u], &p.materials[material], material, ts.area, u3, v3, w3);
-            }
-            // clipped pieces are rare: binned right here, one (scattered) atomic per tile they may touch
-            bin_record_tiles(p, ts, gi | (masked ? CHORD_REC_MASKED : CHORD_REC_WIDE));   // clipped pieces take the 48-byte form
-        }
+        clip_entry<true>(p, L, p.clipTris[k], listShard);
     }
 }
 
@@ -3434,6 +3600,10 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     p.tilesX = c->tilesX; p.tilesY = c->tilesY;
     p.clipTris = c->dClipTris + (size_t)pass * (c->clipTriCap / 2); p.clipTriCap = c->clipTriCap / 2; p.pass = pass;
     p.largeList = c->dLargeList + (size_t)pass * (c->largeCap / 2); p.largeCap = c->largeCap / 2 / CHORD_LIST_SHARDS;   // per shard
+    // The record kernel bins its large records and clips its clip triangles itself: no lists, no binner launch.  CHORDVIS_BIN_IN_SETUP=0:
+    // the lists and raster_clip_and_bin_large_kernel (A/B runs; the same bins and images)
+    static const bool binInSetup = [] { const char* e = getenv("CHORDVIS_BIN_IN_SETUP"); return !e || atoi(e) != 0; }();
+    p.binInSetup = binInSetup ? 1u : 0u;
     p.counters = c->dCounters;
     p.clearTiles = clearTiles ? 1u : 0u;
     p.depthOnly = c->depthOnly ? 1u : 0u; p.depthClamp = c->depthClamp ? 1u : 0u;
@@ -3549,7 +3719,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     if (c->anyMasked) CHORD_LAUNCH(c, raster_setup_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, p);
     else              CHORD_LAUNCH(c, raster_setup_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, p);
     stamp(c, S_R_CLUSTER);
-    CHORD_LAUNCH(c, raster_clip_and_bin_large_kernel, dim3(CLIP_BLOCKS + (uint32_t)c->numCUs * 4u), dim3(256), 0, c->stream, p);
+    if (!p.binInSetup) CHORD_LAUNCH(c, raster_clip_and_bin_large_kernel, dim3(CLIP_BLOCKS + (uint32_t)c->numCUs * 4u), dim3(256), 0, c->stream, p);
     // The first pass of a main-view frame on one GPU writes EVERY tile (it is the clear): its work items are all the tiles whatever
     // their bins hold, and only their order (heaviest first) and the cut of long bins depend on this frame.  Both change slowly from
     // frame to frame, so the schedule of such a pass is kept in a buffer of its own and made again only every orderKeepFrames + 1
