@@ -1560,6 +1560,13 @@ int chordvis_debug_tile_profile(ChordCtx* c, int pass, uint64_t* hostTicks, uint
     return CHORDVIS_OK;
 }
 
+int chordvis_debug_setup_kernels(ChordCtx* c, uint32_t wide[2])
+{
+    if (!c || !wide) return fail(c, CHORDVIS_E_INVALID, "debug_setup_kernels: bad arguments");
+    wide[0] = c->setupWide[0]; wide[1] = c->setupWide[1];
+    return CHORDVIS_OK;
+}
+
 // Measurement aid: captures two consecutive frames (the history slot alternates) into a hipGraph and replays it.
 int chordvis_debug_graph_frames(ChordCtx* c, uint32_t pairs, float* msPerFrameStream, float* msPerFrameGraph)
 {

@@ -457,6 +457,7 @@ struct ChordCtx {
     float depthBiasConst = 0.0f, depthBiasSlope = 0.0f;
 
     uint64_t launchCount = 0;          // kernel launches since the context was made (CHORD_LAUNCH)
+    uint32_t setupWide[2] = {0, 0};    // per raster pass: 1 when its latest launch took raster_setup_wide_kernel (chordvis_debug_setup_kernels)
     uint64_t frameLaunchBase = 0;      // ... at the start of the current frame
     uint32_t lastFrameLaunches = 0;    // launches of the last finished frame
     // timers: mode 0 off, 1 = last frame only, 2 = accumulate until chordvis_stats

@@ -15,6 +15,8 @@
 //                         touched; every reservation of a meshlet in one memory round trip.  Records touching more than 2x2
 //                         tiles are binned by the same wave right after (wave_bin_large), and its clip triangles are clipped
 //                         and binned by it once its clusters are done (clip_entry)
+//   raster_setup_wide_kernel  light later passes only: the same set-up with one 256-thread workgroup per cluster (a vertex
+//                         per thread, a triangle per lane, reservations merged through an LDS tile table)
 //   raster_setup_blocks_kernel  dense launches (a cluster per 16 pixels or more: sub-pixel geometry) run this one first: a
 //                         cluster that fits a 16x16-pixel window is resolved in LDS and leaves as a pixel block per
 //                         touched tile (one bin entry each) instead of a record per triangle; the clusters it cannot
@@ -121,6 +123,7 @@ struct RasterParams {
     uint32_t* tileTouched;                              // direct passes that take only touched tiles (launch_raster TILE_TOUCHED): this pass's bits of FrameState::tileTouched,
                                                         // set by bin_alloc for the slot 0 of a tile, read by the tile kernel (touched_tile); NULL: no bit is set or read
     uint32_t debug;                                     // ablation switches (chordvis_set_debug), 0 in production
+    uint32_t wideMax;                                   // raster_setup_wide_kernel: a list longer than this is set up one wave per cluster (TILE_DIRECT_MAX_CLUSTERS)
 };
 // The per-phase clocks of the setup kernels (debug bit 512) and of the tile kernel (bit 16) exist only in a build with
 // -DRASTER_PROFILE=1 (python chord_amd/build.py --tag prof -DRASTER_PROFILE=1; the profile tools load that library): their
@@ -1846,6 +1849,338 @@ __global__ __launch_bounds__(256, MASKED ? SETUP_MASKED_WAVES : SETUP_MIN_WAVES)
     bool firstValid = true;
     if (launch_is_dense(p, count)) { count = *p.leftCount; cmds = p.leftCmds; firstValid = false; }   // (what the block kernel left over: another list)
     raster_setup_body<MASKED>(p, cmds, count, sVert, sClip[threadIdx.x >> 6], f0, f1, f2, firstValid);
+}
+
+// ---- the wide set-up kernel: one 256-thread workgroup per cluster (light later passes) ------------------------------------
+// A light later pass (config 3's second pass: 205 clusters) fills a fifth of the device with raster_setup_kernel's one wave per
+// cluster, and that launch lasts as long as one wave's chain: two rounds of the vertex phase, two triangles per lane, then its large
+// records and clip triangles one after another.  Here the four waves of a workgroup share one cluster: vertex i on thread i (one
+// pass over up to 256 vertices), triangle t on lane t % 32 of wave t / 32, the (record, candidate tile) pairs of the cluster's large
+// records dealt over all 256 threads, and the clip triangles CLIP_SETUP_LANES per wave.  Same arithmetic, same records, bin entries
+// and counters as raster_setup_body (only the order of slots inside lists and bins differs, as it does from run to run).
+// Reservations: one memory round trip per cluster as in the wave form.  Every primary tile of the cluster's records goes into an LDS
+// table (tile -> count; the LDS atomic's return is the thread's rank); after a barrier one thread per distinct tile issues the bin
+// reservation while thread 0 issues the list reservations, the bases come back through the same table, and only then is anything
+// stored.  A slot is allocated for (bin_alloc) by the thread that stores it, right after that barrier and before any wait.
+// launch_raster takes it for light later passes only (RasterParams::orderKept == 2); it needs binInSetup.  The host's choice rests on
+// a report of a frame long past: a list longer than RasterParams::wideMax (a camera cut, a path across the light / heavy edge) is set
+// up by the same launch one wave per cluster (raster_setup_body), so a long list costs what it costs raster_setup_kernel.
+#define WIDE_HASH 1024u                // table entries: more than the 4 x 128 primary tiles a cluster can have, so a probe always ends
+#define WIDE_EMPTY 0xFFFFFFFFu
+#ifndef SETUP_WIDE_WAVES
+#define SETUP_WIDE_WAVES 4              // waves per SIMD (workgroups per CU) the wide kernel's registers aim at; the host's grid is numCUs x this
+#endif
+template <bool MASKED>
+__global__ __launch_bounds__(256, SETUP_WIDE_WAVES) void raster_setup_wide_kernel(RasterParams p)
+{
+    // The LDS of raster_setup_kernel (the form a long list falls back to); the wide form carves its arrays out of sVert.
+    __shared__ __attribute__((aligned(16))) float sVert[6][4][LDS_VERTS];
+    __shared__ uint32_t sClipW[4][1 + CLIP_RANGES];
+    float* const sBuf = &sVert[0][0][0];
+    // 0..5: x, y, w, u, v, depth of the cluster's vertices; 6..10: its large records (LargeLds, record k = triangle k);
+    // after the cluster loop: the clip polygons, arrays 3w .. 3w + 2 for wave w (ClipLds)
+    float (*const sV)[LDS_VERTS] = reinterpret_cast<float (*)[LDS_VERTS]>(sBuf);
+    uint32_t* const sKey = reinterpret_cast<uint32_t*>(sBuf + 12u * LDS_VERTS);          // primary tile -> records binned there
+    uint32_t* const sCnt = sKey + WIDE_HASH;                                               // ... (then: the bin's base)
+    uint32_t* const sIncl = sCnt + WIDE_HASH;              // [128] large records: inclusive prefix of their candidate tile counts
+    uint32_t (*const sWave)[4] = reinterpret_cast<uint32_t (*)[4]>(sIncl + 128);   // per wave: clip triangles, compact, wide, large records
+    uint32_t* const sBase = sIncl + 128 + 16;              // [3] list bases of the cluster: clip, compact, wide
+    static_assert(12u * LDS_VERTS + 2u * WIDE_HASH + 128u + 16u + 3u <= 6u * 4u * LDS_VERTS, "the wide form's arrays fit sVert");
+    uint32_t* const sClip = sClipW[0];                     // the workgroup's ranges of the clip list (count, then base | (n - 1) << 25)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // the workgroup's first command is asked for together with the count (the list has room for the index whatever the count is)
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(min(blockIdx.x, p.cmdCap - 1u));
+    const uint32_t* __restrict__ cw0 = reinterpret_cast<const uint32_t*>(p.cmds + c0);
+    const uint32_t f0 = scalar_load(cw0), f1 = scalar_load(cw0 + 1), f2 = scalar_load(cw0 + 2);
+    uint32_t count = *p.count;
+    const ChordDrawCmd* cmds = p.cmds;
+    bool firstValid = true;
+    if (launch_is_dense(p, count)) { count = *p.leftCount; cmds = p.leftCmds; firstValid = false; }
+    count = __builtin_amdgcn_readfirstlane(count);
+    // A list longer than a light pass's (the host chose this kernel from a report of a frame long past: a camera cut, or a path that
+    // crosses the light / heavy edge) is set up one wave per cluster, as raster_setup_kernel does -- a workgroup per cluster, four or
+    // five barriers each, is the slower form once the list fills the device.  (The wave's first command is then read in the body.)
+    if (count > p.wideMax) {
+        raster_setup_body<MASKED>(p, cmds, count, sVert, sClipW[wave], 0u, 0u, 0u, false);
+        return;
+    }
+    if (blockIdx.x >= count) return;
+
+    auto header_of = [&](uint32_t objectId, uint32_t meshletId, uint32_t slot) -> SetupHeader {
+        SetupHeader h;
+        h.objectId = objectId; h.meshletId = meshletId; h.slot = slot;
+        const DMeshlet* __restrict__ mm = &p.meshlets[meshletId];
+        const uint32_t vt = scalar_load(&mm->vertexTriangleCount);
+        h.V = vt & 0xFFu; h.T = (vt >> 8) & 0xFFu;
+        h.dataOffset = scalar_load(&mm->dataOffset);
+        h.vertexBase = scalar_load(&mm->vertexBase);
+        h.matFlags = scalar_load(&p.objStatic[objectId].matFlags);
+        if (CHORD_MATFLAG_ALPHA(h.matFlags) >= CHORD_ALPHA_BLEND) h.T = 0u;      // blended: in no bucket of renderMesh
+        return h;
+    };
+    auto load_header = [&](uint32_t i) -> SetupHeader {
+        const uint32_t k = __builtin_amdgcn_readfirstlane(min(i, count - 1u));
+        const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(cmds + k);
+        return header_of(scalar_load(cw), scalar_load(cw + 1), scalar_load(cw + 2));
+    };
+    float* lX = sV[0]; float* lY = sV[1]; float* lW = sV[2]; float* lU = sV[3]; float* lV = sV[4]; float* lD = sV[5];
+    const LargeLds LL = {{sV[6], sV[7], sV[8], sV[9], sV[10]}};
+    const uint32_t listShard = blockIdx.x % CHORD_LIST_SHARDS;
+    const uint32_t t = wave * 32u + lane;                                        // this thread's triangle (lanes 0..31 of each wave)
+    SetupHeader hdr = firstValid ? header_of(f0, f1, f2) : load_header(blockIdx.x);
+    if (tid == 0u) sClip[0] = 0u;
+    for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {
+        // the next cluster's header is on its way while this one is processed
+        const SetupHeader hdrN = load_header(c + gridDim.x);
+        const uint32_t V = hdr.V, T = min(hdr.T, 128u), dataOffset = hdr.dataOffset, vertexBase = hdr.vertexBase;
+        const bool twoSided = (hdr.matFlags & CHORD_MATFLAG_TWO_SIDED) != 0u || p.depthOnly != 0u;
+        const bool masked = MASKED && CHORD_MATFLAG_ALPHA(hdr.matFlags) == CHORD_ALPHA_MASK;
+        const uint32_t* __restrict__ md = p.meshletData;
+        const bool hasTri = lane < 32u && t < T;
+        const uint32_t triWord = hasTri ? md[dataOffset + V + t] : 0u;
+        Mat4 mvp;
+        {
+            const float* __restrict__ mv = p.objFrame[hdr.objectId].mvp;
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int cc = 0; cc < 4; cc++) mvp.r[r][cc] = scalar_load(mv + r * 4 + cc);
+        }
+        // (the table of the cluster before was last read ahead of the barrier that ended its iteration)
+        for (uint32_t h = tid; h < WIDE_HASH; h += 256u) { sKey[h] = WIDE_EMPTY; sCnt[h] = 0u; }
+        // ---- vertex phase: one vertex per thread ----------------------------------------------------------------------------
+        if (tid < V) {
+            const float* __restrict__ pp = p.positions + (size_t)((md[dataOffset + tid] + vertexBase) * 3u);
+            const f4 h = mul_mv(mvp, pp[0], pp[1], pp[2], 1.0f);
+            const float aw = fabsf(h.w);
+            lX[tid] = h.x; lY[tid] = h.y; lW[tid] = h.w;
+            lU[tid] = h.x / aw * 0.5f + 0.5f;
+            lV[tid] = h.y / aw * -0.5f + 0.5f;
+            const bool fast = p.depthClamp ? in_fast_volume_xy(h) : in_fast_volume(h);
+            lD[tid] = fast ? h.z / h.w : __builtin_nanf("");
+        }
+        float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (MASKED && masked && hasTri && p.texcoords != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const size_t vi = (size_t)(md[dataOffset + ((triWord >> (8 * i)) & 0xFFu)] + vertexBase) * 2;
+                uv[2 * i] = p.texcoords[vi]; uv[2 * i + 1] = p.texcoords[vi + 1];
+            }
+        }
+        __syncthreads();
+        // ---- triangle phase: one triangle per lane, the culls and set-up of raster_setup_body ---------------------------------
+        int kind = K_NONE;
+        TriSetup ts;
+        ts.px0 = ts.py0 = ts.px1 = ts.py1 = 0;
+        float d[3] = {0.0f, 0.0f, 0.0f};
+        if (hasTri) {
+            const uint32_t i0 = triWord & 0xFFu, i1 = (triWord >> 8) & 0xFFu, i2 = (triWord >> 16) & 0xFFu;
+            const float x0 = lX[i0], y0 = lY[i0], w0 = lW[i0];
+            const float x1 = lX[i1], y1 = lY[i1], w1 = lW[i1];
+            const float x2 = lX[i2], y2 = lY[i2], w2 = lW[i2];
+            bool culled = false;
+            if (!twoSided) {
+                const float det = (x0 * (y1 * w2 - w1 * y2) - y0 * (x1 * w2 - w1 * x2)) + w0 * (x1 * y2 - y1 * x2);
+                culled = det <= 0.0f;
+            }
+            culled = culled || (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);
+            const float u0 = lU[i0], v0 = lV[i0], u1 = lU[i1], v1 = lV[i1], u2 = lU[i2], v2 = lV[i2];
+            const float maxU = fmaxf(u0, fmaxf(u1, u2)), maxV = fmaxf(v0, fmaxf(v1, v2));
+            const float minU = fminf(u0, fminf(u1, u2)), minV = fminf(v0, fminf(v1, v2));
+            culled = culled || ((minU >= 1.0f || minV >= 1.0f) || (maxU <= 0.0f || maxV <= 0.0f));
+            culled = culled || (rintf(minU * p.W) == rintf(maxU * p.W) || rintf(minV * p.H) == rintf(maxV * p.H));
+            if (!culled) {
+                d[0] = lD[i0]; d[1] = lD[i1]; d[2] = lD[i2];
+                ts.payload = p.depthOnly ? 0u : encode_triangle_instance(t, hdr.slot);
+                if (d[0] != d[0] || d[1] != d[1] || d[2] != d[2]) {          // (NaN: a vertex outside the fast volume)
+                    kind = K_CLIP;
+                } else {
+                    ts.X[0] = (int32_t)rintf((u0 * p.W) * 256.0f); ts.Y[0] = (int32_t)rintf((v0 * p.H) * 256.0f);
+                    ts.X[1] = (int32_t)rintf((u1 * p.W) * 256.0f); ts.Y[1] = (int32_t)rintf((v1 * p.H) * 256.0f);
+                    ts.X[2] = (int32_t)rintf((u2 * p.W) * 256.0f); ts.Y[2] = (int32_t)rintf((v2 * p.H) * 256.0f);
+                    if (tri_setup(ts, twoSided, p.Wi, p.Hi) && owns_rect(p.shard, ts.px0, ts.py0, ts.px1, ts.py1)) {
+                        kind = K_EMIT;
+                        if (p.biasConst != 0.0f || p.biasSlope != 0.0f) { const float o = depth_bias(ts, d, p.biasConst, p.biasSlope); d[0] += o; d[1] += o; d[2] += o; }
+                    }
+                }
+            }
+        }
+        if (ABL(p, DBG_NO_BIN)) kind = K_NONE;
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        const bool cp = kind == K_EMIT && !masked && fits_compact(ts);
+        const bool lg = kind == K_EMIT && touches_many_tiles(ts);
+        const unsigned long long cm = __ballot(kind == K_CLIP), ec = __ballot(cp), ew = __ballot(kind == K_EMIT && !cp), lm = __ballot(lg);
+        if (lane == 0u) {
+            sWave[wave][0] = (uint32_t)__popcll(cm); sWave[wave][1] = (uint32_t)__popcll(ec);
+            sWave[wave][2] = (uint32_t)__popcll(ew); sWave[wave][3] = (uint32_t)__popcll(lm);
+        }
+        // primary tiles (records of at most 2x2 tiles) into the table: the LDS atomic's return is the record's rank in the tile
+        uint32_t tileR[4], hR[4], rankR[4], has = 0u;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int32_t tx0 = ts.px0 >> TILE_SHIFT, tx1 = ts.px1 >> TILE_SHIFT, ty0 = ts.py0 >> TILE_SHIFT, ty1 = ts.py1 >> TILE_SHIFT;
+            const int32_t tx = (r & 1) ? tx1 : tx0, ty = (r & 2) ? ty1 : ty0;
+            bool in = kind == K_EMIT && !lg && !((r & 1) && tx1 == tx0) && !((r & 2) && ty1 == ty0);
+            if (in) in = owns_tile(p.shard, tx, ty);
+            tileR[r] = in ? __umul24((uint32_t)ty, p.tilesX) + (uint32_t)tx : 0u;
+            hR[r] = 0u; rankR[r] = 0u;
+            if (in) {
+                has |= 1u << r;
+                uint32_t h = tileR[r] & (WIDE_HASH - 1u);
+                for (;;) {
+                    const uint32_t o = atomicCAS(&sKey[h], WIDE_EMPTY, tileR[r]);
+                    if (o == WIDE_EMPTY || o == tileR[r]) break;
+                    h = (h + 1u) & (WIDE_HASH - 1u);
+                }
+                hR[r] = h;
+                rankR[r] = atomicAdd(&sCnt[h], 1u);
+            }
+        }
+        __syncthreads();
+        // ---- reservations: every list and bin atomic of the cluster in one round trip -------------------------------------
+        const uint32_t nClip = sWave[0][0] + sWave[1][0] + sWave[2][0] + sWave[3][0];
+        const uint32_t nLg = sWave[0][3] + sWave[1][3] + sWave[2][3] + sWave[3][3];
+        {
+            uint32_t n[4], key[4], base[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) { n[i] = sCnt[tid + 256u * i]; key[i] = sKey[tid + 256u * i]; }
+            uint32_t cbase = 0u, ebaseC = 0u, ebaseW = 0u;
+            if (tid == 0u) {
+                const uint32_t nEc = sWave[0][1] + sWave[1][1] + sWave[2][1] + sWave[3][1];
+                const uint32_t nEw = sWave[0][2] + sWave[1][2] + sWave[2][2] + sWave[3][2];
+                if (nClip) cbase = atomicAdd(&p.counters->clipTriCount[p.pass], nClip);
+                if (nEc) ebaseC = atomicAdd(&p.counters->triCountC[listShard * CHORD_SHARD_STRIDE], nEc);
+                if (nEw) ebaseW = atomicAdd(&p.counters->triCount[listShard * CHORD_SHARD_STRIDE], nEw * (masked ? 1u + CHORD_MASK_EXT_SLOTS : 1u));
+                if (nLg) atomicAdd(&p.counters->largeCount[p.pass][listShard * CHORD_SHARD_STRIDE], nLg);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) base[i] = n[i] ? atomicAdd(&p.tileCount[(size_t)key[i] * TC_STRIDE], n[i]) : 0u;
+            if (MASKED && masked) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) if (n[i]) p.tileCount[(size_t)key[i] * TC_STRIDE + TC_MASKED] = 1u;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) if (n[i]) sCnt[tid + 256u * i] = base[i];
+            if (tid == 0u) {
+                sBase[0] = cbase; sBase[1] = ebaseC; sBase[2] = ebaseW;
+                // (the clip triangles are clipped once the workgroup's clusters are done: their ranges of the clip list wait in LDS)
+                if (nClip) {
+                    const uint32_t r = sClip[0];
+                    if (r < CLIP_RANGES) { sClip[1u + r] = cbase | (nClip - 1u) << 25; sClip[0] = r + 1u; } else atomicOr(&p.counters->overflow, 2u);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- emission: records, clip list entries, bin entries -------------------------------------------------------------
+        {
+            uint32_t offClip = 0u, offC = 0u, offW = 0u;
+            for (uint32_t w = 0; w < wave; w++) { offClip += sWave[w][0]; offC += sWave[w][1]; offW += sWave[w][2]; }
+            const uint32_t wSlots = masked ? 1u + CHORD_MASK_EXT_SLOTS : 1u;
+            uint32_t slotR[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) slotR[r] = (has & (1u << r)) ? sCnt[hR[r]] + rankR[r] : 0u;
+            if (kind == K_CLIP) {
+                const uint32_t k = sBase[0] + offClip + (uint32_t)__popcll(cm & lt);
+                if (k < p.clipTriCap) { ClipTri ct; ct.objectId = hdr.objectId; ct.meshletId = hdr.meshletId; ct.slot = hdr.slot; ct.tri = t; p.clipTris[k] = ct; }
+                else atomicOr(&p.counters->overflow, 2u);
+            }
+            uint32_t gi = 0u;
+            bool ok = false;
+            if (cp) {
+                const uint32_t li = sBase[1] + offC + (uint32_t)__popcll(ec & lt);
+                if (li < p.triCapC) { gi = listShard * p.triCapC + li; write_record_c(&p.trisC[gi], ts, d); ok = true; }
+                else atomicOr(&p.counters->overflow, 1u);
+            } else if (kind == K_EMIT) {
+                const uint32_t li = sBase[2] + wSlots * (offW + (uint32_t)__popcll(ew & lt));
+                if (li + wSlots <= p.triCap) {
+                    gi = listShard * p.triCap + li; write_record(&p.tris[gi], ts, d, twoSided, masked);
+                    if (MASKED && masked) setup_emit_mask_ext(p, &p.tris[gi + 1u], triWord, uv, lW, CHORD_MATFLAG_MATERIAL(hdr.matFlags), ts.area);
+                    gi |= (MASKED && masked) ? CHORD_REC_MASKED : CHORD_REC_WIDE; ok = true;
+                } else atomicOr(&p.counters->overflow, 1u);
+            }
+            // every slot this thread drew is allocated for before its first store (bin_put's contract; a record that did not fit its
+            // list still allocates: other threads may wait for the chunk)
+#pragma unroll
+            for (int r = 0; r < 4; r++) if (has & (1u << r)) bin_alloc(p, tileR[r], slotR[r]);
+            if (ok) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) if (has & (1u << r)) bin_put(p, tileR[r], slotR[r], gi);
+            }
+            // records of more than 2x2 tiles: into LDS for the round below, with their candidate tile counts
+            if (nLg) {
+                uint32_t nt = 0u;
+                if (lg && ok) {
+                    large_put(LL, t, ts);
+                    LL.at(LG_GI, t) = gi;
+                    nt = large_tiles(LL.at(LG_BX, t), LL.at(LG_BY, t));
+                }
+                if (lane < 32u) sIncl[t] = nt;
+            }
+        }
+        if (nLg) {
+            // ---- large records: the (record, candidate tile) pairs of the cluster dealt over the workgroup, 256 per round -------
+            __syncthreads();
+            if (wave == 0u) {
+                const uint32_t a = sIncl[2u * lane], b = sIncl[2u * lane + 1u];
+                uint32_t incl = a + b;
+#pragma unroll
+                for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t nb = (uint32_t)__shfl_up((int)incl, dd, 64); if (lane >= (uint32_t)dd) incl += nb; }
+                sIncl[2u * lane] = incl - b; sIncl[2u * lane + 1u] = incl;
+            }
+            __syncthreads();
+            const uint32_t total = sIncl[127];
+            for (uint32_t j = tid; j < total; j += 256u) {
+                uint32_t k = 0u;                                                // the first record whose inclusive count exceeds j
+#pragma unroll
+                for (uint32_t st = 64u; st > 0u; st >>= 1) if (sIncl[k + st - 1u] <= j) k += st;
+                const uint32_t tt = j - (k ? sIncl[k - 1u] : 0u);
+                TriSetup lr;
+#pragma unroll
+                for (int i = 0; i < 3; i++) { lr.X[i] = (int32_t)LL.at(LG_X0 + i, k); lr.Y[i] = (int32_t)LL.at(LG_Y0 + i, k); }
+                lr.s = (int32_t)LL.at(LG_S, k);
+                const uint32_t bx = LL.at(LG_BX, k), by = LL.at(LG_BY, k), lgi = LL.at(LG_GI, k);
+                lr.px0 = (int32_t)(bx & 0xFFFFu); lr.px1 = (int32_t)(bx >> 16); lr.py0 = (int32_t)(by & 0xFFFFu); lr.py1 = (int32_t)(by >> 16);
+                const int32_t tx0 = lr.px0 >> TILE_SHIFT, ty0 = lr.py0 >> TILE_SHIFT;
+                const uint32_t tw = (uint32_t)((lr.px1 >> TILE_SHIFT) - tx0 + 1);
+                const int32_t tx = tx0 + (int32_t)(tt % tw), ty = ty0 + (int32_t)(tt / tw);
+                // pixel rectangle of this tile clipped to the triangle's bbox; conservative edge test at its corners (bin_record_tiles)
+                const int32_t rx0 = max(lr.px0, tx << TILE_SHIFT), rx1 = min(lr.px1, (tx << TILE_SHIFT) + TILE - 1);
+                const int32_t ry0 = max(lr.py0, ty << TILE_SHIFT), ry1 = min(lr.py1, (ty << TILE_SHIFT) + TILE - 1);
+                const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
+                bool hit = owns_tile(p.shard, tx, ty);
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const int64_t dxe = (int64_t)(lr.X[eb[i]] - lr.X[ea[i]]), dye = (int64_t)(lr.Y[eb[i]] - lr.Y[ea[i]]);
+                    const int64_t a = -(int64_t)lr.s * dye, b = (int64_t)lr.s * dxe;
+                    const int64_t bias = (a > 0 || (a == 0 && b > 0)) ? 0 : -1;
+                    const int64_t cx = (int64_t)(a > 0 ? rx1 : rx0) * 256 + 128, cy = (int64_t)(b > 0 ? ry1 : ry0) * 256 + 128;
+                    hit = hit && !((int64_t)lr.s * (dxe * (cy - lr.Y[ea[i]]) - dye * (cx - lr.X[ea[i]])) + bias < 0);
+                }
+                if (!hit) continue;
+                const uint32_t tile = (uint32_t)ty * p.tilesX + (uint32_t)tx;
+                bin_store(p, tile, atomicAdd(&p.tileCount[(size_t)tile * TC_STRIDE], 1u), lgi);
+                if ((lgi & 0xE0000000u) == CHORD_REC_MASKED) p.tileCount[(size_t)tile * TC_STRIDE + TC_MASKED] = 1u;
+            }
+        }
+        // the LDS of this cluster is rewritten by the next one
+        __syncthreads();
+        hdr = hdrN;
+    }
+    // ---- the clip triangles of the workgroup's clusters: CLIP_SETUP_LANES per wave at a time, in the wave's three arrays of sV --
+    __syncthreads();
+    if (const uint32_t ranges = sClip[0]) {
+        float* a = sV[3u * wave]; float* b = sV[3u * wave + 1u]; float* cc = sV[3u * wave + 2u];
+        const ClipLds<CLIP_SETUP_LANES> L = {reinterpret_cast<float4*>(a), b, b + 2u * CLIP_MAXV * CLIP_SETUP_LANES,
+                                             reinterpret_cast<int32_t*>(cc), reinterpret_cast<int32_t*>(cc) + CLIP_MAXV * CLIP_SETUP_LANES,
+                                             cc + 2u * CLIP_MAXV * CLIP_SETUP_LANES, lane};
+        for (uint32_t i = 0; i < ranges; i++) {
+            const uint32_t w = sClip[1u + i], base = w & 0x1FFFFFFu, n = (w >> 25) + 1u;
+            for (uint32_t k0 = 0; k0 < n; k0 += 4u * CLIP_SETUP_LANES) {
+                const uint32_t k = k0 + wave * CLIP_SETUP_LANES + lane;
+                if (lane < CLIP_SETUP_LANES && k < n && base + k < p.clipTriCap) clip_entry<MASKED>(p, L, p.clipTris[base + k], listShard);
+            }
+        }
+    }
 }
 
 // HOT: the variant that draws bin slots ahead on hot tiles (above).  It costs the plain kernel's loop 3 % (registers: the loop
@@ -3716,8 +4051,23 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
         if (hot) CHORD_LAUNCH(c, raster_setup_blocks_kernel<true>, dim3(bb), dim3(256), 0, c->stream, p);
         else     CHORD_LAUNCH(c, raster_setup_blocks_kernel<false>, dim3(bb), dim3(256), 0, c->stream, p);
     }
-    if (c->anyMasked) CHORD_LAUNCH(c, raster_setup_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, p);
-    else              CHORD_LAUNCH(c, raster_setup_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, p);
+    // A light later pass (direct: the latest report says at most TILE_DIRECT_MAX_CLUSTERS clusters) is set up by the wide kernel, a
+    // workgroup per cluster: its few clusters would leave most SIMDs idle under one wave each.  One wave of workgroups of the device.
+    // The report may be stale (the host runs frames ahead): a list that turns out longer than TILE_DIRECT_MAX_CLUSTERS is set up by
+    // the same launch one wave per cluster, the form of raster_setup_kernel (RasterParams::wideMax).  First passes, heavy later
+    // passes, dense and sharded launches keep raster_setup_kernel.  CHORDVIS_SETUP_WIDE=0: raster_setup_kernel everywhere (A/B runs;
+    // the same records, bins and images); a number above 1: the wide form up to that many clusters instead (tests: the edge between
+    // the two forms at a pass's own count).
+    static const int setupWide = [] { const char* e = getenv("CHORDVIS_SETUP_WIDE"); return e ? atoi(e) : 1; }();
+    p.wideMax = setupWide > 1 ? (uint32_t)setupWide : TILE_DIRECT_MAX_CLUSTERS;
+    c->setupWide[pass] = 0u;
+    if (setupWide != 0 && p.orderKept == 2u && p.binInSetup && !blocksWorthLaunching && !sh) {
+        const uint32_t wideBlocks = std::max(1u, std::min(std::max(in.capacity, 1u), (uint32_t)c->numCUs * SETUP_WIDE_WAVES));
+        if (c->anyMasked) CHORD_LAUNCH(c, raster_setup_wide_kernel<true>, dim3(wideBlocks), dim3(256), 0, c->stream, p);
+        else              CHORD_LAUNCH(c, raster_setup_wide_kernel<false>, dim3(wideBlocks), dim3(256), 0, c->stream, p);
+        c->setupWide[pass] = 1u;
+    } else if (c->anyMasked) CHORD_LAUNCH(c, raster_setup_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, p);
+    else                     CHORD_LAUNCH(c, raster_setup_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, p);
     stamp(c, S_R_CLUSTER);
     if (!p.binInSetup) CHORD_LAUNCH(c, raster_clip_and_bin_large_kernel, dim3(CLIP_BLOCKS + (uint32_t)c->numCUs * 4u), dim3(256), 0, c->stream, p);
     // The first pass of a main-view frame on one GPU writes EVERY tile (it is the clear): its work items are all the tiles whatever

@@ -233,6 +233,7 @@ def _load():
         "chordvis_stats": (i32, [vp, P(Stats)]),
         "chordvis_set_debug": (i32, [vp, u32]),
         "chordvis_debug_tile_profile": (i32, [vp, i32, vp, vp, u32]),
+        "chordvis_debug_setup_kernels": (i32, [vp, P(u32)]),
         "chordvis_debug_setup_profile": (i32, [vp, i32, vp, P(u32)]),
         "chordvis_debug_read": (i32, [vp, i32, C.c_uint64, C.c_uint64, vp]),
         "chordvis_debug_slab_nonzero": (i32, [vp, P(C.c_uint64)]),

@@ -581,6 +581,9 @@ int chordvis_debug_graph_frames(ChordCtx* ctx, uint32_t pairs, float* msPerFrame
  * their accumulators cost the product kernels scalar registers they do not have); the product library leaves the ticks zero. */
 int chordvis_debug_setup_profile(ChordCtx* ctx, int pass, uint64_t hostTicks[5], uint32_t* waves);
 int chordvis_debug_tile_profile(ChordCtx* ctx, int pass, uint64_t* hostTicks, uint32_t* hostCounts, uint32_t capacity);
+/* Which set-up kernel the latest launch of each raster pass took: wide[pass] = 1 for raster_setup_wide_kernel (a light later pass),
+ * 0 for raster_setup_kernel. */
+int chordvis_debug_setup_kernels(ChordCtx* ctx, uint32_t wide[2]);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
