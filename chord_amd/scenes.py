@@ -829,3 +829,63 @@ def config5_subpixel(width=3840, height=2160, prims=1024, patches_per_prim=1024,
         for i in range(instances):
             sb.add_object(prim, translate(0.013 * i, 0.007 * i, -0.05 * i))
     return sb.build(), cam
+
+
+def stacked_layers(variant="large", width=320, height=192, layers=None, per_object=16):
+    """Layers of one two-sided meshlet each (81 vertices / 128 triangles), stacked so that one binner of the set-up kernels
+    fills a few tiles' bins far past their fixed part; groups of per_object layers are objects of their own (so that
+    update_objects can take some of them out of view).
+      * "large": camera-facing layers at distinct view depths 4 .. 20 m, camera at the origin looking down -z.  Every triangle
+        of a layer is a sliver of a wedge through the screen centre (rows of vertices alternate between two opposite rays
+        1 200 px out), so its bbox spans the whole screen -- a large record -- and every triangle touches the centre tile
+        (2, 1): that bin holds 128 entries per layer.  Nothing crosses the near plane or the guard band.  An opaque backdrop
+        at 40 m covers the screen behind them (its cells are small: not large records), so a history HZB occludes anything
+        moved further down the view.
+      * "near": horizontal layers 2 mm apart, 0 .. 0.64 m under a camera looking down and forward; rows of vertices alternate
+        between 3 m in front of the camera and 2 m behind it, so every triangle straddles the near plane and nearly all the
+        bin entries of the frame come from clipped pieces."""
+    sb = SceneBuilder("stacked_layers_" + variant)
+    mat = sb.add_material(1)
+    i = np.arange(9, dtype=np.float64)[None, :]
+    j = np.arange(9, dtype=np.float64)[:, None]
+    if variant == "large":
+        layers = 192 if layers is None else layers
+        cam = Camera((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), width, height)
+        th, aspect = math.tan(0.5 * cam.fovy), width / height
+        R, delta = 1200.0, 4.0 / 1200.0
+        golden = math.pi * (3.0 - math.sqrt(5.0))
+
+        def world(sx, sy, zv):
+            return np.stack([(sx / width * 2.0 - 1.0) * zv * th * aspect, -(sy / height * 2.0 - 1.0) * zv * th,
+                             np.broadcast_to(-zv, np.shape(sx))], axis=-1)
+
+        def layer(l):
+            ang = (l * golden) % math.pi + i * delta + j * math.pi
+            rad = R * (1.0 + 0.03 * j)
+            zv = 4.0 + 16.0 * l / layers
+            return world(0.5 * width + rad * np.cos(ang), 0.5 * height + rad * np.sin(ang), zv)
+    elif variant == "near":
+        layers = 320 if layers is None else layers
+        cam = Camera((0.3, 0.25, 0.2), (0.1, -0.6, -1.0), width, height)
+        cx, cz = cam.position[0], cam.position[2]
+
+        def layer(l):
+            x = np.broadcast_to(cx - 0.6 + 1.2 * i / 8.0, (9, 9))
+            z = np.broadcast_to(cz + np.where(j % 2 == 0, -3.0, 2.0) - 0.05 * j, (9, 9))
+            return np.stack([x, np.full((9, 9), -0.002 * l), z], axis=-1)
+    else:
+        raise ValueError(variant)
+    assert layers % per_object == 0 and per_object % 4 == 0
+    for o in range(layers // per_object):
+        pos = np.stack([layer(o * per_object + k) for k in range(per_object)]).astype(np.float32).reshape(per_object, 81, 3)
+        pb = PrimitiveBuilder()
+        ids = pb._add_meshlets(pos, 0)
+        pb._add_groups(ids.reshape(-1, 4), 0.0, -1.0, 0.0, FLT_MAX)     # un-parented LOD0 groups of 4
+        sb.add_object(sb.add_primitive(pb), material=mat)
+    if variant == "large":
+        pb = PrimitiveBuilder()
+        zb = 40.0
+        x0, y0 = -1.1 * zb * th * aspect, -1.1 * zb * th
+        pb.add_surface(plane_surface((x0, y0, -zb), (-2.0 * x0, 0.0, 0.0), (0.0, -2.0 * y0, 0.0)), 1, 1)
+        sb.add_object(sb.add_primitive(pb), material=mat)
+    return sb.build(), cam

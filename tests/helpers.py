@@ -143,3 +143,71 @@ def close_view_chain(scene, flags=ALL_FLAGS):
     L.fill_objects(scene, cam, occ)
     view, iv = L.make_views(cam, view_o)
     return chain, view, iv
+
+
+# ---- sharded frames on one device: every rank a context of its own, the all-gathers replaced by device-to-device copies ----
+
+def sharded_contexts(scene, view, iv, w, h, flags, ranks, tile_map="default", limits=None, debug_of_rank=None):
+    """One context per rank of a `ranks`-rank frame on device 0, each with the scene, its rank and the view.  tile_map
+    "checker" makes every tile border a rank border (chordvis_set_tile_owners); any other value keeps the library's compact
+    regions.  debug_of_rank(rank) -> chordvis_set_debug flags (0 / None: none)."""
+    from chord_amd.renderer import VisibilityRenderer
+    from chord_amd.sharding import TileLayout
+    lay = TileLayout(w, h, ranks)
+    ctxs = []
+    for rk in range(ranks):
+        r = VisibilityRenderer(0)
+        if limits:
+            r.set_limits(**limits)
+        r.upload_scene(scene)
+        r.set_shard(ranks, rk)
+        r.allocate_gbuffer(w, h)
+        assert np.array_equal(r.tile_owners(), lay.owners)
+        if tile_map == "checker":
+            r.set_tile_owners([(t % lay.tiles_x + t // lay.tiles_x) % ranks for t in range(lay.tiles)])
+        r.set_view(view, iv, flags)
+        dbg = debug_of_rank(rk) if debug_of_rank else 0
+        if dbg:
+            r.set_debug(dbg)
+        ctxs.append(r)
+    return ctxs
+
+
+def sharded_gather(ctxs, ptrs, chunk_bytes):
+    """The all-gather of rank chunks: rank src's chunk src of each buffer is copied into every other rank's buffer."""
+    import ctypes as C
+    from chord_amd import lib as L
+    hip = L._preload_hip_runtime()
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    for r in ctxs:
+        r.sync()
+    ranks = len(ctxs)
+    for dst in range(ranks):
+        for src in range(ranks):
+            if src != dst:
+                assert hip.hipMemcpy(ptrs[dst] + src * chunk_bytes, ptrs[src] + src * chunk_bytes, chunk_bytes, 3) == 0
+    # a device-to-device hipMemcpy is ordered on the null stream only; the contexts run on non-blocking streams
+    assert hip.hipDeviceSynchronize() == 0
+
+
+def sharded_frame(ctxs, sharded_cull=True):
+    """One frame on every rank: [phase cull, gather of the rank masks,] phase a, gather of the mid-frame HZB texels, phase b,
+    gathers of the end-of-frame HZB texels and of the visibility words, phase c.  Without sharded_cull the frame starts at
+    phase a (the replicated group cull)."""
+    if sharded_cull:
+        for r in ctxs:
+            r.frame_phase_cull()
+        cx = [r.cull_exchange() for r in ctxs]
+        assert all(c[0] and c[1] == cx[0][1] for c in cx)
+        sharded_gather(ctxs, [c[0] for c in cx], cx[0][1])
+    for r in ctxs:
+        r.frame_phase_a()
+    ex = [r.hzb_exchange() for r in ctxs]
+    sharded_gather(ctxs, [e[0] for e in ex], ex[0][2] * 2)
+    for r in ctxs:
+        r.frame_phase_b()
+    fin = [r.hzb_final_exchange() for r in ctxs]
+    sharded_gather(ctxs, [f[0] for f in fin], fin[0][1])
+    sharded_gather(ctxs, [r.visibility_ptr() for r in ctxs], ctxs[0].visibility_chunk_words() * 8)
+    for r in ctxs:
+        r.frame_phase_c()

@@ -297,3 +297,129 @@ def test_cascade_setup_matches_the_float32_fixture_bit_for_bit():
                                    ("orthoDepthConvertToView", got[k]["orthoDepthConvertToView"], want["orthoDepthConvertToView"], again[k]["ortho"])):
                 assert np.array_equal(u(a), np.asarray(b, np.uint32)), "%s cascade %d: %s differs from the fixture" % (case["name"], k, label)
                 assert np.array_equal(u(c), np.asarray(b, np.uint32)), "%s cascade %d: the restatement no longer reproduces the fixture (%s)" % (case["name"], k, label)
+
+
+# ---- depth-only views through the set-up kernels' own binners: large records and clip triangles -------------------------
+
+def _coarse_ground_scene(width=320, height=200):
+    """A 16 km ground of 2 km cells (its vertices far past a cascade's guard band), a 60 m x 1 km wall of 7.5 m x 125 m cells just
+    in front of the camera (past the cascade box's depth range at both ends; seen by the light at an angle, its triangles cross
+    the whole shadow map) and a 60 m x 3 m ledge of 7.5 m wide cells near the camera (inside the depth range: large records
+    also when the depth is not clamped)."""
+    sb = scenes.SceneBuilder("coarse_ground_pillar")
+    mat = sb.add_material(1)
+    for surf in (scenes.plane_surface((-8000.0, 0.0, 8000.0), (16000.0, 0.0, 0.0), (0.0, 0.0, -16000.0)),
+                 scenes.plane_surface((-30.0, -500.0, -1.5), (60.0, 0.0, 0.0), (0.0, 1000.0, 0.0)),
+                 scenes.plane_surface((-30.0, 0.3, -0.5), (60.0, 0.0, 0.0), (0.0, 0.0, -3.0))):
+        pb = scenes.PrimitiveBuilder()
+        pb.add_surface(surf, 1, 1)
+        sb.add_object(sb.add_primitive(pb), material=mat)
+    scene = sb.build()
+    cam = scenes.Camera((0.0, 1.7, 0.0), (0.1, -0.3, -1.0), width, height)
+    L.fill_objects(scene, cam)
+    cfg, view, iv, views = _cascades(cam, cascadeCount=3, realtimeCascadeCount=2, cascadeDim=256, cascadeEndDistance=14.0,
+                                     farCascadeEndDistance=40.0)
+    return scene, cam, view, iv, views
+
+
+DEPTH_MODES = [("clamped", True, (0.0, 0.0), 0), ("clamped_biased", True, (-48.0, -1.25), 0),
+               ("unclamped", False, (0.0, 0.0), 0), ("clamped_pixel_blocks", True, (0.0, 0.0), 65536)]
+DEPTH_FLAGS = R.FLAG_FRUSTUM_CULL | R.FLAG_CONE_CULL
+
+
+def test_coarse_ground_cascade_reaches_past_the_guard_band_and_the_depth_range():
+    scene, cam, view, iv, views = _coarse_ground_scene()
+    vp = _m(views[0], "translatedWorldToClip")
+    campos = np.frombuffer(iv["cameraWorldPos"][0].tobytes(), dtype=np.float64)[:3]
+    p = scene.positions.astype(np.float64)
+    ground = p[: 81] - campos
+    clip = vp @ np.concatenate([ground, np.ones((81, 1))], axis=1).T
+    texels = np.abs(clip[:2] / clip[3]) * 128.0
+    assert texels.max() > 1024 * 128                                     # beyond the guard band, in texels of a 256 map
+    wall = vp @ np.concatenate([p[81:162] - campos, np.ones((81, 1))], axis=1).T
+    z = wall[2] / wall[3]
+    assert z.min() < 0.0 and z.max() > 1.0                               # past the box's depth range at both ends
+    tx = np.clip((wall[0] / wall[3] * 0.5 + 0.5) * 256.0, 0.0, 256.0)[scenes._TI]
+    ty = np.clip((0.5 - wall[1] / wall[3] * 0.5) * 256.0, 0.0, 256.0)[scenes._TI]
+    assert ((np.ptp(tx, axis=1) > 128) | (np.ptp(ty, axis=1) > 128)).sum() >= 8          # triangles over more than 2 x 2 tiles
+    ledge = vp @ np.concatenate([p[162:243] - campos, np.ones((81, 1))], axis=1).T
+    lz = (ledge[2] / ledge[3])[scenes._TI]
+    lx = np.clip((ledge[0] / ledge[3] * 0.5 + 0.5) * 256.0, 0.0, 256.0)[scenes._TI]
+    ly = np.clip((0.5 - ledge[1] / ledge[3] * 0.5) * 256.0, 0.0, 256.0)[scenes._TI]
+    inside = (lz.min(axis=1) > 0.0) & (lz.max(axis=1) < 1.0)
+    assert (inside & ((np.ptp(lx, axis=1) > 128) | (np.ptp(ly, axis=1) > 128))).any()   # large records that no plane clips
+    cmds = orc.instance_culling(scene, view, views[0:1], DEPTH_FLAGS)
+    for _, clamp, bias, _ in DEPTH_MODES[:3]:
+        _, st = orc.raster_depth(scene, views[0:1], cmds, 256, 256, clamp, bias[0], bias[1])
+        assert st.trianglesClipped > 0, (clamp, bias)
+
+
+def _depth_child_main(out_path):
+    from chord_amd.renderer import VisibilityRenderer
+    scene, cam, view, iv, views = _coarse_ground_scene()
+    r = VisibilityRenderer(0)
+    r.upload_scene(scene)
+    r.allocate_gbuffer(cam.width, cam.height)
+    r.set_view(view, iv, DEPTH_FLAGS)
+    r.allocate_depth_views(256, len(views))
+    r.set_instance_views(views)
+    res = {}
+    for name, clamp, bias, debug in DEPTH_MODES:
+        r.set_debug(debug)
+        lst = r.instance_culling_view(0)
+        res["cmds_" + name] = r.read_cmds(lst)
+        target = r.render_mesh_depth(0, lst, clamp, bias[0], bias[1])
+        res["depth_" + name] = r.read_depth(target)
+        st = r.depth_view_stats()
+        res["stats_" + name] = np.array([st["overflow"], sum(st["largeRecords"]), sum(st["clipTriangles"]), st["binEntries"]], np.int64)
+    r.close()
+    np.savez(out_path, **res)
+
+
+@pytest.fixture(scope="module")
+def depth_runs(gpu, tmp_path_factory):
+    """{CHORDVIS_BIN_IN_SETUP value: npz of the four depth passes}, one child interpreter per value."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for value in ("1", "0"):
+        path = os.path.join(str(tmp_path_factory.mktemp("depth_bin_" + value)), "depth.npz")
+        env = dict(os.environ)
+        env["CHORDVIS_BIN_IN_SETUP"] = value
+        code = "import sys; sys.path[:0] = [%r, %r]; import test_depth_views as T; T._depth_child_main(%r)" % (
+            root, os.path.join(root, "tests"), path)
+        p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, "child (CHORDVIS_BIN_IN_SETUP=%s) failed:\n%s\n%s" % (value, p.stdout[-2000:], p.stderr[-4000:])
+        out[value] = np.load(path)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,clamp,bias,debug", DEPTH_MODES, ids=[m[0] for m in DEPTH_MODES])
+def test_depth_views_bin_large_and_clipped_triangles_in_setup(depth_runs, name, clamp, bias, debug):
+    """A cascade (dim 256) of the coarse ground: its triangles cross the guard band (clamped: the clipper's planes 2..5 and
+    in_fast_volume_xy) or, unclamped, the near and far planes as well, and the wall's and the ledge's cross the whole map (large records).
+    Each depth image is bit-exact against orc.raster_depth with the same clamp and bias, and CHORDVIS_BIN_IN_SETUP=0 (the
+    lists and the binner launch) gives the same images and counts."""
+    scene, cam, view, iv, views = _coarse_ground_scene()
+    want_cmds = orc.instance_culling(scene, view, views[0:1], DEPTH_FLAGS)
+    want, st = orc.raster_depth(scene, views[0:1], want_cmds, 256, 256, clamp, bias[0], bias[1])
+    assert st.trianglesClipped > 0
+    for value, g in depth_runs.items():
+        what = "%s, CHORDVIS_BIN_IN_SETUP=%s" % (name, value)
+        assert np.array_equal(H.sort_cmds(g["cmds_" + name]), H.sort_cmds(want_cmds)), what
+        got = g["depth_" + name]
+        bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
+        assert len(bad) == 0, "%s: %d texels differ, first %d: %r vs %r" % (what, len(bad), bad[0], got[bad[0]], want[bad[0]])
+        overflow, large, clipped, entries = g["stats_" + name].tolist()
+        assert overflow == 0 and large > 0 and clipped > 0, (what, overflow, large, clipped)
+    assert np.array_equal(depth_runs["1"]["stats_" + name], depth_runs["0"]["stats_" + name]), name
+    if not clamp:
+        # unclamped, the near and far planes clip as well: more clip triangles than the clamped pass of the same view
+        cmds_c = orc.instance_culling(scene, view, views[0:1], DEPTH_FLAGS)
+        _, st_c = orc.raster_depth(scene, views[0:1], cmds_c, 256, 256, True, bias[0], bias[1])
+        assert st.trianglesClipped > st_c.trianglesClipped, (st.trianglesClipped, st_c.trianglesClipped)
+        for value, g in depth_runs.items():
+            assert g["stats_unclamped"][2] > g["stats_clamped"][2], (value, g["stats_unclamped"].tolist(), g["stats_clamped"].tolist())

@@ -540,11 +540,7 @@ def test_sharded_frames_reassemble_to_the_single_gpu_image(gpu, name, builder, r
     """The multi-GPU path on one device: every rank's context runs its phases in turn, the three
     all-gathers (mid-frame HZB texels; end-of-frame HZB texels; visibility words) are replaced by device-to-device
     copies of the rank chunks, and each rank must end up with exactly the single-GPU visibility buffer and HZB."""
-    import ctypes as C
-    import torch
-    from chord_amd import lib as L
-    from chord_amd.renderer import VisibilityRenderer
-    from chord_amd.sharding import TileLayout
+    import torch  # noqa: F401
     scene, cam, view, iv = H.setup_scene(builder)
     w, h, flags = cam.width, cam.height, H.ALL_FLAGS
     case_index = [c[0] for c in SHARDED].index(name)
@@ -552,35 +548,9 @@ def test_sharded_frames_reassemble_to_the_single_gpu_image(gpu, name, builder, r
     # reference below): beyond the default 16 Ki + 240 Ki entries per tile, so it runs under the documented raised limit
     limits = dict(bin_max_chunks_per_tile=2048) if name.startswith("hotspot") else None
     ref = _renderer(gpu, scene, view, iv, w, h, flags, limits=limits)
-    lay = TileLayout(w, h, ranks)
-    ctxs = []
-    for rk in range(ranks):
-        r = VisibilityRenderer(0)
-        if limits:
-            r.set_limits(**limits)
-        r.upload_scene(scene)
-        r.set_shard(ranks, rk)
-        r.allocate_gbuffer(w, h)
-        assert np.array_equal(r.tile_owners(), lay.owners)
-        if tile_map == "checker":
-            r.set_tile_owners([(t % lay.tiles_x + t // lay.tiles_x) % ranks for t in range(lay.tiles)])
-        r.set_view(view, iv, flags)
-        if name.endswith("_blocks"):
-            # (the hotspot case: odd ranks also draw bin slots ahead on hot tiles, the sharded form of the hot-tile variant)
-            r.set_debug(FORCE_BLOCKS | (FORCE_HOT if name.startswith("hotspot") and rk % 2 else 0))
-        ctxs.append(r)
-    hip = L._preload_hip_runtime()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def gather(ptrs, chunk_bytes):
-        for r in ctxs:
-            r.sync()
-        for dst in range(ranks):
-            for src in range(ranks):
-                if src != dst:
-                    assert hip.hipMemcpy(ptrs[dst] + src * chunk_bytes, ptrs[src] + src * chunk_bytes, chunk_bytes, 3) == 0
-        # a device-to-device hipMemcpy is ordered on the null stream only; the contexts run on non-blocking streams
-        assert hip.hipDeviceSynchronize() == 0
+    # (the hotspot case: odd ranks also draw bin slots ahead on hot tiles, the sharded form of the hot-tile variant)
+    blocks = (lambda rk: FORCE_BLOCKS | (FORCE_HOT if name.startswith("hotspot") and rk % 2 else 0)) if name.endswith("_blocks") else None
+    ctxs = H.sharded_contexts(scene, view, iv, w, h, flags, ranks, tile_map, limits, blocks)
 
     # the small cases are also held against the ORACLE directly (not only against the single-GPU HIP frame: a defect common
     # to both HIP paths would pass the comparison between them)
@@ -598,23 +568,7 @@ def test_sharded_frames_reassemble_to_the_single_gpu_image(gpu, name, builder, r
             want = o["vis"]                              # the ranks below are compared with the oracle's image
         # the sharded group cull (every frame but frame 0 of every other case, which starts at phase a: the replicated cull): each
         # rank tests its share of the group instances, the rank-mask words are all-gathered, phase a goes on from them
-        if frame > 0 or case_index % 2 == 0:
-            for r in ctxs:
-                r.frame_phase_cull()
-            cx = [r.cull_exchange() for r in ctxs]
-            assert all(c[0] and c[1] == cx[0][1] for c in cx)
-            gather([c[0] for c in cx], cx[0][1])
-        for r in ctxs:
-            r.frame_phase_a()
-        ex = [r.hzb_exchange() for r in ctxs]
-        gather([e[0] for e in ex], ex[0][2] * 2)
-        for r in ctxs:
-            r.frame_phase_b()
-        fin = [r.hzb_final_exchange() for r in ctxs]
-        gather([f[0] for f in fin], fin[0][1])
-        gather([r.visibility_ptr() for r in ctxs], ctxs[0].visibility_chunk_words() * 8)
-        for r in ctxs:
-            r.frame_phase_c()
+        H.sharded_frame(ctxs, sharded_cull=(frame > 0 or case_index % 2 == 0))
         for rk, r in enumerate(ctxs):
             H.assert_vis_equal(r.read_visibility(), want, w, h, "frame %d rank %d" % (frame, rk))
             mn, mx, rng = r.read_hzb(r.history_hzb())
