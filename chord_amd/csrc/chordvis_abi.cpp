@@ -408,10 +408,11 @@ int chordvis_destroy(ChordCtx* c)
     if (c->sharedScene) {       // a depth-view child: the scene buffers are the parent's
         c->dPrims = nullptr; c->dGroups = nullptr; c->dMeshlets = nullptr; c->dGroupIndices = nullptr; c->dMeshletData = nullptr;
         c->dPositions = nullptr; c->dObjStatic = nullptr; c->dGroupRefs = nullptr; c->dMaterials = nullptr; c->dTexAlpha = nullptr;
-        c->dTexcoords = nullptr; c->dBvhNodes = nullptr; c->dMeshletLod = nullptr;
+        c->dTexcoords = nullptr; c->dBvhNodes = nullptr; c->dMeshletLod = nullptr; c->dNormals = nullptr; c->dTangents = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
+    dfree(c->dNormals); dfree(c->dTangents);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -742,6 +743,22 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         }
     }
     c->anyMasked = anyMasked;
+    // normals (float3) and tangents (float4) per vertex: read by chordvis_resolve_surface alone.  Assets without a stream
+    // contribute zeros; a scene where no asset has one allocates nothing for it.
+    std::vector<float> nrm, tng;
+    for (uint32_t a = 0; a < s->assetCount; a++) {
+        const ChordAssetDesc& as = s->assets[a];
+        if ((as.normals && as.normalCount && as.normalCount != as.vertexCount) || (as.tangents && as.tangentCount && as.tangentCount != as.vertexCount))
+            return fail(c, CHORDVIS_E_INVALID, "upload_scene: normalCount / tangentCount must equal vertexCount (or be 0: no such stream)");
+        if (as.normals && as.normalCount) {
+            if (nrm.empty()) nrm.assign((size_t)nV * 3, 0.0f);
+            std::memcpy(nrm.data() + (size_t)vB[a] * 3, as.normals, sizeof(float) * 3 * as.vertexCount);
+        }
+        if (as.tangents && as.tangentCount) {
+            if (tng.empty()) tng.assign((size_t)nV * 4, 0.0f);
+            std::memcpy(tng.data() + (size_t)vB[a] * 4, as.tangents, sizeof(float) * 4 * as.vertexCount);
+        }
+    }
 
     int rc;
 #define UP(dst, vec)                                                                                          \
@@ -754,6 +771,8 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     c->bvhComplete = bvhComplete;
     if (!alpha.empty()) { UP(c->dTexAlpha, alpha) } else dfree(c->dTexAlpha);
     if (!uvs.empty()) { UP(c->dTexcoords, uvs) } else dfree(c->dTexcoords);
+    if (!nrm.empty()) { UP(c->dNormals, nrm) } else dfree(c->dNormals);
+    if (!tng.empty()) { UP(c->dTangents, tng) } else dfree(c->dTangents);
 #undef UP
     c->instTriangles = instTriangles;
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }       // (it aliased the old scene buffers)
@@ -1412,22 +1431,68 @@ int chordvis_visibility_mark(ChordCtx* c, ChordCountAndCmd drawed, ChordTileMark
 
 // ---------------------------------------------------------------- per-pixel attributes of the visible triangle --
 
-int chordvis_resolve_attributes(ChordCtx* c, ChordCountAndCmd drawed, const ChordResolveDesc* desc, const ChordResolveTargets* t)
+// The preconditions chordvis_resolve_attributes and chordvis_resolve_surface share, in this order: a scene and gbuffer, a frame
+// since, no update_objects / set_view after it, a command list, a target, debugMode within range.  `fn` names the entry point in
+// the messages.
+static int resolve_checks(ChordCtx* c, const char* fn, ChordCountAndCmd drawed, bool anyTarget, bool wantDebug, const ChordResolveDesc& d)
 {
-    if (!c || !c->dVis || !c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no scene / gbuffer");
-    if (!c->resolveFrame) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no frame rendered yet");
-    if (c->resolveStale)
-        return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: chordvis_update_objects / chordvis_set_view came after the frame (the image's matrices are gone)");
-    if (!drawed.count || !drawed.cmds) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: null command list");
-    if (!t || !(t->barycentrics || t->baryDdx || t->baryDdy || t->uv || t->uvGrad || t->positionRS || t->motionVector || t->debugRGBA8))
-        return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: no target");
-    const ChordResolveDesc d = desc ? *desc : ChordResolveDesc{};
-    if (t->debugRGBA8 && d.debugMode > CHORD_NANITE_DEBUG_BARYCENTRICS) return fail(c, CHORDVIS_E_INVALID, "resolve_attributes: debugMode beyond 4");
+    char buf[224];
+    auto refuse = [&](const char* why) { std::snprintf(buf, sizeof(buf), "%s: %s", fn, why); return fail(c, CHORDVIS_E_INVALID, buf); };
+    if (!c || !c->dVis || !c->sceneLoaded) return refuse("no scene / gbuffer");
+    if (!c->resolveFrame) return refuse("no frame rendered yet");
+    if (c->resolveStale) return refuse("chordvis_update_objects / chordvis_set_view came after the frame (the image's matrices are gone)");
+    if (!drawed.count || !drawed.cmds) return refuse("null command list");
+    if (!anyTarget) return refuse("no target");
+    if (wantDebug && d.debugMode > CHORD_NANITE_DEBUG_BARYCENTRICS) return refuse("debugMode beyond 4");
+    return CHORDVIS_OK;
+}
+
+// What both do before their launch: the full list's fill when the list is the frame's, and the wait for a pipelined frame's
+// gather.  *vis = the image chordvis_visibility_mark reads (the resolved one of a sharded context).
+static int resolve_source(ChordCtx* c, ChordCountAndCmd drawed, const unsigned long long** vis)
+{
     if (drawed.cmds == c->lists[0].cmds) { launch_full_list(c); CHORD_HIP(c, hipGetLastError()); }
-    const unsigned long long* vis = (const unsigned long long*)(c->shard.ranks > 1 ? c->dVisResolved : c->dVis);
+    *vis = (const unsigned long long*)(c->shard.ranks > 1 ? c->dVisResolved : c->dVis);
     // (pipelined group frames: the image is gathered and resolved beside the context's stream)
     if (c->visReadyEvent[0]) CHORD_HIP(c, hipStreamWaitEvent(c->stream, c->visReadyEvent[0], 0));
-    chord::launch_resolve_attributes(c, vis, drawed.cmds, drawed.count, d, *t);
+    return CHORDVIS_OK;
+}
+
+static bool any_resolve_target(const ChordResolveTargets& t)
+{
+    return t.barycentrics || t.baryDdx || t.baryDdy || t.uv || t.uvGrad || t.positionRS || t.motionVector || t.debugRGBA8;
+}
+
+int chordvis_resolve_attributes(ChordCtx* c, ChordCountAndCmd drawed, const ChordResolveDesc* desc, const ChordResolveTargets* t)
+{
+    const ChordResolveTargets tt = t ? *t : ChordResolveTargets{};
+    const ChordResolveDesc d = desc ? *desc : ChordResolveDesc{};
+    int rc = resolve_checks(c, "resolve_attributes", drawed, any_resolve_target(tt), tt.debugRGBA8 != nullptr, d);
+    const unsigned long long* vis = nullptr;
+    if (rc || (rc = resolve_source(c, drawed, &vis))) return rc;
+    chord::launch_resolve_attributes(c, vis, drawed.cmds, drawed.count, d, tt);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+// chordvis_resolve_attributes' preconditions and refusals, then those of the surface streams the targets need
+int chordvis_resolve_surface(ChordCtx* c, ChordCountAndCmd drawed, const ChordResolveDesc* desc, const ChordResolveTargets* t,
+                             const ChordSurfaceTargets* s)
+{
+    const ChordResolveTargets tt = t ? *t : ChordResolveTargets{};
+    const ChordSurfaceTargets ss = s ? *s : ChordSurfaceTargets{};
+    const ChordResolveDesc d = desc ? *desc : ChordResolveDesc{};
+    const bool anySurface = ss.vertexNormal || ss.tangent || ss.bitangent;
+    int rc = resolve_checks(c, "resolve_surface", drawed, any_resolve_target(tt) || anySurface, tt.debugRGBA8 != nullptr, d);
+    if (rc) return rc;
+    if (ss.pad) return fail(c, CHORDVIS_E_INVALID, "resolve_surface: ChordSurfaceTargets::pad must be NULL");
+    if ((ss.tangent || ss.bitangent) && !c->dTangents)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_surface: the scene was uploaded without tangents (ChordAssetDesc::tangents)");
+    if (anySurface && !c->dNormals)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_surface: the scene was uploaded without normals (ChordAssetDesc::normals)");
+    const unsigned long long* vis = nullptr;
+    if ((rc = resolve_source(c, drawed, &vis))) return rc;
+    chord::launch_resolve_surface(c, vis, drawed.cmds, drawed.count, d, tt, ss);
     CHORD_HIP(c, hipGetLastError());
     return CHORDVIS_OK;
 }

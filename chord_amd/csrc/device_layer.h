@@ -315,6 +315,8 @@ struct ChordCtx {
     chord::DMaterial* dMaterials = nullptr;   // per material: what the masked buckets sample
     uint8_t* dTexAlpha = nullptr;             // alpha channel of every level of every texture, back to back
     float* dTexcoords = nullptr;              // float2 per vertex (textureCoord0Buffer), or null
+    float* dNormals = nullptr;                // float3 per vertex (normalBuffer), or null: no asset has normals (chordvis_resolve_surface only)
+    float* dTangents = nullptr;               // float4 per vertex (tangentBuffer), or null: no asset has tangents (likewise)
     uint8_t* dMeshletLod = nullptr;           // per device meshlet: ChordMeshlet::lod (DMeshlet carries vertexBase instead; the resolve's debug view reads it)
     bool anyMasked = false;
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
@@ -523,6 +525,8 @@ void launch_visibility_mark(ChordCtx* c, const unsigned long long* vis, const Ch
 void launch_shading_tiles(ChordCtx* c, const uint32_t* marker, uint32_t shadingType, uint32_t* tiles, uint32_t* count, uint32_t* args);
 void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                                const ChordResolveDesc& desc, const ChordResolveTargets& targets);   // kernels_resolve.hip
+void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                            const ChordResolveDesc& desc, const ChordResolveTargets& targets, const ChordSurfaceTargets& surface);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

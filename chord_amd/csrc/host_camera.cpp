@@ -75,7 +75,7 @@ inline uint32_t nextPOT(uint32_t v) { v--; v |= v >> 1; v |= v >> 2; v |= v >> 4
 
 extern "C" {
 
-const char* chordvis_version(void) { return "chordvis-mi355x 0.1 (gfx950)"; }
+const char* chordvis_version(void) { return "chordvis-mi355x 0.2 (gfx950)"; }
 
 int chordvis_hzb_desc(uint32_t srcWidth, uint32_t srcHeight, ChordHZBDesc* out)
 {

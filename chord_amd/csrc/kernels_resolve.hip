@@ -3,13 +3,20 @@
 // (getTriangleMiscInfo), material.hlsli:41-64 (uv, uv gradients, motion, positionRS), base.hlsli:457-495
 // (calculateTriangleBarycentrics) and nanite_debug.hlsl:30-43,104-130 (the debug colours).
 //
-//   resolve_attributes_kernel   a wave per 16 x 4 pixels.  Its lanes load their visibility words; a ballot loop names one
-//                               leader lane per distinct low word (slot | triangle) of the block; each leader fetches its
-//                               triangle (command -> object / meshlet -> index word -> three vertices) and forms the per-vertex
-//                               products (clip position, translated-world position, the two motion clip positions, uv); every
-//                               pixel reads its leader's values through ds_bpermute and finishes the per-pixel arithmetic.
-//                               Stores: 16 bytes per lane for the float4 images, 256 contiguous bytes per wave and row.
-//
+//   resolve_attributes_kernel<kSurface>   a wave per 16 x 4 pixels.  Its lanes load their visibility words; a ballot loop
+//                               names one leader lane per distinct low word (slot | triangle) of the block; each leader fetches
+//                               its triangle (command -> object / meshlet -> index word -> three vertices) and forms the
+//                               per-vertex products (clip position, translated-world position, the two motion clip positions,
+//                               uv); every pixel reads its leader's values through ds_bpermute and finishes the per-pixel
+//                               arithmetic.  Stores: 16 bytes per lane for the float4 images, 256 contiguous bytes per wave and row.
+//     <false>                   chordvis_resolve_attributes: the eight images.  Same arithmetic and resources as the
+//                               non-template kernel it replaces (108 VGPRs, occupancy 4); its gfx950 code differs from it only
+//                               in register assignment and two integer instructions.
+//     <true>                    chordvis_resolve_surface: the surface channels compiled in.  The leader also fetches the three
+//                               vertices' normals (float3) and tangents (float4) and forms nRS, tRS, bRS
+//                               (nanite_shared.hlsli:157-175); the pixels interpolate them (material.hlsli:95-108).  134 VGPRs,
+//                               occupancy 3.
+
 // The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
 // does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
 
@@ -42,6 +49,16 @@ __constant__ float kLodDebugColor[12][3] = {
 };
 
 __device__ __forceinline__ uint32_t pack_unorm8(float c) { return (uint32_t)(saturatef(c) * 255.0f + 0.5f); }
+
+// normalize(v) = v / sqrt(dot(v, v)), each component divided separately.  Departure from the reference: a vector whose dot(v, v)
+// is not above 0 gives 0, not NaN (a G-buffer carries no NaN)
+__device__ __forceinline__ f3 normalize_or_zero(f3 v)
+{
+    const float l2 = dot3(v, v);
+    if (!(l2 > 0.0f)) return f3{0.0f, 0.0f, 0.0f};
+    const float s = sqrtf(l2);
+    return f3{v.x / s, v.y / s, v.z / s};
+}
 
 // (a0 * b.x + a1 * b.y) + a2 * b.z -- material.hlsli:52-61's interpolation, one component
 __device__ __forceinline__ float interp3(float a0, float a1, float a2, f3 b) { return (a0 * b.x + a1 * b.y) + a2 * b.z; }
@@ -77,7 +94,23 @@ struct ResolveArgs {
 #define RESOLVE_MOTION 64u
 #define RESOLVE_DEBUG 128u
 
-__global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveArgs a)
+// what the surface variant reads besides ResolveArgs
+struct SurfaceArgs {
+    const float* normals;              // float3 per vertex (non-null whenever want != 0)
+    const float* tangents;             // float4 per vertex (non-null whenever want has SURFACE_TANGENT | SURFACE_BITANGENT)
+    uint32_t want;                     // SURFACE_* bits of the non-null targets
+    ChordSurfaceTargets t;
+};
+#define SURFACE_NORMAL 1u
+#define SURFACE_TANGENT 2u
+#define SURFACE_BITANGENT 4u
+
+// resolve_attributes_kernel<false> takes ResolveArgs alone; <true> carries SurfaceArgs after it
+template <bool kSurface> struct KernelArgs : ResolveArgs {};
+template <> struct KernelArgs<true> : ResolveArgs { SurfaceArgs e; };
+
+template <bool kSurface>
+__global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArgs<kSurface> a)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t block = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -106,6 +139,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveAr
     bool ok = false;
     float phs[3][4] = {}, prs[3][3] = {}, cur[3][3] = {}, last[3][3] = {}, uvv[3][2] = {};
     uint32_t meshletHashId = 0u, triWord = 0u, lod = 0u;
+    float nrs[3][3] = {}, trs[3][3] = {}, brs[3][3] = {};                 // (surface variant only)
     if (isLeader) {
         const ChordDrawCmd cmd = a.cmds[slot];
         const uint32_t tri = low & 0xFFu;
@@ -125,6 +159,8 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveAr
                 triWord = a.meshletData[m.dataOffset + V + tri];
                 meshletHashId = cmd.meshletId - a.prims[a.objStatic[cmd.objectId].prim].assetMeshletBase;   // the reference's cmd.y
                 lod = a.meshletLod[cmd.meshletId];
+                Mat4 Mi = {};
+                if constexpr (kSurface) Mi = load_mat(obj.basicData.translatedWorldToLocal);
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
                     const uint32_t vi = a.meshletData[m.dataOffset + ((triWord >> (8 * i)) & 0xFFu)] + m.vertexBase;
@@ -138,6 +174,32 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveAr
                     const f4 ll = mul_mv(mLast, px, py, pz, 1.0f);
                     last[i][0] = ll.x; last[i][1] = ll.y; last[i][2] = ll.w;
                     if (a.texcoords) { uvv[i][0] = a.texcoords[(size_t)vi * 2]; uvv[i][1] = a.texcoords[(size_t)vi * 2 + 1]; }
+                    if constexpr (kSurface) {
+                        if (a.e.want) {
+                            // nRS = normalize(mul(float4(nLS, 0), translatedWorldToLocal).xyz): the row-vector product, component j
+                            // = (x * m0j + y * m1j) + z * m2j
+                            const float nx = a.e.normals[(size_t)vi * 3], ny = a.e.normals[(size_t)vi * 3 + 1], nz = a.e.normals[(size_t)vi * 3 + 2];
+                            const f3 nw = {(nx * Mi.r[0][0] + ny * Mi.r[1][0]) + nz * Mi.r[2][0],
+                                           (nx * Mi.r[0][1] + ny * Mi.r[1][1]) + nz * Mi.r[2][1],
+                                           (nx * Mi.r[0][2] + ny * Mi.r[1][2]) + nz * Mi.r[2][2]};
+                            const f3 n = normalize_or_zero(nw);
+                            nrs[i][0] = n.x; nrs[i][1] = n.y; nrs[i][2] = n.z;
+                            if (a.e.want & (SURFACE_TANGENT | SURFACE_BITANGENT)) {
+                                const float4 tl = reinterpret_cast<const float4*>(a.e.tangents)[vi];
+                                // t = mul(localToTranslatedWorld, float4(tLS.xyz, 0)).xyz; tRS = normalize(t - dot(t, nRS) * nRS)
+                                const f3 tw = {(M.r[0][0] * tl.x + M.r[0][1] * tl.y) + M.r[0][2] * tl.z,
+                                               (M.r[1][0] * tl.x + M.r[1][1] * tl.y) + M.r[1][2] * tl.z,
+                                               (M.r[2][0] * tl.x + M.r[2][1] * tl.y) + M.r[2][2] * tl.z};
+                                const float d = dot3(tw, n);
+                                const f3 t = normalize_or_zero(f3{tw.x - d * n.x, tw.y - d * n.y, tw.z - d * n.z});
+                                trs[i][0] = t.x; trs[i][1] = t.y; trs[i][2] = t.z;
+                                // bRS = cross(nRS, tRS) * tLS.w
+                                brs[i][0] = (n.y * t.z - n.z * t.y) * tl.w;
+                                brs[i][1] = (n.z * t.x - n.x * t.z) * tl.w;
+                                brs[i][2] = (n.x * t.y - n.y * t.x) * tl.w;
+                            }
+                        }
+                    }
                 }
             }
         }
@@ -239,10 +301,27 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const ResolveAr
         const uint32_t rgba = pack_unorm8(c.x) | pack_unorm8(c.y) << 8 | pack_unorm8(c.z) << 16 | 0xFF000000u;
         if (inside) a.t.debugRGBA8[pix] = hit ? rgba : 0xFF000000u;
     }
+    if constexpr (kSurface) {
+        // vertexNormal / tangent / bitangent = (v0 * b.x + v1 * b.y) + v2 * b.z, not renormalised (material.hlsli:98-99)
+        auto put = [&](const float (&V)[3][3], float* dst) {
+            float Q[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) Q[i][k] = lane_read(V[i][k], leader);
+            const float4 v = make_float4(interp3(Q[0][0], Q[1][0], Q[2][0], bary), interp3(Q[0][1], Q[1][1], Q[2][1], bary),
+                                         interp3(Q[0][2], Q[1][2], Q[2][2], bary), 0.0f);
+            if (inside) reinterpret_cast<float4*>(dst)[pix] = hit ? v : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        };
+        if (a.e.want & SURFACE_NORMAL) put(nrs, a.e.t.vertexNormal);
+        if (a.e.want & SURFACE_TANGENT) put(trs, a.e.t.tangent);
+        if (a.e.want & SURFACE_BITANGENT) put(brs, a.e.t.bitangent);
+    }
 }
 
-void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
-                               const ChordResolveDesc& desc, const ChordResolveTargets& t)
+
+static ResolveArgs resolve_args(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                                const ChordResolveDesc& desc, const ChordResolveTargets& t)
 {
     ResolveArgs a;
     a.vis = vis; a.cmds = cmds; a.cmdCount = cmdCount;
@@ -256,8 +335,27 @@ void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const
              (t.debugRGBA8 ? RESOLVE_DEBUG : 0u);
     a.vpNoJitter = desc.translatedWorldToClipNoJitter; a.vpLastNoJitter = desc.translatedWorldToClipLastFrameNoJitter;
     a.t = t;
+    return a;
+}
+
+void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                               const ChordResolveDesc& desc, const ChordResolveTargets& t)
+{
+    KernelArgs<false> a;
+    static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
     const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
-    CHORD_LAUNCH(c, resolve_attributes_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+    CHORD_LAUNCH(c, resolve_attributes_kernel<false>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+}
+
+void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                            const ChordResolveDesc& desc, const ChordResolveTargets& t, const ChordSurfaceTargets& s)
+{
+    KernelArgs<true> a;
+    static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
+    a.e.normals = c->dNormals; a.e.tangents = c->dTangents; a.e.t = s;
+    a.e.want = (s.vertexNormal ? SURFACE_NORMAL : 0u) | (s.tangent ? SURFACE_TANGENT : 0u) | (s.bitangent ? SURFACE_BITANGENT : 0u);
+    const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
+    CHORD_LAUNCH(c, resolve_attributes_kernel<true>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
 }
 
 } // namespace chord

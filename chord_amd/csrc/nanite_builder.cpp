@@ -446,6 +446,7 @@ void build_tree(const std::vector<BGroup>& groups, std::vector<ChordBVHNode>& no
 
 struct ChordBuiltAsset {
     std::vector<float> positions, texcoords;
+    std::vector<float> normals, tangents;       // float3 / float4 per vertex, or empty
     std::vector<ChordMeshlet> meshlets;
     std::vector<ChordMeshletGroup> groups;
     std::vector<uint32_t> groupIndices, meshletData;
@@ -574,6 +575,17 @@ int chordvis_nanite_build(const float* positionsIn, uint32_t vertexCount, const 
     return CHORDVIS_OK;
 }
 
+// Every LOD's vertices are input vertex ids (simplify() collapses onto existing vertices), so the attributes are copied by id.
+int chordvis_nanite_build_attributes(const float* positions, uint32_t vertexCount, const uint32_t* indices, uint32_t indexCount,
+                                     const float* texcoord0, const float* normals, const float* tangents, ChordBuiltAsset** out)
+{
+    const int rc = chordvis_nanite_build(positions, vertexCount, indices, indexCount, texcoord0, out);
+    if (rc != CHORDVIS_OK) return rc;
+    if (normals) (*out)->normals.assign(normals, normals + (size_t)vertexCount * 3);
+    if (tangents) (*out)->tangents.assign(tangents, tangents + (size_t)vertexCount * 4);
+    return CHORDVIS_OK;
+}
+
 int chordvis_built_asset_desc(const ChordBuiltAsset* a, ChordAssetDesc* outAsset, ChordPrimitive* outPrimitive, uint32_t* outLodCount)
 {
     if (!a || !outAsset || !outPrimitive) return CHORDVIS_E_INVALID;
@@ -585,6 +597,8 @@ int chordvis_built_asset_desc(const ChordBuiltAsset* a, ChordAssetDesc* outAsset
     outAsset->positions = a->positions.data(); outAsset->vertexCount = (uint32_t)(a->positions.size() / 3);
     outAsset->texcoord0 = a->texcoords.empty() ? nullptr : a->texcoords.data(); outAsset->texcoord0Count = (uint32_t)(a->texcoords.size() / 2);
     outAsset->bvhNodes = a->bvh.data(); outAsset->bvhNodeCount = (uint32_t)a->bvh.size();
+    outAsset->normals = a->normals.empty() ? nullptr : a->normals.data(); outAsset->normalCount = (uint32_t)(a->normals.size() / 3);
+    outAsset->tangents = a->tangents.empty() ? nullptr : a->tangents.data(); outAsset->tangentCount = (uint32_t)(a->tangents.size() / 4);
     *outPrimitive = a->prim;
     if (outLodCount) *outLodCount = a->lodCount;
     return CHORDVIS_OK;
@@ -595,21 +609,35 @@ void chordvis_free_built_asset(ChordBuiltAsset* a) { delete a; }
 // A flat little-endian container for a built asset: magic, counts, then the arrays as they stand in memory.  (The
 // reference stores cereal binary archives under LZ4, serialize.h:217-320 -- third-party formats of no use without the
 // rest of its asset system; this is the minimum that lets a built mesh be kept and reloaded.)
+// CHRDAS02 (written only when the asset has normals or tangents): two more counts, and the two streams after the BVH.
 static const char kMagic[8] = {'C', 'H', 'R', 'D', 'A', 'S', '0', '1'};
+static const char kMagic2[8] = {'C', 'H', 'R', 'D', 'A', 'S', '0', '2'};
+
+// a stream holds one element per vertex, or none
+static bool streams_match(const ChordBuiltAsset* a)
+{
+    const size_t nv = a->positions.size() / 3;
+    return (a->texcoords.empty() || a->texcoords.size() == nv * 2) && (a->normals.empty() || a->normals.size() == nv * 3) &&
+           (a->tangents.empty() || a->tangents.size() == nv * 4);
+}
 
 int chordvis_save_asset(const ChordBuiltAsset* a, const char* path)
 {
-    if (!a || !path) return CHORDVIS_E_INVALID;
+    if (!a || !path || !streams_match(a)) return CHORDVIS_E_INVALID;
     FILE* f = std::fopen(path, "wb");
     if (!f) return CHORDVIS_E_INVALID;
-    const uint64_t counts[8] = {a->positions.size(), a->texcoords.size(), a->meshlets.size(), a->groups.size(), a->groupIndices.size(),
-                                a->meshletData.size(), a->bvh.size(), a->lodCount};
-    bool ok = std::fwrite(kMagic, 1, 8, f) == 8 && std::fwrite(counts, 8, 8, f) == 8 && std::fwrite(&a->prim, sizeof(a->prim), 1, f) == 1;
+    const bool v2 = !a->normals.empty() || !a->tangents.empty();
+    const uint64_t counts[10] = {a->positions.size(), a->texcoords.size(), a->meshlets.size(), a->groups.size(), a->groupIndices.size(),
+                                 a->meshletData.size(), a->bvh.size(), a->lodCount, a->normals.size(), a->tangents.size()};
+    const size_t nCounts = v2 ? 10 : 8;
+    bool ok = std::fwrite(v2 ? kMagic2 : kMagic, 1, 8, f) == 8 && std::fwrite(counts, 8, nCounts, f) == nCounts &&
+              std::fwrite(&a->prim, sizeof(a->prim), 1, f) == 1;
     auto put = [&](const void* p, size_t bytes) { if (bytes) ok = ok && std::fwrite(p, 1, bytes, f) == bytes; };
     put(a->positions.data(), a->positions.size() * 4); put(a->texcoords.data(), a->texcoords.size() * 4);
     put(a->meshlets.data(), a->meshlets.size() * sizeof(ChordMeshlet)); put(a->groups.data(), a->groups.size() * sizeof(ChordMeshletGroup));
     put(a->groupIndices.data(), a->groupIndices.size() * 4); put(a->meshletData.data(), a->meshletData.size() * 4);
     put(a->bvh.data(), a->bvh.size() * sizeof(ChordBVHNode));
+    put(a->normals.data(), a->normals.size() * 4); put(a->tangents.data(), a->tangents.size() * 4);
     ok = std::fclose(f) == 0 && ok;
     return ok ? CHORDVIS_OK : CHORDVIS_E_INVALID;
 }
@@ -620,16 +648,20 @@ int chordvis_load_asset(const char* path, ChordBuiltAsset** out)
     *out = nullptr;
     FILE* f = std::fopen(path, "rb");
     if (!f) return CHORDVIS_E_INVALID;
-    char magic[8]; uint64_t counts[8];
+    char magic[8]; uint64_t counts[10] = {};
     ChordBuiltAsset* a = new ChordBuiltAsset();
-    bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, kMagic, 8) == 0 && std::fread(counts, 8, 8, f) == 8 &&
-              std::fread(&a->prim, sizeof(a->prim), 1, f) == 1;
-    for (int i = 0; ok && i < 7; i++) ok = counts[i] < (1ull << 32);
+    bool ok = std::fread(magic, 1, 8, f) == 8;
+    const bool v2 = ok && std::memcmp(magic, kMagic2, 8) == 0;
+    ok = ok && (v2 || std::memcmp(magic, kMagic, 8) == 0);
+    const size_t nCounts = v2 ? 10 : 8;
+    ok = ok && std::fread(counts, 8, nCounts, f) == nCounts && std::fread(&a->prim, sizeof(a->prim), 1, f) == 1;
+    for (int i = 0; ok && i < 10; i++) ok = i == 7 || counts[i] < (1ull << 32);
     auto get = [&](auto& vec, uint64_t n) { if (!ok) return; vec.resize((size_t)n); if (n) ok = std::fread(vec.data(), sizeof(vec[0]), (size_t)n, f) == n; };
     if (ok) { get(a->positions, counts[0]); get(a->texcoords, counts[1]); get(a->meshlets, counts[2]); get(a->groups, counts[3]);
-              get(a->groupIndices, counts[4]); get(a->meshletData, counts[5]); get(a->bvh, counts[6]); a->lodCount = (uint32_t)counts[7]; }
+              get(a->groupIndices, counts[4]); get(a->meshletData, counts[5]); get(a->bvh, counts[6]); a->lodCount = (uint32_t)counts[7];
+              get(a->normals, counts[8]); get(a->tangents, counts[9]); }
     std::fclose(f);
-    if (!ok) { delete a; return CHORDVIS_E_INVALID; }
+    if (!ok || !streams_match(a)) { delete a; return CHORDVIS_E_INVALID; }
     *out = a;
     return CHORDVIS_OK;
 }
@@ -647,8 +679,8 @@ int chordvis_load_asset(const char* path, ChordBuiltAsset** out)
 //   LZ4 block: sequences of {token, [literal length bytes], literals, offset16, [match length bytes]}, min match 4, the last
 //     sequence literals only.
 // Pinned by tests/golden/gltf_binary_{raw,lz4}.bin, which the reference's vendored cereal and LZ4 wrote
-// (tests/golden/make_gltf_binary_fixture.{cpp,sh}).  Vertex attributes this path never reads (normals, tangents, second UV set,
-// colours, smooth normals, LOD-0 indices) are skipped on load and written empty.
+// (tests/golden/make_gltf_binary_fixture.{cpp,sh}).  Vertex attributes this path never reads (second UV set, colours, smooth
+// normals, LOD-0 indices) are skipped on load and written empty.
 
 namespace {
 
@@ -726,14 +758,14 @@ extern "C" {
 // The reference's GLTFBinary archive of a built asset (compressionMode None / Lz4).
 int chordvis_save_gltf_binary(const ChordBuiltAsset* a, const char* path, int lz4)
 {
-    if (!a || !path) return CHORDVIS_E_INVALID;
+    if (!a || !path || !streams_match(a)) return CHORDVIS_E_INVALID;
     ByteWriter w;
     w.put<uint32_t>(0u);                                                             // GLTFBinary: class version (kAssetVersion = 0)
     const uint64_t nv = a->positions.size() / 3;
     w.put<uint64_t>(nv); w.raw(a->positions.data(), a->positions.size() * 4);       // positions (vec3 by component = the floats as they stand)
-    w.put<uint64_t>(0);                                                              // normals
+    w.put<uint64_t>(a->normals.size() / 3); w.raw(a->normals.data(), a->normals.size() * 4);         // normals (vec3)
     w.put<uint64_t>(a->texcoords.size() / 2); w.raw(a->texcoords.data(), a->texcoords.size() * 4);   // texcoords0
-    w.put<uint64_t>(0);                                                              // tangents
+    w.put<uint64_t>(a->tangents.size() / 4); w.raw(a->tangents.data(), a->tangents.size() * 4);      // tangents (vec4)
     w.put<uint64_t>(0); w.put<uint64_t>(0); w.put<uint64_t>(0);                     // smoothNormals, texcoords1, colors0
     w.put<uint64_t>(a->meshlets.size());
     for (size_t i = 0; i < a->meshlets.size(); i++) {                                // serialize.h:64-75 member order
@@ -807,9 +839,9 @@ static int load_gltf_binary_impl(const char* path, ChordBuiltAsset** out)
     // an element count times its size, refused (reader marked bad) when the product exceeds the bytes that remain
     auto bytes_of = [&](uint64_t elem) -> uint64_t { const uint64_t n = r.get<uint64_t>(); if (n > (raw.size() - r.i) / elem) { r.ok = false; return 0; } return n * elem; };
     r.floats(a->positions, bytes_of(12) / 4);
-    r.skip(bytes_of(12));                                                            // normals
+    r.floats(a->normals, bytes_of(12) / 4);
     r.floats(a->texcoords, bytes_of(8) / 4);
-    r.skip(bytes_of(16));                                                            // tangents
+    r.floats(a->tangents, bytes_of(16) / 4);
     r.skip(bytes_of(12)); r.skip(bytes_of(8)); r.skip(bytes_of(16));                 // smoothNormals, texcoords1, colors0
     uint64_t n = r.get<uint64_t>();
     if (n > (raw.size() - r.i) / 64) r.ok = false;
@@ -847,7 +879,7 @@ static int load_gltf_binary_impl(const char* path, ChordBuiltAsset** out)
     if (n > (raw.size() - r.i) / 4) r.ok = false; else { a->groupIndices.resize((size_t)n); for (uint64_t i = 0; i < n; i++) a->groupIndices[(size_t)i] = r.get<uint32_t>(); }
     r.skip(bytes_of(4));                                                             // lod0Indices
     if (!r.ok || r.i != raw.size() || a->positions.empty()) return CHORDVIS_E_INVALID;
-    if (!a->texcoords.empty() && a->texcoords.size() / 2 != a->positions.size() / 3) return CHORDVIS_E_INVALID;   // one uv per vertex, or none
+    if (!streams_match(a)) return CHORDVIS_E_INVALID;                                // one uv / normal / tangent per vertex, or none
     // one primitive over everything
     std::memset(&a->prim, 0, sizeof(a->prim));
     const size_t nv = a->positions.size() / 3;

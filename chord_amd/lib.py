@@ -48,8 +48,15 @@ class ResolveTargets(C.Structure):
                 ("uvGrad", C.c_void_p), ("positionRS", C.c_void_p), ("motionVector", C.c_void_p), ("debugRGBA8", C.c_void_p)]
 
 
+class SurfaceTargets(C.Structure):
+    """ChordSurfaceTargets: device pointers, None = not written (pad stays None)."""
+    _fields_ = [("vertexNormal", C.c_void_p), ("tangent", C.c_void_p), ("bitangent", C.c_void_p), ("pad", C.c_void_p)]
+
+
 # name -> floats (or uint32 for debugRGBA8) per texel of each resolve target (include/chordvis.h ChordResolveTargets)
 RESOLVE_CHANNELS = {"barycentrics": 4, "baryDdx": 4, "baryDdy": 4, "uv": 2, "uvGrad": 4, "positionRS": 4, "motionVector": 2, "debugRGBA8": 1}
+# ... and of the surface targets of chordvis_resolve_surface (ChordSurfaceTargets)
+SURFACE_CHANNELS = {"vertexNormal": 4, "tangent": 4, "bitangent": 4}
 DEBUG_MESHLET, DEBUG_TRIANGLE, DEBUG_LOD, DEBUG_LOD_MESHLET, DEBUG_BARYCENTRICS = 0, 1, 2, 3, 4
 
 
@@ -129,6 +136,7 @@ def _load():
         "chordvis_object_basic_data": (i32, [vp, vp, vp, vp, vp]),
         "chordvis_object_basic_data_batch": (i32, [u32, vp, vp, vp, vp, vp]),
         "chordvis_nanite_build": (i32, [vp, u32, vp, u32, vp, P(vp)]),
+        "chordvis_nanite_build_attributes": (i32, [vp, u32, vp, u32, vp, vp, vp, P(vp)]),
         "chordvis_meshlet_bounds": (i32, [vp, u32, vp, u32, vp]),
         "chordvis_built_asset_desc": (i32, [vp, P(R.AssetDesc), vp, P(u32)]),
         "chordvis_free_built_asset": (None, [vp]),
@@ -197,6 +205,7 @@ def _load():
         "chordvis_wait_visibility": (i32, [vp, vp]),
         "chordvis_prepare_shading_tile_param": (i32, [vp, u32, P(TileMarker), P(ShadingTiles)]),
         "chordvis_resolve_attributes": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets)]),
+        "chordvis_resolve_surface": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets)]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),
         "chordvis_readback_shading_tiles": (i32, [vp, P(ShadingTiles), vp, u32, P(u32), vp]),
@@ -335,16 +344,28 @@ class BuiltAsset:
         self.positions = arr(ad.positions, ad.vertexCount * 3, np.float32).reshape(-1, 3)
         self.texcoord0 = arr(ad.texcoord0, ad.texcoord0Count * 2, np.float32).reshape(-1, 2) if ad.texcoord0 else None
         self.bvh_nodes = arr(ad.bvhNodes, ad.bvhNodeCount, R.BVH_NODE)
+        self.normals = arr(ad.normals, ad.normalCount * 3, np.float32).reshape(-1, 3) if ad.normals else None
+        self.tangents = arr(ad.tangents, ad.tangentCount * 4, np.float32).reshape(-1, 4) if ad.tangents else None
         self.primitive = prim
         self.lod_count = lods.value
 
 
-def nanite_build(positions, indices, texcoord0=None, keep_handle=False):
+def nanite_build(positions, indices, texcoord0=None, keep_handle=False, normals=None, tangents=None):
+    """normals (n, 3) / tangents (n, 4): carried along by vertex id (chordvis_nanite_build_attributes, called only when either is
+    given); the built meshlets, groups and BVH are the same either way."""
     pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
     idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
     uv = None if texcoord0 is None else np.ascontiguousarray(texcoord0, dtype=np.float32).reshape(-1, 2)
     h = C.c_void_p()
-    rc = lib.chordvis_nanite_build(pos.ctypes.data, len(pos), idx.ctypes.data, len(idx), uv.ctypes.data if uv is not None else None, C.byref(h))
+    if normals is None and tangents is None:
+        rc = lib.chordvis_nanite_build(pos.ctypes.data, len(pos), idx.ctypes.data, len(idx), uv.ctypes.data if uv is not None else None, C.byref(h))
+    else:
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        tng = None if tangents is None else np.ascontiguousarray(tangents, dtype=np.float32).reshape(-1, 4)
+        if (nrm is not None and len(nrm) != len(pos)) or (tng is not None and len(tng) != len(pos)):
+            raise ChordvisError("nanite_build: normals / tangents need one entry per vertex")
+        rc = lib.chordvis_nanite_build_attributes(pos.ctypes.data, len(pos), idx.ctypes.data, len(idx), uv.ctypes.data if uv is not None else None,
+                                                  nrm.ctypes.data if nrm is not None else None, tng.ctypes.data if tng is not None else None, C.byref(h))
     if rc != OK:
         raise ChordvisError("chordvis_nanite_build -> %d" % rc)
     if keep_handle:

@@ -100,6 +100,8 @@ class AssetDesc(C.Structure):
         ("positions", C.c_void_p), ("vertexCount", C.c_uint32),
         ("texcoord0", C.c_void_p), ("texcoord0Count", C.c_uint32),
         ("bvhNodes", C.c_void_p), ("bvhNodeCount", C.c_uint32),
+        ("normals", C.c_void_p), ("normalCount", C.c_uint32),
+        ("tangents", C.c_void_p), ("tangentCount", C.c_uint32),
     ]
 
 
@@ -171,8 +173,9 @@ class Scene:
     """
 
     def __init__(self, objects, primitives, materials, meshlets, groups, group_indices, meshlet_data, positions,
-                 name="scene", texcoord0=None, textures=(), samplers=None, bvh_nodes=None):
-        """textures: sequence of (H, W, 4) uint8 images (mip chains are built here); samplers: SAMPLER records."""
+                 name="scene", texcoord0=None, textures=(), samplers=None, bvh_nodes=None, normals=None, tangents=None):
+        """textures: sequence of (H, W, 4) uint8 images (mip chains are built here); samplers: SAMPLER records; normals (n, 3) and
+        tangents (n, 4, w = handedness) float32 per vertex, or None (read only by chordvis_resolve_surface)."""
         self.name = name
         self.objects = np.ascontiguousarray(objects, dtype=OBJECT)
         self.primitives = np.ascontiguousarray(primitives, dtype=PRIMITIVE)
@@ -184,6 +187,8 @@ class Scene:
         self.positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         self.bvh_nodes = None if bvh_nodes is None else np.ascontiguousarray(bvh_nodes, dtype=BVH_NODE)
         self.texcoord0 = None if texcoord0 is None else np.ascontiguousarray(texcoord0, dtype=f32).reshape(-1, 2)
+        self.normals = None if normals is None else np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
+        self.tangents = None if tangents is None else np.ascontiguousarray(tangents, dtype=f32).reshape(-1, 4)
         self.texture_images = list(textures)
         self._tex_chains = [mip_chain_rgba8(t) for t in self.texture_images]
         self._textures = (Texture * max(1, len(self._tex_chains)))()
@@ -198,6 +203,8 @@ class Scene:
             self.positions.ctypes.data, len(self.positions),
             self.texcoord0.ctypes.data if self.texcoord0 is not None else None, len(self.texcoord0) if self.texcoord0 is not None else 0,
             self.bvh_nodes.ctypes.data if self.bvh_nodes is not None else None, len(self.bvh_nodes) if self.bvh_nodes is not None else 0,
+            self.normals.ctypes.data if self.normals is not None else None, len(self.normals) if self.normals is not None else 0,
+            self.tangents.ctypes.data if self.tangents is not None else None, len(self.tangents) if self.tangents is not None else 0,
         )
         self._assets = (AssetDesc * 1)(self._asset)
         self.desc = SceneDesc(
@@ -213,7 +220,8 @@ class Scene:
         """The same geometry, textures and samplers under other object / material records (shallow: arrays are shared)."""
         out = Scene(self.objects if objects is None else objects, self.primitives, self.materials if materials is None else materials,
                     self.meshlets, self.groups, self.group_indices, self.meshlet_data, self.positions, name=self.name,
-                    texcoord0=self.texcoord0, textures=self.texture_images, samplers=self.samplers, bvh_nodes=self.bvh_nodes)
+                    texcoord0=self.texcoord0, textures=self.texture_images, samplers=self.samplers, bvh_nodes=self.bvh_nodes,
+                    normals=self.normals, tangents=self.tangents)
         if hasattr(self, "local_to_world"):
             out.local_to_world = self.local_to_world
         return out

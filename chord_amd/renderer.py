@@ -299,12 +299,15 @@ class VisibilityRenderer:
         launch: {name: tensor} for `names` (default: every target of L.RESOLVE_CHANNELS), each (height, width, channels) float32
         ((height, width) int32 holding RGBA8 for "debugRGBA8") on the context's device.  desc: an L.ResolveDesc or None (all zero).
         out: {name: tensor} to write into instead of fresh tensors.  The tensors are ordered against the context's stream
-        both ways: the resolve waits for the current torch stream, which in turn waits for the resolve."""
+        both ways: the resolve waits for the current torch stream, which in turn waits for the resolve.
+        Names of L.SURFACE_CHANNELS (vertexNormal, tangent, bitangent; float4 each) may be asked for too: the call then goes through
+        chordvis_resolve_surface, still one launch (the scene must have been uploaded with normals / tangents)."""
         import torch
         names = list(L.RESOLVE_CHANNELS) if names is None else list(names)
-        bad = [n for n in names if n not in L.RESOLVE_CHANNELS]
+        channels = dict(L.RESOLVE_CHANNELS, **L.SURFACE_CHANNELS)
+        bad = [n for n in names if n not in channels]
         if bad or not names:
-            raise ValueError("resolve_attributes: unknown or no target names %r (known: %s)" % (bad, ", ".join(L.RESOLVE_CHANNELS)))
+            raise ValueError("resolve_attributes: unknown or no target names %r (known: %s)" % (bad, ", ".join(channels)))
         dev = torch.device("cuda", self.device)
         mine = torch.cuda.ExternalStream(self.stream(), device=dev)
         cur = torch.cuda.current_stream(dev)
@@ -313,18 +316,23 @@ class VisibilityRenderer:
             if out is not None and n in out:
                 t = out[n]
             else:
-                ch = L.RESOLVE_CHANNELS[n]
+                ch = channels[n]
                 shape = (self.height, self.width) if ch == 1 else (self.height, self.width, ch)
                 with torch.cuda.device(dev):
                     t = torch.empty(shape, dtype=torch.int32 if n == "debugRGBA8" else torch.float32, device=dev)
-            assert t.is_contiguous() and t.numel() == self.width * self.height * L.RESOLVE_CHANNELS[n], n
+            assert t.is_contiguous() and t.numel() == self.width * self.height * channels[n], n
             res[n] = t
-        targets = L.ResolveTargets(**{n: t.data_ptr() for n, t in res.items()})
+        targets = L.ResolveTargets(**{n: t.data_ptr() for n, t in res.items() if n in L.RESOLVE_CHANNELS})
+        surface = {n: t.data_ptr() for n, t in res.items() if n in L.SURFACE_CHANNELS}
         cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
         if mine.cuda_stream != cur.cuda_stream:
             mine.wait_stream(cur)                      # (the allocator may hand out memory torch work on `cur` still uses)
-        self._check(L.lib.chordvis_resolve_attributes(self._ctx, cmd, C.byref(desc) if desc is not None else None, C.byref(targets)),
-                    "resolve_attributes")
+        d = C.byref(desc) if desc is not None else None
+        if surface:
+            self._check(L.lib.chordvis_resolve_surface(self._ctx, cmd, d, C.byref(targets), C.byref(L.SurfaceTargets(**surface))),
+                        "resolve_surface")
+        else:
+            self._check(L.lib.chordvis_resolve_attributes(self._ctx, cmd, d, C.byref(targets)), "resolve_attributes")
         if mine.cuda_stream != cur.cuda_stream:
             cur.wait_stream(mine)
             for t in res.values():

@@ -96,9 +96,16 @@ def _meshlet_bounds(pos):
 
 
 class PrimitiveBuilder:
-    """Accumulates parametric surfaces into one primitive (one GLTFPrimitiveBuffer)."""
+    """Accumulates parametric surfaces into one primitive (one GLTFPrimitiveBuffer).
 
-    def __init__(self):
+    attributes=True also makes per-vertex normals and tangents (surface_frames): smooth, unit length in float32, the tangent along
+    +u, its handedness w alternating +1 / -1 from one add_surface to the next."""
+
+    def __init__(self, attributes=False):
+        self.attributes = attributes
+        self.normals = []          # list of (n,3) float32 (attributes only)
+        self.tangents = []         # list of (n,4) float32 (attributes only)
+        self.nsurfaces = 0
         self.positions = []        # list of (n,3) float32
         self.texcoords = []        # list of (n,2) float32: the surface parameters (u, v) times uv_scale
         self.uv_scale = (1.0, 1.0)
@@ -115,6 +122,9 @@ class PrimitiveBuilder:
         """pos (M,81,3) float32, uv (M,81,2). Returns meshlet ids (relative to this primitive)."""
         M = pos.shape[0]
         self.texcoords.append(np.zeros((M * PATCH_V, 2), np.float32) if uv is None else uv.reshape(-1, 2).astype(np.float32))
+        if self.attributes:
+            self.normals.append(self._last_frame[0].reshape(-1, 3))
+            self.tangents.append(self._last_frame[1].reshape(-1, 4))
         pmin, pmax, axis, cutoff, apex = _meshlet_bounds(pos)
         ml = np.zeros(M, dtype=T.MESHLET)
         ml["posMin"], ml["posMax"] = pmin, pmax
@@ -154,6 +164,8 @@ class PrimitiveBuilder:
         if lods > 1:
             assert P % 4 == 0 and Q % 4 == 0, "LOD quadtree needs patch grids in multiples of 4"
         k = np.arange(9) / 8.0
+        handedness = 1.0 if self.nsurfaces % 2 == 0 else -1.0
+        self.nsurfaces += 1
 
         def sample(u0, v0, du, dv):
             # u0,v0: (M,) patch origins; du,dv patch extents -> (M,81,3) float32 (row j = v, col i = u)
@@ -161,6 +173,8 @@ class PrimitiveBuilder:
             V = v0[:, None, None] + dv * k[None, :, None]
             U, V = np.broadcast_arrays(U, V)
             self._last_uv = np.stack([U * self.uv_scale[0], V * self.uv_scale[1]], axis=-1).astype(np.float32).reshape(len(u0), 81, 2)
+            if self.attributes:
+                self._last_frame = surface_frames(S, U, V, handedness)
             return S(U, V).astype(np.float32).reshape(len(u0), 81, 3)
 
         pi, pj = np.meshgrid(np.arange(P), np.arange(Q), indexing="xy")     # (Q,P)
@@ -220,11 +234,72 @@ class PrimitiveBuilder:
             bvh_nodes=nodes,
             positions=pos,
             texcoords=np.concatenate(self.texcoords) if self.texcoords else np.zeros((0, 2), np.float32),
+            normals=np.concatenate(self.normals) if self.attributes else None,
+            tangents=np.concatenate(self.tangents) if self.attributes else None,
             meshlets=np.concatenate(self.meshlets),
             meshlet_data=np.concatenate(self.meshlet_data),
             groups=np.concatenate(self.groups),
             group_indices=np.concatenate(self.group_indices),
         )
+
+
+def surface_frames(S, U, V, handedness=1.0, h=1e-5):
+    """Normals and tangents of the surface S at the parameters (U, V): the partials dS/du and dS/dv by float64 central differences
+    of the surface function, n = normalize(dS/du x dS/dv), t = (normalize(dS/du), handedness).  Returns float32 (..., 3) and
+    (..., 4)."""
+    su = (S(U + h, V) - S(U - h, V)) / (2.0 * h)
+    sv = (S(U, V + h) - S(U, V - h)) / (2.0 * h)
+    n = np.cross(su, sv)
+    n = n / np.linalg.norm(n, axis=-1, keepdims=True)
+    t = su / np.linalg.norm(su, axis=-1, keepdims=True)
+    return _unit32(n), np.concatenate([_unit32(t), np.full(t.shape[:-1] + (1,), handedness, np.float32)], axis=-1)
+
+
+def _unit32(v):
+    """float64 unit vectors -> float32: divided by the length of their float32 rounding, then rounded (|v| = 1 to float32 rounding)"""
+    v = np.asarray(v, dtype=np.float64)
+    v32 = v.astype(np.float32)
+    l = np.sqrt((v32.astype(np.float64) ** 2).sum(axis=-1, keepdims=True))
+    return (v / l).astype(np.float32)
+
+
+def mesh_attributes(positions, indices, texcoord0=None):
+    """Smooth normals and tangents of an indexed triangle mesh, in float64: normals = normalized area-weighted face normals; tangents
+    = the area-weighted dP/du of the texture coordinates (u along +x of the mesh when there are none), made orthogonal to the normal
+    and normalised, w = the sign of dot(cross(n, t), dP/dv).  A vertex with no usable direction gets a tangent perpendicular to n."""
+    p = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    tri = np.asarray(indices, dtype=np.int64).reshape(-1, 3)
+    e1, e2 = p[tri[:, 1]] - p[tri[:, 0]], p[tri[:, 2]] - p[tri[:, 0]]
+    fn = np.cross(e1, e2)                                       # |fn| = 2 x area: the area weight
+    n = np.zeros_like(p)
+    for k in range(3):
+        np.add.at(n, tri[:, k], fn)
+    n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-300)
+    tu, tv = np.zeros_like(p), np.zeros_like(p)
+    if texcoord0 is not None:
+        uv = np.asarray(texcoord0, dtype=np.float64).reshape(-1, 2)
+        d1, d2 = uv[tri[:, 1]] - uv[tri[:, 0]], uv[tri[:, 2]] - uv[tri[:, 0]]
+        d1 = d1 - np.round(d1); d2 = d2 - np.round(d2)            # (wrapped coordinates: the seam of a closed surface)
+        det = d1[:, 0] * d2[:, 1] - d2[:, 0] * d1[:, 1]
+        ok = np.abs(det) > 1e-12
+        r = np.where(ok, 1.0 / np.where(ok, det, 1.0), 0.0)[:, None]
+        area = 0.5 * np.linalg.norm(fn, axis=1)[:, None]
+        fu = (e1 * d2[:, 1:2] - e2 * d1[:, 1:2]) * r
+        fv = (e2 * d1[:, 0:1] - e1 * d2[:, 0:1]) * r
+        fu *= area / np.maximum(np.linalg.norm(fu, axis=1, keepdims=True), 1e-300)
+        fv *= area / np.maximum(np.linalg.norm(fv, axis=1, keepdims=True), 1e-300)
+        for k in range(3):
+            np.add.at(tu, tri[:, k], fu)
+            np.add.at(tv, tri[:, k], fv)
+    else:
+        tu[:] = (1.0, 0.0, 0.0)
+    t = tu - (tu * n).sum(axis=1, keepdims=True) * n
+    bad = np.linalg.norm(t, axis=1) < 1e-9
+    alt = np.cross(n, np.where(np.abs(n[:, 1:2]) < 0.9, (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)))
+    t = np.where(bad[:, None], alt, t)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    w = np.where((np.cross(n, t) * tv).sum(axis=1) < 0.0, -1.0, 1.0)
+    return _unit32(n), np.concatenate([_unit32(t), w[:, None].astype(np.float32)], axis=1)
 
 
 def build_bvh(groups):
@@ -299,8 +374,9 @@ def build_bvh(groups):
 
 
 class SceneBuilder:
-    def __init__(self, name):
+    def __init__(self, name, attributes=False):
         self.name = name
+        self.attributes = attributes      # normals and tangents in the scene (every primitive's PrimitiveBuilder makes them)
         self.prims = []
         self.materials = [self._material(0)]
         self.obj_prim = []
@@ -344,7 +420,7 @@ class SceneBuilder:
 
     def build(self):
         prims = np.zeros(len(self.prims), dtype=T.PRIMITIVE)
-        pos, ml, md, gr, gi, uv, bv = [], [], [], [], [], [], []
+        pos, ml, md, gr, gi, uv, bv, nrm, tng = [], [], [], [], [], [], [], [], []
         nv = nm = nd = ng = ni = nb = 0
         for i, p in enumerate(self.prims):
             prims[i]["posMin"] = p["positions"].min(axis=0)
@@ -359,6 +435,9 @@ class SceneBuilder:
             m = p["meshlets"].copy()
             m["dataOffset"] += nd
             uv.append(p["texcoords"]); pos.append(p["positions"]); ml.append(m); md.append(p["meshlet_data"]); gr.append(p["groups"]); gi.append(p["group_indices"])
+            if self.attributes:
+                assert p["normals"] is not None, "SceneBuilder(attributes=True): every primitive needs PrimitiveBuilder(attributes=True)"
+                nrm.append(p["normals"]); tng.append(p["tangents"])
             nv += len(p["positions"]); nm += len(m); nd += len(p["meshlet_data"]); ng += len(p["groups"]); ni += len(p["group_indices"])
         objects = np.zeros(len(self.obj_prim), dtype=T.OBJECT)
         objects["GLTFPrimitiveDetail"] = np.array(self.obj_prim, dtype=np.uint32)
@@ -367,7 +446,8 @@ class SceneBuilder:
                         np.concatenate(gi), np.concatenate(md), np.concatenate(pos), name=self.name,
                         texcoord0=np.concatenate(uv) if (self.textures and uv) else None, textures=self.textures,
                         samplers=np.array(self.samplers, dtype=T.SAMPLER) if self.samplers else None,
-                        bvh_nodes=np.concatenate(bv) if bv else None)
+                        bvh_nodes=np.concatenate(bv) if bv else None,
+                        normals=np.concatenate(nrm) if self.attributes else None, tangents=np.concatenate(tng) if self.attributes else None)
         # glm column-major doubles
         scene.local_to_world = np.ascontiguousarray(np.stack([m.T.reshape(16) for m in self.obj_l2w]), dtype=np.float64)
         return scene
@@ -518,7 +598,7 @@ def _street_primitives(sb, lods=3, uv_tiles=None):
     """Unique geometry of one 'street' block: ground + 40 buildings + 311 props. Returns [(prim, l2w)].
     uv_tiles: (buildings, props) texture repeats per surface for the masked variant (texture coordinates are generated either way)."""
     out = []
-    pb = PrimitiveBuilder()
+    pb = PrimitiveBuilder(sb.attributes)
     pb.add_surface(plane_surface((-64, 0, 64), (128, 0, 0), (0, 0, -128), 3000, 0.08, 0.9), 64, 64, lods)
     out.append((sb.add_primitive(pb), np.eye(4)))
     # 4 rows x 10 buildings along x; rows at z = -34, -14 | +14, +34 (street down the middle)
@@ -527,7 +607,7 @@ def _street_primitives(sb, lods=3, uv_tiles=None):
         for k in range(10):
             r = rand01(3100, np.arange(b * 4, b * 4 + 4))
             w, d, h = 9.0 + 2.0 * r[0], 9.0 + 2.0 * r[1], 10.0 + 14.0 * r[2]
-            pb = PrimitiveBuilder()
+            pb = PrimitiveBuilder(sb.attributes)
             if uv_tiles:
                 pb.uv_scale = (uv_tiles[0], uv_tiles[0])
             _building(pb, w, d, h, 3200 + b * 8, lods)
@@ -538,7 +618,7 @@ def _street_primitives(sb, lods=3, uv_tiles=None):
     for p in range(311):
         r = rand01(3900, np.arange(p * 5, p * 5 + 5))
         rad, hgt = 0.15 + 0.5 * r[0], 0.8 + 3.5 * r[1]
-        pb = PrimitiveBuilder()
+        pb = PrimitiveBuilder(sb.attributes)
         if uv_tiles:
             pb.uv_scale = (uv_tiles[1], uv_tiles[1])
         pb.add_surface(cylinder_surface((0, 0, 0), rad, hgt, 4000 + p, 0.02), 4, 4, lods)
@@ -547,12 +627,13 @@ def _street_primitives(sb, lods=3, uv_tiles=None):
     return out
 
 
-def config3_street(width=3840, height=2160, lods=3, masked=False):
+def config3_street(width=3840, height=2160, lods=3, masked=False, attributes=False):
     """BASELINE config 3 (Bistro-class): 21 872 LOD0 patches = 2 799 616 triangles, 352 objects, 3 LOD levels.
     masked: the SAME geometry with alpha-tested materials (mesh_raster.hlsl:34-38,107-112,198-204) on every prop and every other
     building -- two-sided foliage-style cut-outs (a noise and a disc texture, trilinear / nearest samplers): the workload of
-    bench.py --workload street_4k_masked, triangle for triangle the opaque scene."""
-    sb = SceneBuilder("config3_street" + ("_masked" if masked else ""))
+    bench.py --workload street_4k_masked, triangle for triangle the opaque scene.
+    attributes: with per-vertex normals and tangents (PrimitiveBuilder); the geometry is the same."""
+    sb = SceneBuilder("config3_street" + ("_masked" if masked else ""), attributes)
     mats = [0]
     if masked:
         tex = [sb.add_texture(t) for t in _alpha_textures(11)]
@@ -589,16 +670,16 @@ def config4_street_x64(width=3840, height=2160, grid=8, lods=3):
     return sb.build(), cam
 
 
-def small_test_scene(width=160, height=96, lods=3, seed=7, two_sided_every=3):
-    """A small multi-object scene with LODs for parity tests (a few hundred meshlets)."""
-    sb = SceneBuilder("small_test_scene")
+def small_test_scene(width=160, height=96, lods=3, seed=7, two_sided_every=3, attributes=False):
+    """A small multi-object scene with LODs for parity tests (a few hundred meshlets).  attributes: with normals and tangents."""
+    sb = SceneBuilder("small_test_scene", attributes)
     two = sb.add_material(1)
-    pb = PrimitiveBuilder()
+    pb = PrimitiveBuilder(sb.attributes)
     pb.add_surface(plane_surface((-8, 0, 8), (16, 0, 0), (0, 0, -16), seed, 0.2, 0.7), 8, 8, lods)
     sb.add_object(sb.add_primitive(pb))
     for k in range(6):
         r = rand01(seed + 1, np.arange(k * 4, k * 4 + 4))
-        pb = PrimitiveBuilder()
+        pb = PrimitiveBuilder(sb.attributes)
         if k % 2 == 0:
             _building(pb, 1.5 + r[0], 1.5 + r[1], 1.0 + 2.5 * r[2], seed * 100 + k * 8, min(lods, 3))
         else:
@@ -659,11 +740,12 @@ def _alpha_textures(seed):
     return out
 
 
-def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2, 6.0), front=(0.75, -0.22, -0.62)):
+def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2, 6.0), front=(0.75, -0.22, -0.62), attributes=False):
     """small_test_scene's layout with alpha-tested, blended and white-fallback materials (mesh_raster.hlsl:34-38,107-112,
     198-204; mesh_raster.cpp:224): holes in the masked surfaces show the geometry behind them, blended objects draw
-    nothing.  Three textures x three samplers (every wrap mode, nearest and linear, with and without minification)."""
-    sb = SceneBuilder("masked_test_scene")
+    nothing.  Three textures x three samplers (every wrap mode, nearest and linear, with and without minification).
+    attributes: with normals and tangents."""
+    sb = SceneBuilder("masked_test_scene", attributes)
     tex = [sb.add_texture(t) for t in _alpha_textures(seed)]
     smp = [sb.add_sampler(T.FILTER_LINEAR_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_REPEAT),
            sb.add_sampler(T.FILTER_NEAREST, T.FILTER_NEAREST, T.WRAP_CLAMP_TO_EDGE, T.WRAP_MIRRORED_REPEAT),
@@ -674,12 +756,12 @@ def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2
             sb.add_material(0, T.ALPHA_BLEND),                                  # blended: draws nothing
             sb.add_material(0, T.ALPHA_MASK, 0xFFFFFFFF, 99, 0.5, 1.0),        # no texture: white fallback, opaque in effect
             sb.add_material(1, T.ALPHA_MASK, tex[0], smp[0], 0.5, 0.4)]        # alpha factor below the cut-off: nothing survives
-    pb = PrimitiveBuilder()
+    pb = PrimitiveBuilder(sb.attributes)
     pb.add_surface(plane_surface((-8, 0, 8), (16, 0, 0), (0, 0, -16), seed, 0.2, 0.7), 8, 8, lods)
     sb.add_object(sb.add_primitive(pb))                                          # opaque ground
     for k in range(8):
         r = rand01(seed + 1, np.arange(k * 4, k * 4 + 4))
-        pb = PrimitiveBuilder()
+        pb = PrimitiveBuilder(sb.attributes)
         pb.uv_scale = (1.0 + 3.0 * r[3], 0.5 + 2.5 * r[2]) if k % 3 else (-2.0, 3.0)     # tiling, incl. negative coordinates
         if k % 2 == 0:
             _building(pb, 1.5 + r[0], 1.5 + r[1], 1.0 + 2.5 * r[2], seed * 100 + k * 8, lods)
@@ -691,7 +773,7 @@ def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2
         if k in (1, 4):                                                          # an opaque copy behind a masked one
             sb.add_object(prim, translate(0.6, 0.0, -1.2) @ m, material=0)
     # a masked screen right in front of the camera: magnified texels, clipped by the near plane at the edges
-    pb = PrimitiveBuilder()
+    pb = PrimitiveBuilder(sb.attributes)
     pb.uv_scale = (3.0, 2.0)
     f = np.array(front, dtype=np.float64) / np.linalg.norm(front)
     side = np.cross(f, (0.0, 1.0, 0.0)); side /= np.linalg.norm(side)
@@ -741,12 +823,19 @@ def bumpy_sphere_mesh(n=96, seed=1):
     return pos, idx, uv
 
 
-def scene_from_meshes(meshes, local_to_world, prim_of_object=None, two_sided_of_object=None, name="mesh_scene"):
+def scene_from_meshes(meshes, local_to_world, prim_of_object=None, two_sided_of_object=None, name="mesh_scene", attributes=False):
     """A scene of triangle meshes that go through chordvis_nanite_build (own clusterizer / partition / simplifier, SURVEY
     8f-4): `meshes` = [(positions, indices, texcoord0 or None), ...], one primitive each; `local_to_world` = 4x4 matrices, one
-    object each (object k instantiates primitive prim_of_object[k], default k mod len(meshes))."""
+    object each (object k instantiates primitive prim_of_object[k], default k mod len(meshes)).  attributes: normals and tangents of
+    mesh_attributes built along (chordvis_nanite_build_attributes)."""
     from . import lib as L
-    prims = [L.nanite_build(pos, idx, uv) for pos, idx, uv in meshes]
+    if attributes:
+        prims = []
+        for pos, idx, uv in meshes:
+            nrm, tng = mesh_attributes(pos, idx, uv)
+            prims.append(L.nanite_build(pos, idx, uv, normals=nrm, tangents=tng))
+    else:
+        prims = [L.nanite_build(pos, idx, uv) for pos, idx, uv in meshes]
     pr = np.zeros(len(prims), dtype=T.PRIMITIVE)
     ml, md, gr, gi, ps, bv, uvs = [], [], [], [], [], [], []
     nv = nm = nd = ng = ni = nb = 0
@@ -763,18 +852,21 @@ def scene_from_meshes(meshes, local_to_world, prim_of_object=None, two_sided_of_
     objects["GLTFPrimitiveDetail"] = (np.arange(len(local_to_world)) % len(prims)) if prim_of_object is None else np.asarray(prim_of_object)
     objects["GLTFMaterialData"] = 0 if two_sided_of_object is None else np.asarray(two_sided_of_object)
     scene = T.Scene(objects, pr, mats, np.concatenate(ml), np.concatenate(gr), np.concatenate(gi), np.concatenate(md), np.concatenate(ps),
-                    name=name, texcoord0=np.concatenate(uvs), bvh_nodes=np.concatenate(bv))
+                    name=name, texcoord0=np.concatenate(uvs), bvh_nodes=np.concatenate(bv),
+                    normals=np.concatenate([a.normals for a in prims]) if attributes else None,
+                    tangents=np.concatenate([a.tangents for a in prims]) if attributes else None)
     scene.local_to_world = np.ascontiguousarray(np.stack([np.asarray(m).T.reshape(16) for m in local_to_world]), dtype=np.float64)
     scene.built = prims
     return scene
 
 
-def built_mesh_scene(width=640, height=360, n=96):
+def built_mesh_scene(width=640, height=360, n=96, attributes=False):
     """Meshes that went through chordvis_nanite_build instead of the grid-patch generator: instances of a bumpy sphere from
-    3 m to 400 m so that every LOD level of the DAG is in use."""
+    3 m to 400 m so that every LOD level of the DAG is in use.  attributes: with normals and tangents (mesh_attributes)."""
     dists = [3.0, 6.0, 14.0, 30.0, 70.0, 160.0, 400.0]
     l2w = [translate(((k % 3) - 1) * 0.3 * dist, 0.08 * dist * ((k // 3) - 1), -dist) @ rotate_y(0.7 * k) @ scale(1.0 + 0.15 * k) for k, dist in enumerate(dists)]
-    scene = scene_from_meshes([bumpy_sphere_mesh(n, seed) for seed in (1, 2)], l2w, two_sided_of_object=(np.arange(len(l2w)) // 2) % 2, name="built_mesh_scene")
+    scene = scene_from_meshes([bumpy_sphere_mesh(n, seed) for seed in (1, 2)], l2w, two_sided_of_object=(np.arange(len(l2w)) // 2) % 2, name="built_mesh_scene",
+                              attributes=attributes)
     return scene, Camera((0.0, 0.4, 1.0), (0.0, -0.05, -1.0), width, height)
 
 

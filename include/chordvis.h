@@ -183,6 +183,11 @@ int chordvis_object_basic_data_batch(uint32_t count, const double* localToWorld 
 typedef struct ChordBuiltAsset ChordBuiltAsset;
 int chordvis_nanite_build(const float* positions, uint32_t vertexCount, const uint32_t* indices, uint32_t indexCount,
                           const float* texcoord0, ChordBuiltAsset** outAsset);
+/* The same build carrying per-vertex normals (float3) and tangents (float4, w = handedness) along: the simplifier collapses onto
+ * existing vertices, so every LOD's vertices are input vertex ids and the attributes ride along by id.  Meshlets, groups, BVH and
+ * meshlet data are byte for byte chordvis_nanite_build's for the same mesh.  normals / tangents may be NULL. */
+int chordvis_nanite_build_attributes(const float* positions, uint32_t vertexCount, const uint32_t* indices, uint32_t indexCount,
+                                     const float* texcoord0, const float* normals, const float* tangents, ChordBuiltAsset** outAsset);
 /* bounds + normal cone of ONE meshlet as the builder computes them (posMin/posMax, coneAxis, coneCutOff, coneApex of `out`;
  * the reference: meshopt_computeMeshletBounds, nanite_builder.cpp:476-486).  positions: the meshlet's own <= 255 vertices;
  * localTriangles: 3 indices into them per triangle (<= 128 triangles). */
@@ -190,13 +195,15 @@ int chordvis_meshlet_bounds(const float* positions, uint32_t vertexCount, const 
 /* views into the built arrays (valid until chordvis_free_built_asset): one ChordAssetDesc holding one primitive */
 int chordvis_built_asset_desc(const ChordBuiltAsset* asset, ChordAssetDesc* outAsset, ChordPrimitive* outPrimitive, uint32_t* outLodCount);
 void chordvis_free_built_asset(ChordBuiltAsset* asset);
-/* a flat container for a built asset (the reference: cereal + LZ4 archives, serialize.h:217-320) */
+/* a flat container for a built asset (the reference: cereal + LZ4 archives, serialize.h:217-320): layout CHRDAS01, or CHRDAS02
+ * (two more counts and the normal / tangent streams) when the asset has normals or tangents; both are read */
 int chordvis_save_asset(const ChordBuiltAsset* asset, const char* path);
 int chordvis_load_asset(const char* path, ChordBuiltAsset** outAsset);
 /* The reference's own container for an asset's geometry: the GLTFBinary archive (asset_gltf.h:260-300) as saveAsset / loadAsset
  * write and read it (serialize.h:217-320: cereal binary archive, LZ4 block compression when lz4 != 0).  Load yields ONE
- * primitive spanning the file (the per-primitive offsets live in the reference's GLTFAsset, another archive); attributes
- * this path does not read (normals, tangents, ...) are skipped on load and written empty. */
+ * primitive spanning the file (the per-primitive offsets live in the reference's GLTFAsset, another archive).  Positions,
+ * normals, texcoords0, tangents and the Nanite data are read and written; the attributes this path does not use (smooth
+ * normals, second uv set, colours, LOD-0 indices) are skipped on load and written empty. */
 int chordvis_save_gltf_binary(const ChordBuiltAsset* asset, const char* path, int lz4);
 int chordvis_load_gltf_binary(const char* path, ChordBuiltAsset** outAsset);
 
@@ -528,6 +535,30 @@ typedef struct ChordResolveTargets {
  * desc NULL: all zero. */
 int chordvis_resolve_attributes(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
                                 const ChordResolveTargets* targets);
+/* The surface frame of the visible triangle -- getTriangleMiscInfo (nanite_shared.hlsli:157-175) and
+ * loadGLTFMetallicRoughnessPBRMaterial (material.hlsli:95-108).  Per vertex, float32, every step in source order:
+ *   nRS = normalize(mul(float4(nLS, 0), translatedWorldToLocal).xyz)   row-vector product (the inverse transpose), component j
+ *                                                                      = (x * m0j + y * m1j) + z * m2j (the w = 0 term dropped)
+ *   t   = mul(localToTranslatedWorld, float4(tLS.xyz, 0)).xyz          component i = (mi0 * x + mi1 * y) + mi2 * z
+ *   tRS = normalize(t - dot(t, nRS) * nRS)                             (Gram-Schmidt)
+ *   bRS = cross(nRS, tRS) * tLS.w
+ * normalize(v) = v / sqrt(dot(v, v)), dot = (x * x + y * y) + z * z, each component divided separately.  Departure: a vector
+ * whose dot(v, v) is not above 0 normalises to 0, not NaN (a G-buffer carries no NaN).  Per pixel each is interpolated with the
+ * barycentrics, (a0 * b.x + a1 * b.y) + a2 * b.z, NOT renormalised (material.hlsli:98-99).  The reference forms tangents only
+ * for materials with a normal texture; here they are formed whenever the scene has tangents.  Caller-owned device images as in
+ * ChordResolveTargets; empty pixels hold 0. */
+typedef struct ChordSurfaceTargets {
+    float* vertexNormal; /* float4: xyz, 0 */
+    float* tangent;      /* float4: xyz, 0 */
+    float* bitangent;    /* float4: xyz, 0 */
+    float* pad;          /* must be NULL   */
+} ChordSurfaceTargets;
+/* chordvis_resolve_attributes plus the surface images, any subset of the eleven in ONE launch, under the same preconditions and
+ * refusals; targets may be NULL.  CHORDVIS_E_INVALID also when a vertexNormal target is asked of a scene uploaded without
+ * normals, or a tangent / bitangent target of one without tangents or without normals (Gram-Schmidt needs both).  Assets of a
+ * scene without a stream read it as 0. */
+int chordvis_resolve_surface(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
+                             const ChordResolveTargets* targets, const ChordSurfaceTargets* surface);
 /* The hipStream_t the context enqueues on (the one given to chordvis_create, or its own): a host that allocates targets on a
  * stream of its own orders the two against each other. */
 void* chordvis_stream(ChordCtx* ctx);

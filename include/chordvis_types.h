@@ -234,6 +234,10 @@ typedef struct ChordAssetDesc {
                                                                               * masked materials then sample at uv (0, 0) */
     const ChordBVHNode*      bvhNodes;           uint32_t bvhNodeCount;      /* bvhNodeBuffer, or NULL / 0 (flat culling only);
                                                                               * primitive p's tree starts at bvhNodeOffset */
+    const float*             normals;            uint32_t normalCount;       /* float3 per vertex (normalBuffer), or NULL / 0 */
+    const float*             tangents;           uint32_t tangentCount;      /* float4 per vertex (tangentBuffer: xyz, handedness
+                                                                              * w = +-1), or NULL / 0.  Read only by
+                                                                              * chordvis_resolve_surface */
 } ChordAssetDesc;
 
 typedef struct ChordSceneDesc {
