@@ -981,3 +981,294 @@ def stacked_layers(variant="large", width=320, height=192, layers=None, per_obje
         pb.add_surface(plane_surface((x0, y0, -zb), (-2.0 * x0, 0.0, 0.0), (0.0, -2.0 * y0, 0.0)), 1, 1)
         sb.add_object(sb.add_primitive(pb), material=mat)
     return sb.build(), cam
+
+
+# ------------------------------------------------------------------ general transforms and motion ---
+
+def rotate_x(a):
+    c, s = math.cos(a), math.sin(a)
+    m = np.eye(4)
+    m[1, 1], m[1, 2], m[2, 1], m[2, 2] = c, -s, s, c
+    return m
+
+
+def rotate_z(a):
+    c, s = math.cos(a), math.sin(a)
+    m = np.eye(4)
+    m[0, 0], m[0, 1], m[1, 0], m[1, 1] = c, -s, s, c
+    return m
+
+
+def rotate_axis(axis, a):
+    """Rotation by `a` about an arbitrary axis (Rodrigues)."""
+    k = np.asarray(axis, dtype=np.float64)
+    k = k / np.linalg.norm(k)
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    m = np.eye(4)
+    m[:3, :3] = np.eye(3) + math.sin(a) * K + (1.0 - math.cos(a)) * (K @ K)
+    return m
+
+
+# classes of general_transform_scene's objects (Scene.transform_class)
+TILTED, STRETCHED, MIRRORED, SIZED = 0, 1, 2, 3
+
+
+def _moving(scene, at):
+    """Gives a built scene its motion: at(t) -> list of 4x4 local-to-world matrices; t = 1 is the scene's own frame, t = 0 the one
+    before it.  Scene.local_to_world_at(t) has Scene.local_to_world's layout (glm column-major doubles)."""
+    scene.local_to_world_at = lambda t: np.ascontiguousarray(np.stack([np.asarray(m).T.reshape(16) for m in at(float(t))]), dtype=np.float64)
+    scene.local_to_world = scene.local_to_world_at(1.0)
+    return scene.local_to_world_at(0.0)
+
+
+def _camera_basis(position, front, world_up=(0.0, 1.0, 0.0)):
+    f = np.asarray(front, dtype=np.float64); f = f / np.linalg.norm(f)
+    r = np.cross(f, np.asarray(world_up, dtype=np.float64)); r = r / np.linalg.norm(r)
+    return np.asarray(position, dtype=np.float64), f, r, np.cross(r, f)
+
+
+def general_transform_scene(width=640, height=360, seed=11, masked=False, attributes=False, lods=3,
+                            position=(-7.0, 1.6, 6.5), front=(0.8, -0.12, -0.6), world_up=(0.22, 1.0, 0.13)):
+    """The primitives of small_test_scene / masked_test_scene under general object transforms, in motion.  Returns (scene, camera,
+    local_to_world_last); the scene also carries transform_class (one of TILTED, STRETCHED, MIRRORED, SIZED per object), motion (a
+    word per object) and local_to_world_at(t) (t = 1: the scene's frame, 0: the frame before, 2, 3 ..: the motion continued).
+
+    Classes cycle over the objects so that each occurs several times with single- and two-sided materials:
+      TILTED     rotations about x, y and z composed, uniform scale;
+      STRETCHED  R1 @ scale(sx, sy, sz) @ R2 with one factor below 1 and one above 2: sheared relative to the mesh axes;
+      MIRRORED   one of the two above with one axis negated (determinant < 0);
+      SIZED      instances of one building from large and near to small and far (the LOD cut picks different levels).
+    Motion: "spin" rotates in place, "slide" translates across the view, "rescale" changes scale, "reveal" starts behind the wall (a
+    large occluder in front of the camera) and ends beside it, "hide" does the reverse, "enter" comes into the frustum from outside,
+    "still" does not move.  masked: alpha-tested materials on every class and a masked quad that crosses the near plane."""
+    sb = SceneBuilder("general_transform_scene" + ("_masked" if masked else ""), attributes)
+    P, f, r, u = _camera_basis(position, front, world_up)
+    if masked:
+        tex = [sb.add_texture(t) for t in _alpha_textures(seed)]
+        smp = [sb.add_sampler(T.FILTER_LINEAR_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_REPEAT),
+               sb.add_sampler(T.FILTER_NEAREST, T.FILTER_NEAREST, T.WRAP_CLAMP_TO_EDGE, T.WRAP_MIRRORED_REPEAT)]
+        one = [sb.add_material(0, T.ALPHA_MASK, tex[0], smp[0], 0.5, 1.0), 0]
+        two = [sb.add_material(1, T.ALPHA_MASK, tex[1], smp[1], 0.4, 0.9), sb.add_material(1, T.ALPHA_MASK, tex[2], smp[0], 0.35, 1.0)]
+    else:
+        one, two = [0], [sb.add_material(1)]
+    objs = []                                   # (prim, material, class, motion word, at(t) -> 4x4)
+
+    def rnd(k, n=12):
+        return rand01(seed + 1, np.arange(k * n, k * n + n))
+
+    def tilt(q, t=0.0):
+        return rotate_y(q[0] * 6.0 + t) @ rotate_x((q[1] - 0.5) * 1.2 + 0.35) @ rotate_z((q[2] - 0.5) * 1.2 + 0.3)
+
+    def general(cls, q, mirror_axis=0):
+        """t -> the 4x4 without its translation, for a class and 12 random numbers"""
+        if cls == TILTED:
+            return lambda t, spin=0.0, grow=0.0: tilt(q, spin * t) @ scale((0.8 + 0.6 * q[3]) * (1.0 + grow * t))
+        s3 = (0.4 + 0.25 * q[3], 2.1 + 0.4 * q[4], 1.0 + 0.3 * q[5])
+        s3 = tuple(np.roll(s3, int(q[6] * 3)))
+        R2 = rotate_z(0.4 + q[7]) @ rotate_x(0.3 + q[8])
+        if cls == STRETCHED:
+            return lambda t, spin=0.0, grow=0.0: tilt(q, spin * t) @ scale(*s3) @ scale(1.0 + grow * t) @ R2
+        flip = np.ones(3); flip[mirror_axis] = -1.0
+        base = general(TILTED if q[9] < 0.5 else STRETCHED, q)
+        return lambda t, spin=0.0, grow=0.0: base(t, spin, grow) @ scale(*flip)
+
+    # the ground, tilted a little (class TILTED, still)
+    pb = PrimitiveBuilder(sb.attributes)
+    pb.add_surface(plane_surface((-8, 0, 8), (16, 0, 0), (0, 0, -16), seed, 0.2, 0.7), 8, 8, min(lods, 3))
+    g = translate(0.0, -0.4, 0.0) @ rotate_y(0.5) @ rotate_x(0.06) @ rotate_z(-0.05)
+    objs.append((sb.add_primitive(pb), 0, TILTED, "still", lambda t, g=g: g))
+    # one building shared by the SIZED objects
+    pb = PrimitiveBuilder(sb.attributes)
+    if masked:
+        pb.uv_scale = (2.0, 3.0)
+    _building(pb, 2.0, 1.6, 2.4, seed * 100 + 900, min(lods, 3))
+    sized_prim = sb.add_primitive(pb)
+    motions = ["spin", "slide", "rescale", "still"]
+    n_cycle = 16
+    for k in range(n_cycle):
+        q = rnd(k)
+        cls = k % 4
+        two_sided = (k // 4) % 2 == 1
+        mat = (two if two_sided else one)[(k // 8) % len(two if two_sided else one)]
+        if cls == SIZED:
+            prim = sized_prim
+            j = k // 4                                               # 0 .. 3: near and large -> far and small
+            dist, size = (4.5, 8.0, 16.0, 34.0)[j], (0.45, 0.6, 0.45, 0.25)[j]
+            centre = P + dist * f + ((j % 2) * 2 - 1) * 0.25 * dist * r - 0.2 * dist * u
+            base = lambda t, spin=0.0, grow=0.0, q=q, size=size: tilt(q, spin * t) @ scale(size * (1.0 + grow * t))
+        else:
+            pb = PrimitiveBuilder(sb.attributes)
+            if masked:
+                pb.uv_scale = (1.0 + 3.0 * q[10], 0.5 + 2.5 * q[11]) if k % 3 else (-2.0, 3.0)
+            if (k + k // 4) % 2 == 0:
+                _building(pb, 1.5 + q[3], 1.5 + q[4], 1.0 + 2.5 * q[5], seed * 100 + k * 8, min(lods, 3))
+            else:
+                pb.add_surface(cylinder_surface((0, 0, 0), 0.3 + 0.4 * q[3], 1.0 + 2.0 * q[4], seed * 100 + k, 0.03), 4, 4, lods)
+            prim = sb.add_primitive(pb)
+            centre = P + (5.0 + 9.0 * q[10]) * f + (q[11] - 0.5) * 7.0 * r - (0.6 + 0.8 * q[9]) * u
+            base = general(cls, q, mirror_axis=k % 3)
+        word = motions[(k // 4 + k) % 4]
+        d = {"spin": dict(spin=0.35), "rescale": dict(grow=0.3)}.get(word, {})
+        v = (1.2 * r + 0.3 * f) if word == "slide" else np.zeros(3)
+        objs.append((prim, mat, cls, word, lambda t, c=centre, v=v, base=base, d=d: translate(*(c + (t - 1.0) * v)) @ base(t, **d)))
+    # the wall: a large occluder 4 m in front of the camera, right of the view's centre (single-sided, facing the camera; TILTED by
+    # construction: its plane follows the rolled camera)
+    pb = PrimitiveBuilder(sb.attributes)
+    pb.add_surface(plane_surface((0, 0, 0), (1, 0, 0), (0, 1, 0), seed + 3, 0.0, 1.0), 4, 4, 1)
+    wall = np.eye(4)
+    wall[:3, 0], wall[:3, 1], wall[:3, 2] = 2.2 * r, 1.7 * u, -f
+    wall[:3, 3] = P + 4.0 * f + 0.5 * r - 0.6 * u
+    objs.append((sb.add_primitive(pb), 0, TILTED, "still", lambda t, w=wall: w))
+    # behind it, 7 .. 8 m out: one object of each general class comes out from behind the wall, one of each goes in, one of each
+    # enters the frustum from the left
+    for j, (word, cls) in enumerate([(w_, c_) for w_ in ("reveal", "hide", "enter") for c_ in (TILTED, STRETCHED, MIRRORED)]):
+        q = rnd(100 + j)
+        pb = PrimitiveBuilder(sb.attributes)
+        if masked:
+            pb.uv_scale = (2.0, 2.0)
+        pb.add_surface(cylinder_surface((0, -0.5, 0), 0.35, 1.0, seed * 100 + 500 + j, 0.03), 4, 4, lods)
+        prim = sb.add_primitive(pb)
+        base = general(cls, q, mirror_axis=j % 3)
+        dist = 7.0 + 0.35 * (j % 3)
+        row = (((j % 3) - 1) * 0.7 + 0.4) * u
+        half = dist * math.tan(math.radians(22.5)) * width / height
+        if word == "reveal":
+            c0, c1 = P + dist * f + 2.8 * r + row, P + dist * f - 1.6 * r + row
+        elif word == "hide":
+            c0, c1 = P + (dist + 1.0) * f - 2.4 * r + row, P + (dist + 1.0) * f + 3.0 * r + row
+        else:                                                        # (the mirrored one is a frame late: still outside at t = 1)
+            c0 = P + dist * f - (half + (4.5 if cls == MIRRORED else 2.5)) * r + row
+            c1 = c0 + (2.6 if cls == MIRRORED else 3.7) * r
+        mat = (two if j % 2 else one)[0]
+        objs.append((prim, mat, cls, word, lambda t, c0=c0, c1=c1, base=base: translate(*(c0 + t * (c1 - c0))) @ base(t, spin=0.2)))
+    # two single-sided panels whose surface normal points at the camera, one stretched, one stretched and mirrored: the mirrored
+    # one has every triangle wound the other way on screen and loses them all to the back-face rule (mesh_raster.cpp:235)
+    pb = PrimitiveBuilder(sb.attributes)
+    if masked:
+        pb.uv_scale = (2.0, 1.0)
+    pb.add_surface(plane_surface((-0.5, -0.5, 0), (1, 0, 0), (0, 1, 0), seed + 4, 0.03, 5.0), 2, 2, 1)
+    panel = sb.add_primitive(pb)
+    for sign, cls, c in ((1.0, STRETCHED, P + 5.0 * f - 2.6 * r + 1.25 * u), (-1.0, MIRRORED, P + 5.2 * f - 0.3 * r + 1.3 * u)):
+        m = np.eye(4)
+        m[:3, 0], m[:3, 1], m[:3, 2], m[:3, 3] = sign * 2.1 * r, 0.55 * u, -f, c
+        objs.append((panel, one[0], cls, "spin", lambda t, m=m: m @ rotate_z(0.25 * (t - 1.0))))
+    # a two-sided strip that passes left of and below the camera, from 2 m behind it to 2 m ahead, stretched, sheared and mirrored: its
+    # triangles cross the near plane and (masked: with their texture coordinates) go through the clipper under a general matrix
+    pb = PrimitiveBuilder(sb.attributes)
+    pb.uv_scale = (3.0, 2.0)
+    pb.add_surface(plane_surface((-0.5, -0.5, 0), (1, 0, 0), (0, 1, 0), seed + 5, 0.0, 1.0), 1, 1, 1)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2] = 4.0 * (f + 0.05 * u + 0.03 * r), 0.3 * (r + 0.2 * f + 0.1 * u), u + 0.1 * r - 0.15 * f
+    m[:3, 3] = P + 0.3 * f - 0.05 * r - 0.12 * u
+    objs.append((sb.add_primitive(pb), two[0], MIRRORED, "still", lambda t, m=m: m))
+    for prim, mat, cls, word, at in objs:
+        sb.add_object(prim, at(1.0), material=mat)
+    scene = sb.build()
+    scene.transform_class = np.array([o[2] for o in objs])
+    scene.motion = [o[3] for o in objs]
+    last = _moving(scene, lambda t: [o[4](t) for o in objs])
+    return scene, Camera(position, front, width, height, world_up=world_up, jitter=(0.3, -0.2)), last
+
+
+def general_cameras(cam, steps=4):
+    """Views of a sequence that starts at `cam`: the camera turns (front changes) and moves between consecutive views, its world_up
+    is rolled out of the plane of front and +y, and fovy (45, 52, 100, 20 degrees), z_near and jitter change from view to view."""
+    P, f, r, u = _camera_basis(cam.position, cam.front, cam.world_up)
+    out = [cam]
+    spec = [(52.0, 0.05, (-0.25, 0.4), 0.06, (0.1, 0.02, -0.05), (0.3, 1.0, -0.1)),
+            (100.0, 0.01, (0.45, 0.1), -0.05, (0.05, 0.05, 0.1), (-0.25, 1.0, -0.15)),
+            (20.0, 0.2, (-0.4, -0.35), 0.04, (-0.1, 0.0, 0.05), (0.15, 1.0, 0.3))]
+    for k in range(1, steps):
+        fov, zn, jit, turn, move, up = spec[(k - 1) % len(spec)]
+        f = f + turn * r + 0.3 * turn * u
+        f = f / np.linalg.norm(f)
+        P = P + np.asarray(move)
+        out.append(Camera(tuple(P), tuple(f), cam.width, cam.height, math.radians(fov), zn, cam.z_far, up, jit))
+    return out
+
+
+def config3_street_general(width=3840, height=2160, lods=3, share_mirrored=4):
+    """config3_street's geometry (_street_primitives) with every building tilted by a few degrees and stretched non-uniformly, every
+    share_mirrored-th building and prop mirrored, and every seventh prop moving along the street.  Returns (scene, camera,
+    local_to_world_last) like general_transform_scene; the camera is config3_street's, rolled."""
+    sb = SceneBuilder("config3_street_general")
+    ats = []
+    for k, (prim, l2w) in enumerate(_street_primitives(sb, lods)):
+        q = rand01(3777, np.arange(k * 8, k * 8 + 8))
+        if k == 0:
+            m = l2w @ rotate_y(0.02) @ rotate_x(0.004) @ rotate_z(-0.003)
+        else:
+            tilt = rotate_x((q[0] - 0.5) * 0.14 + 0.03) @ rotate_z((q[1] - 0.5) * 0.14 - 0.03) @ rotate_y(0.1 + q[2])
+            s3 = np.roll((0.75 + 0.2 * q[3], 1.0 + 0.2 * q[4], 1.25 + 0.25 * q[5]), k % 3)
+            if k % share_mirrored == 0:
+                s3[k % 2 * 2] *= -1.0
+            m = l2w @ tilt @ scale(*s3) @ rotate_y(-(0.1 + q[2]))
+        v = np.array([2.5 * (q[6] - 0.3), 0.0, 0.4 * (q[7] - 0.5)]) if (k > 40 and k % 7 == 0) else None
+        sb.add_object(prim, m)
+        ats.append((lambda t, m=m: m) if v is None else (lambda t, m=m, v=v: translate(*((t - 1.0) * v)) @ m @ rotate_y(0.3 * (t - 1.0))))
+    scene = sb.build()
+    last = _moving(scene, lambda t: [a(t) for a in ats])
+    return scene, Camera((-62.0, 12.0, 3.0), (1.0, -0.18, -0.04), width, height, world_up=(0.1, 1.0, -0.06)), last
+
+
+def general_long_scene(groups=512 * 256 + 64 * 5 + 7, width=640, height=360, shown=64, seed=2):
+    """group_count_scene's construction (more than 65 536 group instances and more than 512 count blocks of 256 at the default) under
+    general transforms: the shown objects are tilted, stretched or mirrored in turn and move between the frames; the others are
+    behind the camera, general as well.  Returns (scene, camera, local_to_world_last)."""
+    sb = SceneBuilder("general_long_%d" % groups)
+    pb = PrimitiveBuilder()
+    pb.add_surface(plane_surface((-0.5, -0.5, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), seed, 0.05, 2.0), 16, 16, 1)
+    panel = sb.add_primitive(pb)
+    pb = PrimitiveBuilder()
+    pb.add_surface(plane_surface((-0.5, -0.5, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), seed + 1, 0.08, 1.5), 2, 2, 1)
+    tile = sb.add_primitive(pb)
+    two = sb.add_material(1)
+    prims = [panel] * (groups // 64) + [tile] * (groups % 64)
+    n = len(prims)
+    picked = set(np.linspace(0, n - 1, min(n, shown)).round().astype(np.int64).tolist())
+    hidden = rotate_x(0.3) @ rotate_y(0.4) @ rotate_z(0.2) @ scale(0.8, 1.1, 0.9)
+    ats, j = [], 0
+    for k, prim in enumerate(prims):
+        if k in picked:
+            col, row, layer = j % 8, (j // 8) % 4, (j // 32) % 3
+            q = rand01(seed + 7, np.arange(6 * j, 6 * j + 6))
+            c = np.array([col - 3.5 + 0.5 * layer, row - 1.5 + 0.3 * layer, -1.2 * layer - 0.2 * q[0]])
+            s3 = np.roll((0.6, 1.0, 1.3), j % 3) * (1.0, 1.0, 1.0)
+            if j % 3 == 2:
+                s3[j % 2] *= -1.0
+            R = rotate_y((q[1] - 0.5) * 0.8 + 0.15) @ rotate_x((q[2] - 0.5) * 0.6 + 0.1) @ rotate_z((q[3] - 0.5) * 0.6 - 0.1)
+            R2 = rotate_z(0.2 + 0.3 * q[4])
+            v = np.array([0.6 * (q[5] - 0.5), 0.2 * (q[4] - 0.5), 0.5 * (q[3] - 0.5)]) if j % 2 else np.zeros(3)
+            ats.append(lambda t, c=c, v=v, R=R, s3=s3, R2=R2, sp=0.2 * (j % 4): translate(*(c + (t - 1.0) * v)) @ rotate_y(sp * (t - 1.0)) @ R @ scale(*s3) @ R2)
+            mat = two if j % 4 == 1 else 0
+            j += 1
+        else:
+            m = translate((k % 37) * 0.5, (k % 11) * 0.5, 40.0 + (k % 5)) @ hidden @ scale(-1.0 if k % 3 == 0 else 1.0, 1.0, 1.0)
+            ats.append(lambda t, m=m: m)
+            mat = 0
+        sb.add_object(prim, ats[-1](1.0), material=mat)
+    scene = sb.build()
+    assert scene.group_instances == groups
+    last = _moving(scene, lambda t: [a(t) for a in ats])
+    return scene, Camera((0.0, 0.0, 6.0), (0.02, -0.01, -1.0), width, height, world_up=(0.2, 1.0, 0.0)), last
+
+
+def unit_depth_scene(width=320, height=180):
+    """A perspective camera at the origin looking down -z and objects whose origin lies at view depth exactly 1: the float32 product
+    translatedWorldToClip * localToTranslatedWorld has [3][3] == 1.0f.  isOrthoProjection (base.hlsli:243-246) is asked about that
+    PRODUCT (instance_culling.hlsl:71-89: isOrthoProjection(localToClip)), so the shader takes orthoFrustumCulling for these
+    objects, for their meshlets and in the LOD cut -- the branch the text implies, and the one oracle, spec and kernels must share."""
+    sb = SceneBuilder("unit_depth")
+    two = sb.add_material(1)
+    for k in range(6):
+        pb = PrimitiveBuilder()
+        pb.add_surface(cylinder_surface((0, -0.4, 0), 0.25, 0.8, 40 + k, 0.03), 4, 4, 2)
+        R3 = rotate_y(0.4 + k) @ rotate_x(0.3 + 0.2 * k) @ rotate_z(0.2 - 0.3 * k) @ scale(0.5, 1.3, 0.8 if k % 2 else -0.8)
+        x = (-0.9, -0.3, 0.3, 0.9, -4.5, 1.3)[k]
+        if k == 4:      # large, left of the view, reaching behind the camera: every corner is behind the left plane, but the corners
+            R3 = R3 @ scale(4.0)   # with w < 0 project across the screen -- the plane test culls it, the projected rectangle does not
+        sb.add_object(sb.add_primitive(pb), translate(x, 0.1 * (k % 3) - 0.1, -1.0) @ R3, material=two if k % 3 == 0 else 0)
+    pb = PrimitiveBuilder()
+    pb.add_surface(plane_surface((-3, -2, -4), (6, 0, 0), (0, 4, 0), 50, 0.1, 1.0), 4, 4, 1)
+    sb.add_object(sb.add_primitive(pb))
+    return sb.build(), Camera((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), width, height)

@@ -211,3 +211,28 @@ def sharded_frame(ctxs, sharded_cull=True):
     sharded_gather(ctxs, [r.visibility_ptr() for r in ctxs], ctxs[0].visibility_chunk_words() * 8)
     for r in ctxs:
         r.frame_phase_c()
+
+
+# ---- moving scenes (scenes.general_transform_scene and its kin): objects at local_to_world_at(k) under cams[k] in frame k ----
+
+def moving_frame(scene, cams, k, prev_view=None):
+    """Fills the object records for frame k of a moving sequence (this frame's transforms and camera, and the frame before's for
+    the last-frame matrices; frame 0 has no frame before) and returns (view, iv).  prev_view: frame k - 1's view record.
+    Side effect: scene.local_to_world is left at frame k's transforms (and scene.objects filled for frame k), so whoever sets the
+    same scene object up afterwards starts from that frame, not from the builder's."""
+    from chord_amd import lib as L
+    scene.local_to_world = scene.local_to_world_at(k)
+    L.fill_objects(scene, cams[k], cams[k - 1] if k else None, scene.local_to_world_at(k - 1) if k else None)
+    return L.make_views(cams[k], prev_view)
+
+
+def moving_sequence(scene, cams, flags=ALL_FLAGS, frames=None):
+    """Generator over the frames of a moving sequence: yields (k, view, iv, want) with the object records filled for frame k and
+    want = the oracle's frame against the oracle's chain of frame k - 1."""
+    import orc
+    prev_view, prev_hzb = None, None
+    for k in range(len(cams) if frames is None else frames):
+        view, iv = moving_frame(scene, cams, k, prev_view)
+        want = orc.frame(scene, view, iv, flags, prev_hzb_min=prev_hzb)
+        yield k, view, iv, want
+        prev_view, prev_hzb = view, want["hzb_min"]
