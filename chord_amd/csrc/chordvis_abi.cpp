@@ -11,6 +11,7 @@
 // command buffer); counts never come back to the CPU inside a frame.
 
 #include "device_layer.h"
+#include "material_tables.h"
 
 #include <algorithm>
 #include <cmath>
@@ -409,10 +410,11 @@ int chordvis_destroy(ChordCtx* c)
         c->dPrims = nullptr; c->dGroups = nullptr; c->dMeshlets = nullptr; c->dGroupIndices = nullptr; c->dMeshletData = nullptr;
         c->dPositions = nullptr; c->dObjStatic = nullptr; c->dGroupRefs = nullptr; c->dMaterials = nullptr; c->dTexAlpha = nullptr;
         c->dTexcoords = nullptr; c->dBvhNodes = nullptr; c->dMeshletLod = nullptr; c->dNormals = nullptr; c->dTangents = nullptr;
+        c->dMatRecords = nullptr; c->dMatTexels = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -775,6 +777,8 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     if (!tng.empty()) { UP(c->dTangents, tng) } else dfree(c->dTangents);
 #undef UP
     c->instTriangles = instTriangles;
+    dfree(c->dMatRecords); dfree(c->dMatTexels);                           // (chordvis_upload_material_textures is per scene upload)
+    c->matTexturesLoaded = false; c->matAnyNormalTexture = false;
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }       // (it aliased the old scene buffers)
     if ((rc = chord::alloc_scene_work_buffers(c))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dObjectsOwned, s->objects, sizeof(ChordObject) * s->objectCount, hipMemcpyHostToDevice));
@@ -785,6 +789,103 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     c->pendingTailSlot = 0;
     if ((rc = chord::prepare_cull_exchange(c))) { c->sceneLoaded = false; return rc; }     // (a sharded context: the rank-mask exchange buffer of this scene)
     if (c->cullMode == 1 && !c->bvhComplete) return fail(c, CHORDVIS_E_INVALID, "upload_scene: hierarchical culling is selected and a primitive has no BVH");
+    return CHORDVIS_OK;
+}
+
+// The RGBA texels and material records chordvis_resolve_material samples.  Nothing of the scene upload
+// is touched: dTexAlpha / DMaterial stay what the raster reads.
+int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
+{
+    if (!c || !s) return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: null argument");
+    if (c->sharedScene) return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: not on a depth-view context");
+    if (!c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: no scene (call chordvis_upload_scene first)");
+    if (!s->materials || s->materialCount != c->materialCount)
+        return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: the descriptor's materialCount differs from the uploaded scene's");
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));                         // (a resolve in flight may read the records being replaced)
+    dfree(c->dMatRecords); dfree(c->dMatTexels);
+    c->matTexturesLoaded = false; c->matAnyNormalTexture = false;
+
+    const uint32_t nTex = s->textures ? s->textureCount : 0u;
+    std::vector<uint8_t> named(nTex, 0);
+    auto slot_ids = [](const ChordMaterial& m, uint32_t tex[4], uint32_t smp[4]) {
+        tex[CHORD_MATSLOT_BASECOLOR] = m.baseColorId; smp[CHORD_MATSLOT_BASECOLOR] = m.baseColorSampler;
+        tex[CHORD_MATSLOT_EMISSIVE] = m.emissiveTexture; smp[CHORD_MATSLOT_EMISSIVE] = m.emissiveSampler;
+        tex[CHORD_MATSLOT_NORMAL] = m.normalTexture; smp[CHORD_MATSLOT_NORMAL] = m.normalSampler;
+        tex[CHORD_MATSLOT_METALROUGH] = m.metallicRoughnessTexture; smp[CHORD_MATSLOT_METALROUGH] = m.metallicRoughnessSampler;
+    };
+    uint32_t tex[4], smp[4];
+    for (uint32_t m = 0; m < s->materialCount; m++) {
+        slot_ids(s->materials[m], tex, smp);
+        for (int k = 0; k < 4; k++) if (tex[k] < nTex) named[tex[k]] = 1;
+    }
+    std::vector<uint32_t> texels;
+    std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu);
+    for (uint32_t t = 0; t < nTex; t++) {
+        if (!named[t]) continue;
+        const ChordTexture& tx = s->textures[t];
+        if (!tx.rgba8 || tx.width == 0 || tx.height == 0 || tx.mipCount == 0 || tx.width > 16384u || tx.height > 16384u || tx.mipCount > CHORD_MAX_TEX_LEVELS)
+            return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
+        size_t count = 0;
+        for (uint32_t l = 0; l < tx.mipCount; l++) count += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
+        if (texels.size() + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
+        texBase[t] = (uint32_t)texels.size();
+        const size_t base = texels.size();
+        texels.resize(base + count);
+        std::memcpy(texels.data() + base, tx.rgba8, count * 4);            // (little-endian: R is the low byte of the word)
+    }
+    auto wrap_consts = [](uint32_t n, uint32_t mode, uint32_t& magic, uint32_t& bias) {   // (DMatLevel; as chordvis_upload_scene's)
+        magic = 0u; bias = 0u;
+        if (mode == CHORD_WRAP_CLAMP_TO_EDGE) return;
+        const uint32_t period = mode == CHORD_WRAP_MIRRORED_REPEAT ? 2u * n : n;
+        if ((period & (period - 1u)) == 0u) return;
+        magic = (uint32_t)(0x100000000ull / period);
+        bias = (uint32_t)(((0x40000000ull + period - 1u) / period) * period);
+    };
+    auto linear = [](uint32_t f) { return f == CHORD_FILTER_LINEAR || f == CHORD_FILTER_LINEAR_MIPMAP_NEAREST || f == CHORD_FILTER_LINEAR_MIPMAP_LINEAR; };
+    std::vector<chord::DMatRecord> recs(s->materialCount);
+    bool anyNormal = false;
+    for (uint32_t m = 0; m < s->materialCount; m++) {
+        const ChordMaterial& mat = s->materials[m];
+        chord::DMatRecord& d = recs[m];
+        std::memset(&d, 0, sizeof(d));
+        std::memcpy(d.baseColorFactor, mat.baseColorFactor, 16); std::memcpy(d.emissiveFactor, mat.emissiveFactor, 12);
+        d.roughnessFactor = mat.roughnessFactor; d.metallicFactor = mat.metallicFactor; d.normalFactorScale = mat.normalFactorScale;
+        d.occlusionTextureStrength = mat.occlusionTextureStrength; d.bExistOcclusion = mat.bExistOcclusion != 0u;
+        d.pbr = mat.materialType == 1u;                                    // kLightingType_GLTF_MetallicRoughnessPBR, base.h:423
+        slot_ids(mat, tex, smp);
+        for (int k = 0; k < 4; k++) {
+            chord::DMatSlot& S = d.slot[k];
+            ChordSampler sm{CHORD_FILTER_NEAREST, CHORD_FILTER_NEAREST, CHORD_WRAP_REPEAT, CHORD_WRAP_REPEAT};
+            if (s->samplers && smp[k] < s->samplerCount) sm = s->samplers[smp[k]];
+            S.wrapS = sm.wrapS; S.wrapT = sm.wrapT;
+            S.filter = (linear(sm.magFilter) ? CHORD_MATSLOT_MAG_LINEAR : 0u) | (linear(sm.minFilter) ? CHORD_MATSLOT_MIN_LINEAR : 0u) |
+                       ((sm.minFilter == CHORD_FILTER_NEAREST_MIPMAP_NEAREST || sm.minFilter == CHORD_FILTER_LINEAR_MIPMAP_NEAREST) ? CHORD_MATSLOT_MIP_NEAREST : 0u) |
+                       ((sm.minFilter == CHORD_FILTER_NEAREST_MIPMAP_LINEAR || sm.minFilter == CHORD_FILTER_LINEAR_MIPMAP_LINEAR) ? CHORD_MATSLOT_MIP_LINEAR : 0u);
+            if (tex[k] >= nTex) continue;                                  // mips = 0: the slot's fallback
+            const ChordTexture& tx = s->textures[tex[k]];
+            S.mips = tx.mipCount;
+            uint32_t off = texBase[tex[k]];
+            for (uint32_t l = 0; l < tx.mipCount; l++) {
+                const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l);
+                chord::DMatLevel& L = S.levels[l];
+                L.base = off; L.dims = (w - 1u) | (h - 1u) << 16;
+                wrap_consts(w, S.wrapS, L.magicS, L.biasS);
+                wrap_consts(h, S.wrapT, L.magicT, L.biasT);
+                off += w * h;
+            }
+            if (k == (int)CHORD_MATSLOT_NORMAL) anyNormal = true;
+        }
+    }
+    int rc;
+    if ((rc = dalloc(c, &c->dMatRecords, recs.size()))) return rc;
+    CHORD_HIP(c, hipMemcpy(c->dMatRecords, recs.data(), recs.size() * sizeof(recs[0]), hipMemcpyHostToDevice));
+    if (!texels.empty()) {
+        if ((rc = dalloc(c, &c->dMatTexels, texels.size()))) { dfree(c->dMatRecords); return rc; }
+        hipError_t e = hipMemcpy(c->dMatTexels, texels.data(), texels.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { dfree(c->dMatRecords); dfree(c->dMatTexels); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
+    }
+    c->matTexturesLoaded = true; c->matAnyNormalTexture = anyNormal;
     return CHORDVIS_OK;
 }
 
@@ -1494,6 +1595,45 @@ int chordvis_resolve_surface(ChordCtx* c, ChordCountAndCmd drawed, const ChordRe
     if ((rc = resolve_source(c, drawed, &vis))) return rc;
     chord::launch_resolve_surface(c, vis, drawed.cmds, drawed.count, d, tt, ss);
     CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+// chordvis_resolve_surface's preconditions and refusals, then those of the material images
+int chordvis_resolve_material(ChordCtx* c, ChordCountAndCmd drawed, const ChordResolveDesc* desc, const ChordResolveTargets* t,
+                              const ChordSurfaceTargets* s, const ChordMaterialTargets* m)
+{
+    const ChordResolveTargets tt = t ? *t : ChordResolveTargets{};
+    const ChordSurfaceTargets ss = s ? *s : ChordSurfaceTargets{};
+    const ChordMaterialTargets mm = m ? *m : ChordMaterialTargets{};
+    const ChordResolveDesc d = desc ? *desc : ChordResolveDesc{};
+    const bool anySurface = ss.vertexNormal || ss.tangent || ss.bitangent;
+    const bool anyMaterial = mm.baseColor || mm.emissive || mm.pixelNormal || mm.roughMetalAO;
+    int rc = resolve_checks(c, "resolve_material", drawed, any_resolve_target(tt) || anySurface || anyMaterial, tt.debugRGBA8 != nullptr, d);
+    if (rc) return rc;
+    if (ss.pad) return fail(c, CHORDVIS_E_INVALID, "resolve_material: ChordSurfaceTargets::pad must be NULL");
+    if ((ss.tangent || ss.bitangent) && !c->dTangents)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_material: the scene was uploaded without tangents (ChordAssetDesc::tangents)");
+    if (anySurface && !c->dNormals)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_material: the scene was uploaded without normals (ChordAssetDesc::normals)");
+    if (anyMaterial && !c->matTexturesLoaded)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_material: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (mm.pixelNormal && !c->dNormals)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_material: pixelNormal needs a scene uploaded with normals (ChordAssetDesc::normals)");
+    if (mm.pixelNormal && c->matAnyNormalTexture && !c->dTangents)
+        return fail(c, CHORDVIS_E_INVALID, "resolve_material: pixelNormal with a normal texture needs a scene uploaded with tangents (ChordAssetDesc::tangents)");
+    const unsigned long long* vis = nullptr;
+    if ((rc = resolve_source(c, drawed, &vis))) return rc;
+    chord::launch_resolve_material(c, vis, drawed.cmds, drawed.count, d, tt, chord::MaterialLaunch{ss, mm});
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9])
+{
+    static const uint32_t srgb[256] = {CHORD_SRGB_TABLE_BITS};
+    static const uint32_t ap1[9] = {CHORD_SRGB_2_AP1_BITS};
+    if (srgbToLinear) std::memcpy(srgbToLinear, srgb, sizeof(srgb));
+    if (srgbToAp1) std::memcpy(srgbToAp1, ap1, sizeof(ap1));
     return CHORDVIS_OK;
 }
 

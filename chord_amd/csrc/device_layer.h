@@ -93,6 +93,38 @@ struct DMaterial {             // 48 + 15 x 24 B
     uint32_t pad[2];
     DMatLevel levels[CHORD_MAX_TEX_LEVELS];
 };
+// What chordvis_resolve_material samples (kept by chordvis_upload_material_textures; the raster never sees it): per material the four
+// texture slots of loadGLTFMetallicRoughnessPBRMaterial (material.hlsli:66-153) with texture and sampler resolved, and the factors.
+// A level is a DMatLevel whose `base` counts TEXELS (one uint32 RGBA8 each, R in the low byte) of dMatTexels.
+#define CHORD_MATSLOT_BASECOLOR 0u
+#define CHORD_MATSLOT_EMISSIVE 1u
+#define CHORD_MATSLOT_NORMAL 2u
+#define CHORD_MATSLOT_METALROUGH 3u
+#define CHORD_MATSLOT_MAG_LINEAR 1u        // DMatSlot::filter bits: bilinear at lodq <= 0
+#define CHORD_MATSLOT_MIN_LINEAR 2u        // ... bilinear inside a level at lodq > 0
+#define CHORD_MATSLOT_MIP_NEAREST 4u       // ... *_MIPMAP_NEAREST
+#define CHORD_MATSLOT_MIP_LINEAR 8u        // ... *_MIPMAP_LINEAR
+struct DMatSlot {              // 32 + 15 x 24 B
+    uint32_t mips;             // 0: the material names no texture here (id >= textureCount)
+    uint32_t filter;           // CHORD_MATSLOT_* bits of the sampler's magFilter / minFilter
+    uint32_t wrapS, wrapT;
+    uint32_t pad[4];
+    DMatLevel levels[CHORD_MAX_TEX_LEVELS];
+};
+struct DMatRecord {            // 64 + 4 x 392 B
+    float    baseColorFactor[4];
+    float    emissiveFactor[3];
+    float    roughnessFactor;
+    float    metallicFactor;
+    float    normalFactorScale;
+    float    occlusionTextureStrength;
+    uint32_t bExistOcclusion;
+    uint32_t pbr;              // materialType == kLightingType_GLTF_MetallicRoughnessPBR
+    uint32_t pad[3];
+    DMatSlot slot[4];
+};
+static_assert(sizeof(DMatSlot) == 392 && sizeof(DMatRecord) == 64 + 4 * 392, "DMatRecord");
+
 // extension of a masked triangle's 48-byte record, in the TWO slots behind it.  Everything a row unit of the tile kernel needs to
 // sample the triangle's alpha is in here -- the chosen level's first byte and size, the wraps, the material's factor and cut-off --
 // so a unit's set-up is one round trip (this record), not three dependent ones (extension -> material -> level offsets).
@@ -319,6 +351,11 @@ struct ChordCtx {
     float* dTangents = nullptr;               // float4 per vertex (tangentBuffer), or null: no asset has tangents (likewise)
     uint8_t* dMeshletLod = nullptr;           // per device meshlet: ChordMeshlet::lod (DMeshlet carries vertexBase instead; the resolve's debug view reads it)
     bool anyMasked = false;
+    // chordvis_upload_material_textures (read by chordvis_resolve_material alone; dropped by the next chordvis_upload_scene)
+    chord::DMatRecord* dMatRecords = nullptr; // per material
+    uint32_t* dMatTexels = nullptr;           // RGBA8 texels of every level of every texture a material slot names, back to back
+    bool matTexturesLoaded = false;
+    bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
     chord::DBVHNode* dBvhNodes = nullptr;   // every primitive's tree (or null: the scene came without)
     bool bvhComplete = false;         // every primitive has a validated tree
@@ -527,6 +564,9 @@ void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const
                                const ChordResolveDesc& desc, const ChordResolveTargets& targets);   // kernels_resolve.hip
 void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                             const ChordResolveDesc& desc, const ChordResolveTargets& targets, const ChordSurfaceTargets& surface);
+struct MaterialLaunch { ChordSurfaceTargets surface; ChordMaterialTargets material; };
+void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                             const ChordResolveDesc& desc, const ChordResolveTargets& targets, const MaterialLaunch& m);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

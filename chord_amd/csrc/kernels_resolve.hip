@@ -3,25 +3,33 @@
 // (getTriangleMiscInfo), material.hlsli:41-64 (uv, uv gradients, motion, positionRS), base.hlsli:457-495
 // (calculateTriangleBarycentrics) and nanite_debug.hlsl:30-43,104-130 (the debug colours).
 //
-//   resolve_attributes_kernel<kSurface>   a wave per 16 x 4 pixels.  Its lanes load their visibility words; a ballot loop
+//   resolve_attributes_kernel<kLevel>     a wave per 16 x 4 pixels.  Its lanes load their visibility words; a ballot loop
 //                               names one leader lane per distinct low word (slot | triangle) of the block; each leader fetches
 //                               its triangle (command -> object / meshlet -> index word -> three vertices) and forms the
 //                               per-vertex products (clip position, translated-world position, the two motion clip positions,
 //                               uv); every pixel reads its leader's values through ds_bpermute and finishes the per-pixel
 //                               arithmetic.  Stores: 16 bytes per lane for the float4 images, 256 contiguous bytes per wave and row.
-//     <false>                   chordvis_resolve_attributes: the eight images.  Same arithmetic and resources as the
+//     <0>                       chordvis_resolve_attributes: the eight images.  Same arithmetic and resources as the
 //                               non-template kernel it replaces (108 VGPRs, occupancy 4); its gfx950 code differs from it only
 //                               in register assignment and two integer instructions.
-//     <true>                    chordvis_resolve_surface: the surface channels compiled in.  The leader also fetches the three
+//     <1>                       chordvis_resolve_surface: the surface channels compiled in.  The leader also fetches the three
 //                               vertices' normals (float3) and tangents (float4) and forms nRS, tRS, bRS
 //                               (nanite_shared.hlsli:157-175); the pixels interpolate them (material.hlsli:95-108).  134 VGPRs,
 //                               occupancy 3.
+//     <2>                       chordvis_resolve_material: the material channels behind them (material.hlsli:66-153).  Once a
+//                               pixel's attribute and surface values are final (the leaders' set-up registers are dead), a second
+//                               ballot loop walks the distinct MATERIAL ids of the wave: the material's record is read
+//                               wave-uniformly (readlane index -> scalar loads), the lanes of that material sample its four
+//                               texture slots with the pinned sampler of DESIGN.md 2 item 9 and store their texels of the four
+//                               images inside the loop (no accumulators).  1 KB of LDS: the sRGB decode table.
 
 // The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
 // does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
 
 #include "device_layer.h"
 #include "device_math.h"
+#include "material_tables.h"
+#include "texel_wrap.h"
 
 namespace chord {
 
@@ -105,13 +113,106 @@ struct SurfaceArgs {
 #define SURFACE_TANGENT 2u
 #define SURFACE_BITANGENT 4u
 
-// resolve_attributes_kernel<false> takes ResolveArgs alone; <true> carries SurfaceArgs after it
-template <bool kSurface> struct KernelArgs : ResolveArgs {};
-template <> struct KernelArgs<true> : ResolveArgs { SurfaceArgs e; };
+// what the material variant reads besides those two
+struct MaterialArgs {
+    const DMatRecord* records;         // per material (chordvis_upload_material_textures)
+    const uint32_t* texels;            // RGBA8 words, R in the low byte
+    uint32_t want;                     // MATERIAL_* bits of the non-null targets
+    uint32_t needSurface;              // SURFACE_* bits pixelNormal needs formed whether or not their images are asked for
+    ChordMaterialTargets t;
+};
+#define MATERIAL_BASECOLOR 1u
+#define MATERIAL_EMISSIVE 2u
+#define MATERIAL_NORMAL 4u
+#define MATERIAL_RMA 8u
 
-template <bool kSurface>
-__global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArgs<kSurface> a)
+// resolve_attributes_kernel<0> takes ResolveArgs alone; <1> carries SurfaceArgs after it, <2> MaterialArgs after that
+template <int kLevel> struct KernelArgs : ResolveArgs {};
+template <> struct KernelArgs<1> : ResolveArgs { SurfaceArgs e; };
+template <> struct KernelArgs<2> : ResolveArgs { SurfaceArgs e; MaterialArgs m; };
+
+// ---- the pinned sampler ------------------------------------------------------------------------------
+__device__ const uint32_t kSrgbBits[256] = {CHORD_SRGB_TABLE_BITS};
+__device__ const uint32_t kSrgb2Ap1Bits[9] = {CHORD_SRGB_2_AP1_BITS};
+
+// texel decode BEFORE filtering: alpha and linear slots byte / 255, rgb of sRGB slots through the table (in LDS)
+template <bool kSrgb>
+__device__ __forceinline__ float4 decode_texel(uint32_t w, const float* srgb)
 {
+    if constexpr (kSrgb) return make_float4(srgb[w & 255u], srgb[(w >> 8) & 255u], srgb[(w >> 16) & 255u], (float)(w >> 24) * (1.0f / 255.0f));
+    return make_float4((float)(w & 255u) * (1.0f / 255.0f), (float)((w >> 8) & 255u) * (1.0f / 255.0f),
+                       (float)((w >> 16) & 255u) * (1.0f / 255.0f), (float)(w >> 24) * (1.0f / 255.0f));
+}
+
+// one level, per channel sample_alpha's arithmetic (kernels_raster.hip)
+template <bool kSrgb>
+__device__ __forceinline__ float4 sample_level(const uint32_t* __restrict__ texels, const DMatLevel& L, uint32_t wrapS, uint32_t wrapT, bool linear,
+                                               float u, float v, const float* srgb)
+{
+    const int32_t W = (int32_t)(L.dims & 0xFFFFu) + 1, H = (int32_t)(L.dims >> 16) + 1;
+    const float fW = (float)W, fH = (float)H;
+    const uint32_t* base = texels + L.base;
+    if (!linear) {
+        const int32_t ix = wrap_index(texel_floor(u * fW), W, wrapS, L.magicS, L.biasS), iy = wrap_index(texel_floor(v * fH), H, wrapT, L.magicT, L.biasT);
+        return decode_texel<kSrgb>(base[iy * W + ix], srgb);
+    }
+    const float x = u * fW - 0.5f, y = v * fH - 0.5f;
+    const int32_t x0 = texel_floor(x), y0 = texel_floor(y);
+    float fx = x - (float)x0, fy = y - (float)y0;
+    if (!(fabsf(x) < 1.0e9f)) fx = 0.0f;
+    if (!(fabsf(y) < 1.0e9f)) fy = 0.0f;
+    int32_t ix0, ix1, iy0, iy1;
+    wrap_pair(x0, W, wrapS, L.magicS, L.biasS, ix0, ix1);
+    wrap_pair(y0, H, wrapT, L.magicT, L.biasT, iy0, iy1);
+    const float4 a00 = decode_texel<kSrgb>(base[iy0 * W + ix0], srgb), a10 = decode_texel<kSrgb>(base[iy0 * W + ix1], srgb);
+    const float4 a01 = decode_texel<kSrgb>(base[iy1 * W + ix0], srgb), a11 = decode_texel<kSrgb>(base[iy1 * W + ix1], srgb);
+    auto bil = [&](float c00, float c10, float c01, float c11) {
+        const float top = c00 + (c10 - c00) * fx, bot = c01 + (c11 - c01) * fx;
+        return top + (bot - top) * fy;
+    };
+    return make_float4(bil(a00.x, a10.x, a01.x, a11.x), bil(a00.y, a10.y, a01.y, a11.y), bil(a00.z, a10.z, a01.z, a11.z), bil(a00.w, a10.w, a01.w, a11.w));
+}
+
+// level of detail in 1/256 steps from the bit pattern of the squared footprint: the exponent and the top 8 mantissa bits are the
+// piecewise-linear log2 of rho2 in Q8, halved for the square.  A footprint that is not finite or not above 0 gives 0.
+__device__ __forceinline__ int32_t footprint_lodq(float4 g, float fW, float fH)
+{
+    const float ax = g.x * fW, ay = g.y * fH, bx = g.z * fW, by = g.w * fH;
+    const float ra = ax * ax + ay * ay, rb = bx * bx + by * by;
+    const float rho2 = fmaxf(ra, rb);
+    if (!(ra < __builtin_inff()) || !(rb < __builtin_inff()) || !(rho2 > 0.0f)) return 0;
+    return ((int32_t)(__float_as_uint(rho2) >> 15) - (127 << 8)) >> 1;
+}
+
+// S: a slot with mips > 0, read wave-uniformly; u, v, g (du/dx, dv/dx, du/dy, dv/dy) per lane
+template <bool kSrgb>
+__device__ __forceinline__ float4 sample_slot(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g, const float* srgb)
+{
+    const uint32_t d0 = S.levels[0].dims;
+    const int32_t lodq = footprint_lodq(g, (float)((d0 & 0xFFFFu) + 1u), (float)((d0 >> 16) + 1u));
+    const uint32_t filter = S.filter, last = S.mips - 1u;
+    uint32_t l0 = 0u, l1 = 0u;
+    bool linear = (filter & CHORD_MATSLOT_MAG_LINEAR) != 0u;
+    if (lodq > 0) {
+        linear = (filter & CHORD_MATSLOT_MIN_LINEAR) != 0u;
+        if (filter & CHORD_MATSLOT_MIP_NEAREST) l0 = l1 = min((uint32_t)(lodq + 128) >> 8, last);
+        else if (filter & CHORD_MATSLOT_MIP_LINEAR) { l0 = min((uint32_t)lodq >> 8, last); l1 = min(l0 + 1u, last); }
+    }
+    const DMatLevel L0 = S.levels[l0];
+    float4 c = sample_level<kSrgb>(texels, L0, S.wrapS, S.wrapT, linear, u, v, srgb);
+    if (l1 != l0) {                                       // (c0 + (c0 - c0) * f is c0: the second level is skipped when it is the first)
+        const DMatLevel L1 = S.levels[l1];
+        const float4 c1 = sample_level<kSrgb>(texels, L1, S.wrapS, S.wrapT, linear, u, v, srgb);
+        const float f = (float)(lodq & 255) * (1.0f / 256.0f);
+        c = make_float4(c.x + (c1.x - c.x) * f, c.y + (c1.y - c.y) * f, c.z + (c1.z - c.z) * f, c.w + (c1.w - c.w) * f);
+    }
+    return c;
+}
+
+template <int kLevel>
+__global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArgs<kLevel> a)
+{
+    constexpr bool kSurface = kLevel >= 1;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t block = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t bx = block % a.blocksX, by = block / a.blocksX;
@@ -140,6 +241,10 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
     float phs[3][4] = {}, prs[3][3] = {}, cur[3][3] = {}, last[3][3] = {}, uvv[3][2] = {};
     uint32_t meshletHashId = 0u, triWord = 0u, lod = 0u;
     float nrs[3][3] = {}, trs[3][3] = {}, brs[3][3] = {};                 // (surface variant only)
+    uint32_t matId = 0u;                                                  // (material variant only)
+    uint32_t surfNeed = 0u;                                               // SURFACE_* bits the leaders form
+    if constexpr (kSurface) surfNeed = a.e.want;
+    if constexpr (kLevel >= 2) surfNeed |= a.m.needSurface;
     if (isLeader) {
         const ChordDrawCmd cmd = a.cmds[slot];
         const uint32_t tri = low & 0xFFu;
@@ -161,6 +266,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                 lod = a.meshletLod[cmd.meshletId];
                 Mat4 Mi = {};
                 if constexpr (kSurface) Mi = load_mat(obj.basicData.translatedWorldToLocal);
+                if constexpr (kLevel >= 2) matId = CHORD_MATFLAG_MATERIAL(a.objStatic[cmd.objectId].matFlags);
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
                     const uint32_t vi = a.meshletData[m.dataOffset + ((triWord >> (8 * i)) & 0xFFu)] + m.vertexBase;
@@ -175,7 +281,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                     last[i][0] = ll.x; last[i][1] = ll.y; last[i][2] = ll.w;
                     if (a.texcoords) { uvv[i][0] = a.texcoords[(size_t)vi * 2]; uvv[i][1] = a.texcoords[(size_t)vi * 2 + 1]; }
                     if constexpr (kSurface) {
-                        if (a.e.want) {
+                        if (surfNeed) {
                             // nRS = normalize(mul(float4(nLS, 0), translatedWorldToLocal).xyz): the row-vector product, component j
                             // = (x * m0j + y * m1j) + z * m2j
                             const float nx = a.e.normals[(size_t)vi * 3], ny = a.e.normals[(size_t)vi * 3 + 1], nz = a.e.normals[(size_t)vi * 3 + 2];
@@ -184,7 +290,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                                            (nx * Mi.r[0][2] + ny * Mi.r[1][2]) + nz * Mi.r[2][2]};
                             const f3 n = normalize_or_zero(nw);
                             nrs[i][0] = n.x; nrs[i][1] = n.y; nrs[i][2] = n.z;
-                            if (a.e.want & (SURFACE_TANGENT | SURFACE_BITANGENT)) {
+                            if (surfNeed & (SURFACE_TANGENT | SURFACE_BITANGENT)) {
                                 const float4 tl = reinterpret_cast<const float4*>(a.e.tangents)[vi];
                                 // t = mul(localToTranslatedWorld, float4(tLS.xyz, 0)).xyz; tRS = normalize(t - dot(t, nRS) * nRS)
                                 const f3 tw = {(M.r[0][0] * tl.x + M.r[0][1] * tl.y) + M.r[0][2] * tl.z,
@@ -301,9 +407,10 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
         const uint32_t rgba = pack_unorm8(c.x) | pack_unorm8(c.y) << 8 | pack_unorm8(c.z) << 16 | 0xFF000000u;
         if (inside) a.t.debugRGBA8[pix] = hit ? rgba : 0xFF000000u;
     }
+    f3 Npx = {0.0f, 0.0f, 0.0f}, Tpx = {0.0f, 0.0f, 0.0f}, Bpx = {0.0f, 0.0f, 0.0f};   // (material variant: the pixel's frame)
     if constexpr (kSurface) {
         // vertexNormal / tangent / bitangent = (v0 * b.x + v1 * b.y) + v2 * b.z, not renormalised (material.hlsli:98-99)
-        auto put = [&](const float (&V)[3][3], float* dst) {
+        auto put = [&](const float (&V)[3][3], float* dst, bool store) {
             float Q[3][3];
 #pragma unroll
             for (int i = 0; i < 3; i++)
@@ -311,11 +418,87 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                 for (int k = 0; k < 3; k++) Q[i][k] = lane_read(V[i][k], leader);
             const float4 v = make_float4(interp3(Q[0][0], Q[1][0], Q[2][0], bary), interp3(Q[0][1], Q[1][1], Q[2][1], bary),
                                          interp3(Q[0][2], Q[1][2], Q[2][2], bary), 0.0f);
-            if (inside) reinterpret_cast<float4*>(dst)[pix] = hit ? v : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (store)
+                if (inside) reinterpret_cast<float4*>(dst)[pix] = hit ? v : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            return f3{v.x, v.y, v.z};
         };
-        if (a.e.want & SURFACE_NORMAL) put(nrs, a.e.t.vertexNormal);
-        if (a.e.want & SURFACE_TANGENT) put(trs, a.e.t.tangent);
-        if (a.e.want & SURFACE_BITANGENT) put(brs, a.e.t.bitangent);
+        if (surfNeed & SURFACE_NORMAL) Npx = put(nrs, a.e.t.vertexNormal, (a.e.want & SURFACE_NORMAL) != 0u);
+        if (surfNeed & SURFACE_TANGENT) Tpx = put(trs, a.e.t.tangent, (a.e.want & SURFACE_TANGENT) != 0u);
+        if (surfNeed & SURFACE_BITANGENT) Bpx = put(brs, a.e.t.bitangent, (a.e.want & SURFACE_BITANGENT) != 0u);
+    }
+    if constexpr (kLevel >= 2) {
+        // ---- loadGLTFMetallicRoughnessPBRMaterial, material.hlsli:66-153 ---------------------------------------------------
+        __shared__ float sSrgb[256];
+        sSrgb[threadIdx.x] = __uint_as_float(kSrgbBits[threadIdx.x]);
+        __syncthreads();
+        if (a.m.want) {
+            float U[3][2];
+#pragma unroll
+            for (int i = 0; i < 3; i++) { U[i][0] = lane_read(uvv[i][0], leader); U[i][1] = lane_read(uvv[i][1], leader); }
+            const float u = interp3(U[0][0], U[1][0], U[2][0], bary), v = interp3(U[0][1], U[1][1], U[2][1], bary);
+            const float4 g = make_float4(interp3(U[0][0], U[1][0], U[2][0], ddx), interp3(U[0][1], U[1][1], U[2][1], ddx),
+                                         interp3(U[0][0], U[1][0], U[2][0], ddy), interp3(U[0][1], U[1][1], U[2][1], ddy));
+            const uint32_t mId = lane_read(matId, leader);
+            const uint32_t* __restrict__ texels = a.m.texels;
+            bool written = false;
+            // one turn per distinct material of the wave; its record is wave-uniform
+            uint64_t left = __ballot(hit);
+            while (left) {
+                const int l = __ffsll((unsigned long long)left) - 1;
+                const uint32_t mat = (uint32_t)__builtin_amdgcn_readlane((int)mId, l);
+                const bool mine = hit && mId == mat;
+                left &= ~__ballot(mine);
+                const DMatRecord& M = a.m.records[mat];
+                if (!M.pbr) continue;                                   // (lighting.hlsl:369: other shading types leave 0)
+                if (!mine) continue;
+                written = true;
+                if (a.m.want & MATERIAL_BASECOLOR) {
+                    float4 c = make_float4(1.0f, 1.0f, 1.0f, 1.0f);    // the white fallback (asset_gltf.cpp:323-326)
+                    if (M.slot[CHORD_MATSLOT_BASECOLOR].mips) c = sample_slot<true>(texels, M.slot[CHORD_MATSLOT_BASECOLOR], u, v, g, sSrgb);
+                    const float r = c.x * M.baseColorFactor[0], gg = c.y * M.baseColorFactor[1], b = c.z * M.baseColorFactor[2];
+                    const float al = c.w * M.baseColorFactor[3];
+                    float m[9];
+#pragma unroll
+                    for (int i = 0; i < 9; i++) m[i] = __uint_as_float(kSrgb2Ap1Bits[i]);
+                    reinterpret_cast<float4*>(a.m.t.baseColor)[pix] = make_float4((m[0] * r + m[1] * gg) + m[2] * b, (m[3] * r + m[4] * gg) + m[5] * b,
+                                                                                  (m[6] * r + m[7] * gg) + m[8] * b, al);
+                }
+                if (a.m.want & MATERIAL_EMISSIVE) {
+                    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);    // the transparent-black fallback
+                    if (M.slot[CHORD_MATSLOT_EMISSIVE].mips) c = sample_slot<true>(texels, M.slot[CHORD_MATSLOT_EMISSIVE], u, v, g, sSrgb);
+                    reinterpret_cast<float4*>(a.m.t.emissive)[pix] = make_float4(c.x * M.emissiveFactor[0], c.y * M.emissiveFactor[1], c.z * M.emissiveFactor[2], 0.0f);
+                }
+                if (a.m.want & MATERIAL_NORMAL) {
+                    f3 nrm = Npx;
+                    if (M.slot[CHORD_MATSLOT_NORMAL].mips) {
+                        const float4 c = sample_slot<false>(texels, M.slot[CHORD_MATSLOT_NORMAL], u, v, g, sSrgb);
+                        float tx = c.x * 2.0f - 1.0f, ty = c.y * 2.0f - 1.0f;
+                        const float tz = sqrtf(fmaxf(0.0f, 1.0f - (tx * tx + ty * ty)));    // (departure: no NaN from a filtered xy beyond the unit disc)
+                        tx *= M.normalFactorScale; ty *= M.normalFactorScale;
+                        const f3 n = normalize_or_zero(f3{tx, ty, tz});
+                        // mul(n, float3x3(T, B, N)): component j = (n.x * T.j + n.y * B.j) + n.z * N.j
+                        nrm = f3{(n.x * Tpx.x + n.y * Bpx.x) + n.z * Npx.x, (n.x * Tpx.y + n.y * Bpx.y) + n.z * Npx.y, (n.x * Tpx.z + n.y * Bpx.z) + n.z * Npx.z};
+                    }
+                    reinterpret_cast<float4*>(a.m.t.pixelNormal)[pix] = make_float4(nrm.x, nrm.y, nrm.z, 0.0f);
+                }
+                if (a.m.want & MATERIAL_RMA) {
+                    float rough = M.roughnessFactor, metal = M.metallicFactor >= 1.0f ? 0.0f : M.metallicFactor, ao = 1.0f;   // gltf.h:53-58
+                    if (M.slot[CHORD_MATSLOT_METALROUGH].mips) {
+                        const float4 c = sample_slot<false>(texels, M.slot[CHORD_MATSLOT_METALROUGH], u, v, g, sSrgb);
+                        rough = c.y; metal = c.z;
+                        ao = M.bExistOcclusion ? M.occlusionTextureStrength * c.x : 1.0f;
+                    }
+                    reinterpret_cast<float4*>(a.m.t.roughMetalAO)[pix] = make_float4(rough, metal, ao, 0.0f);
+                }
+            }
+            if (inside && !written) {
+                const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (a.m.want & MATERIAL_BASECOLOR) reinterpret_cast<float4*>(a.m.t.baseColor)[pix] = z;
+                if (a.m.want & MATERIAL_EMISSIVE) reinterpret_cast<float4*>(a.m.t.emissive)[pix] = z;
+                if (a.m.want & MATERIAL_NORMAL) reinterpret_cast<float4*>(a.m.t.pixelNormal)[pix] = z;
+                if (a.m.want & MATERIAL_RMA) reinterpret_cast<float4*>(a.m.t.roughMetalAO)[pix] = z;
+            }
+        }
     }
 }
 
@@ -341,21 +524,39 @@ static ResolveArgs resolve_args(ChordCtx* c, const unsigned long long* vis, cons
 void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                                const ChordResolveDesc& desc, const ChordResolveTargets& t)
 {
-    KernelArgs<false> a;
+    KernelArgs<0> a;
     static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
     const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
-    CHORD_LAUNCH(c, resolve_attributes_kernel<false>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+    CHORD_LAUNCH(c, resolve_attributes_kernel<0>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
 }
 
 void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                             const ChordResolveDesc& desc, const ChordResolveTargets& t, const ChordSurfaceTargets& s)
 {
-    KernelArgs<true> a;
+    KernelArgs<1> a;
     static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
     a.e.normals = c->dNormals; a.e.tangents = c->dTangents; a.e.t = s;
     a.e.want = (s.vertexNormal ? SURFACE_NORMAL : 0u) | (s.tangent ? SURFACE_TANGENT : 0u) | (s.bitangent ? SURFACE_BITANGENT : 0u);
     const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
-    CHORD_LAUNCH(c, resolve_attributes_kernel<true>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+    CHORD_LAUNCH(c, resolve_attributes_kernel<1>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+}
+
+void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                             const ChordResolveDesc& desc, const ChordResolveTargets& t, const MaterialLaunch& ml)
+{
+    KernelArgs<2> a;
+    static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
+    const ChordSurfaceTargets& s = ml.surface;
+    const ChordMaterialTargets& m = ml.material;
+    a.e.normals = c->dNormals; a.e.tangents = c->dTangents; a.e.t = s;
+    a.e.want = (s.vertexNormal ? SURFACE_NORMAL : 0u) | (s.tangent ? SURFACE_TANGENT : 0u) | (s.bitangent ? SURFACE_BITANGENT : 0u);
+    a.m.records = c->dMatRecords; a.m.texels = c->dMatTexels; a.m.t = m;
+    a.m.want = (m.baseColor ? MATERIAL_BASECOLOR : 0u) | (m.emissive ? MATERIAL_EMISSIVE : 0u) | (m.pixelNormal ? MATERIAL_NORMAL : 0u) |
+               (m.roughMetalAO ? MATERIAL_RMA : 0u);
+    // pixelNormal reads the pixel's vertex normal, and its tangent and bitangent when some material has a normal texture
+    a.m.needSurface = m.pixelNormal ? (SURFACE_NORMAL | (c->matAnyNormalTexture ? SURFACE_TANGENT | SURFACE_BITANGENT : 0u)) : 0u;
+    const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
+    CHORD_LAUNCH(c, resolve_attributes_kernel<2>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
 }
 
 } // namespace chord

@@ -53,10 +53,17 @@ class SurfaceTargets(C.Structure):
     _fields_ = [("vertexNormal", C.c_void_p), ("tangent", C.c_void_p), ("bitangent", C.c_void_p), ("pad", C.c_void_p)]
 
 
+class MaterialTargets(C.Structure):
+    """ChordMaterialTargets: device pointers, None = not written."""
+    _fields_ = [("baseColor", C.c_void_p), ("emissive", C.c_void_p), ("pixelNormal", C.c_void_p), ("roughMetalAO", C.c_void_p)]
+
+
 # name -> floats (or uint32 for debugRGBA8) per texel of each resolve target (include/chordvis.h ChordResolveTargets)
 RESOLVE_CHANNELS = {"barycentrics": 4, "baryDdx": 4, "baryDdy": 4, "uv": 2, "uvGrad": 4, "positionRS": 4, "motionVector": 2, "debugRGBA8": 1}
 # ... and of the surface targets of chordvis_resolve_surface (ChordSurfaceTargets)
 SURFACE_CHANNELS = {"vertexNormal": 4, "tangent": 4, "bitangent": 4}
+# ... and of the material targets of chordvis_resolve_material (ChordMaterialTargets)
+MATERIAL_CHANNELS = {"baseColor": 4, "emissive": 4, "pixelNormal": 4, "roughMetalAO": 4}
 DEBUG_MESHLET, DEBUG_TRIANGLE, DEBUG_LOD, DEBUG_LOD_MESHLET, DEBUG_BARYCENTRICS = 0, 1, 2, 3, 4
 
 
@@ -206,6 +213,9 @@ def _load():
         "chordvis_prepare_shading_tile_param": (i32, [vp, u32, P(TileMarker), P(ShadingTiles)]),
         "chordvis_resolve_attributes": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets)]),
         "chordvis_resolve_surface": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets)]),
+        "chordvis_upload_material_textures": (i32, [vp, P(R.SceneDesc)]),
+        "chordvis_resolve_material": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets), P(MaterialTargets)]),
+        "chordvis_material_constants": (i32, [vp, vp]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),
         "chordvis_readback_shading_tiles": (i32, [vp, P(ShadingTiles), vp, u32, P(u32), vp]),
@@ -274,6 +284,15 @@ def hzb_desc(width, height):
     if rc != OK:
         raise ChordvisError("chordvis_hzb_desc(%d, %d) -> %d" % (width, height, rc))
     return d
+
+
+def material_constants():
+    """(sRGB8 -> linear table (256,), sRGB_2_AP1 (3, 3)) float32 as the library holds them (chordvis_material_constants)."""
+    srgb, ap1 = np.zeros(256, dtype=np.float32), np.zeros(9, dtype=np.float32)
+    rc = lib.chordvis_material_constants(srgb.ctypes.data, ap1.ctypes.data)
+    if rc != OK:
+        raise ChordvisError("chordvis_material_constants -> %d" % rc)
+    return srgb, ap1.reshape(3, 3)
 
 
 def make_views(camera, last_view=None):

@@ -55,6 +55,12 @@ class VisibilityRenderer:
         self.scene = scene
         self._check(L.lib.chordvis_upload_scene(self._ctx, C.byref(scene.desc)), "upload_scene")
 
+    def upload_material_textures(self, scene=None):
+        """Opt-in, after upload_scene: keeps the RGBA texels of every texture a material names and the per-material records
+        chordvis_resolve_material samples (default: the scene last uploaded).  Dropped by the next upload_scene."""
+        scene = self.scene if scene is None else scene
+        self._check(L.lib.chordvis_upload_material_textures(self._ctx, C.byref(scene.desc)), "upload_material_textures")
+
     def update_objects(self, objects):
         objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
         self._check(L.lib.chordvis_update_objects(self._ctx, objects.ctypes.data, len(objects)), "update_objects")
@@ -301,10 +307,12 @@ class VisibilityRenderer:
         out: {name: tensor} to write into instead of fresh tensors.  The tensors are ordered against the context's stream
         both ways: the resolve waits for the current torch stream, which in turn waits for the resolve.
         Names of L.SURFACE_CHANNELS (vertexNormal, tangent, bitangent; float4 each) may be asked for too: the call then goes through
-        chordvis_resolve_surface, still one launch (the scene must have been uploaded with normals / tangents)."""
+        chordvis_resolve_surface, still one launch (the scene must have been uploaded with normals / tangents).  Likewise the names
+        of L.MATERIAL_CHANNELS (baseColor, emissive, pixelNormal, roughMetalAO; float4 each): the call then goes through
+        chordvis_resolve_material (after upload_material_textures), one launch for any subset of the fifteen."""
         import torch
         names = list(L.RESOLVE_CHANNELS) if names is None else list(names)
-        channels = dict(L.RESOLVE_CHANNELS, **L.SURFACE_CHANNELS)
+        channels = dict(L.RESOLVE_CHANNELS, **L.SURFACE_CHANNELS, **L.MATERIAL_CHANNELS)
         bad = [n for n in names if n not in channels]
         if bad or not names:
             raise ValueError("resolve_attributes: unknown or no target names %r (known: %s)" % (bad, ", ".join(channels)))
@@ -324,11 +332,15 @@ class VisibilityRenderer:
             res[n] = t
         targets = L.ResolveTargets(**{n: t.data_ptr() for n, t in res.items() if n in L.RESOLVE_CHANNELS})
         surface = {n: t.data_ptr() for n, t in res.items() if n in L.SURFACE_CHANNELS}
+        material = {n: t.data_ptr() for n, t in res.items() if n in L.MATERIAL_CHANNELS}
         cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
         if mine.cuda_stream != cur.cuda_stream:
             mine.wait_stream(cur)                      # (the allocator may hand out memory torch work on `cur` still uses)
         d = C.byref(desc) if desc is not None else None
-        if surface:
+        if material:
+            self._check(L.lib.chordvis_resolve_material(self._ctx, cmd, d, C.byref(targets), C.byref(L.SurfaceTargets(**surface)),
+                                                        C.byref(L.MaterialTargets(**material))), "resolve_material")
+        elif surface:
             self._check(L.lib.chordvis_resolve_surface(self._ctx, cmd, d, C.byref(targets), C.byref(L.SurfaceTargets(**surface))),
                         "resolve_surface")
         else:

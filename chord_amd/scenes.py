@@ -396,8 +396,29 @@ class SceneBuilder:
         m["materialType"] = 1
         return m
 
-    def add_material(self, two_sided, alpha_mode=0, texture=0xFFFFFFFF, sampler=0, cutoff=0.5, alpha_factor=1.0):
-        self.materials.append(self._material(two_sided, alpha_mode, texture, sampler, cutoff, alpha_factor))
+    def add_material(self, two_sided, alpha_mode=0, texture=0xFFFFFFFF, sampler=0, cutoff=0.5, alpha_factor=1.0, *, pbr=False,
+                     base_color_factor=None, emissive=None, emissive_factor=None, normal=None, normal_scale=None,
+                     metallic_roughness=None, metallic_factor=None, roughness_factor=None, occlusion_strength=None, material_type=None):
+        """The keyword-only arguments fill the further slots of loadGLTFMetallicRoughnessPBRMaterial (material.hlsli:66-153):
+        emissive / normal / metallic_roughness = (texture, sampler); occlusion_strength not None sets bExistOcclusion.  pbr=True
+        makes the slots that are not given name NO texture (0xFFFFFFFF); without it they keep the 0 this builder has always
+        written (texture 0 of a scene that has textures)."""
+        m = self._material(two_sided, alpha_mode, texture, sampler, cutoff, alpha_factor)
+        for field, smp, pair in (("emissiveTexture", "emissiveSampler", emissive), ("normalTexture", "normalSampler", normal),
+                                 ("metallicRoughnessTexture", "metallicRoughnessSampler", metallic_roughness)):
+            if pair is not None:
+                m[field], m[smp] = pair
+            elif pbr:
+                m[field] = 0xFFFFFFFF
+        if base_color_factor is not None:
+            m["baseColorFactor"][0, :3] = base_color_factor
+        for field, val in (("emissiveFactor", emissive_factor), ("normalFactorScale", normal_scale), ("metallicFactor", metallic_factor),
+                           ("roughnessFactor", roughness_factor), ("materialType", material_type)):
+            if val is not None:
+                m[field] = val
+        if occlusion_strength is not None:
+            m["bExistOcclusion"], m["occlusionTextureStrength"] = 1, occlusion_strength
+        self.materials.append(m)
         return len(self.materials) - 1
 
     def add_texture(self, rgba8):
@@ -627,14 +648,22 @@ def _street_primitives(sb, lods=3, uv_tiles=None):
     return out
 
 
-def config3_street(width=3840, height=2160, lods=3, masked=False, attributes=False):
+def config3_street(width=3840, height=2160, lods=3, masked=False, attributes=False, materials=False):
     """BASELINE config 3 (Bistro-class): 21 872 LOD0 patches = 2 799 616 triangles, 352 objects, 3 LOD levels.
     masked: the SAME geometry with alpha-tested materials (mesh_raster.hlsl:34-38,107-112,198-204) on every prop and every other
     building -- two-sided foliage-style cut-outs (a noise and a disc texture, trilinear / nearest samplers): the workload of
     bench.py --workload street_4k_masked, triangle for triangle the opaque scene.
-    attributes: with per-vertex normals and tangents (PrimitiveBuilder); the geometry is the same."""
-    sb = SceneBuilder("config3_street" + ("_masked" if masked else ""), attributes)
+    attributes: with per-vertex normals and tangents (PrimitiveBuilder); the geometry is the same.
+    materials: the opaque geometry under the textured materials of the material resolve (_pbr_materials, cycled over the objects),
+    with normals, tangents and the masked variant's texture tiling: the workload of tools/resolve_time.py's material sets."""
+    assert not (masked and materials)
+    sb = SceneBuilder("config3_street" + ("_masked" if masked else "_materials" if materials else ""), attributes or materials)
     mats = [0]
+    if materials:
+        pm = _pbr_materials(sb, 11)
+        for k, (prim, l2w) in enumerate(_street_primitives(sb, lods, uv_tiles=(6.0, 3.0))):
+            sb.add_object(prim, l2w, material=pm[k % len(pm)])
+        return sb.build(), Camera((-62.0, 12.0, 3.0), (1.0, -0.18, -0.04), width, height)
     if masked:
         tex = [sb.add_texture(t) for t in _alpha_textures(11)]
         smp = [sb.add_sampler(T.FILTER_LINEAR_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_REPEAT),
@@ -740,6 +769,40 @@ def _alpha_textures(seed):
     return out
 
 
+def _masked_layout(sb, mats, lods, seed, position, front, width, height, ground=0, screen=None, behind=0, ground_uv=None, screen_scale=1.0):
+    """The geometry of masked_test_scene: a ground, eight buildings / cylinders with tiled (also negative) texture coordinates and
+    material mats[k % len(mats)], two copies behind masked ones, a screen right in front of the camera.  ground / screen / behind:
+    the materials of those objects (screen None: mats[1])."""
+    pb = PrimitiveBuilder(sb.attributes)
+    if ground_uv:
+        pb.uv_scale = ground_uv
+    pb.add_surface(plane_surface((-8, 0, 8), (16, 0, 0), (0, 0, -16), seed, 0.2, 0.7), 8, 8, lods)
+    sb.add_object(sb.add_primitive(pb), material=ground)                         # ground (opaque in masked_test_scene)
+    for k in range(8):
+        r = rand01(seed + 1, np.arange(k * 4, k * 4 + 4))
+        pb = PrimitiveBuilder(sb.attributes)
+        pb.uv_scale = (1.0 + 3.0 * r[3], 0.5 + 2.5 * r[2]) if k % 3 else (-2.0, 3.0)     # tiling, incl. negative coordinates
+        if k % 2 == 0:
+            _building(pb, 1.5 + r[0], 1.5 + r[1], 1.0 + 2.5 * r[2], seed * 100 + k * 8, lods)
+        else:
+            pb.add_surface(cylinder_surface((0, 0, 0), 0.3 + 0.4 * r[0], 1.0 + 2.0 * r[1], seed * 100 + k, 0.03), 4, 4, lods)
+        prim = sb.add_primitive(pb)
+        m = translate(-5.0 + 10.0 * r[2], 0.0, -5.0 + 10.0 * r[3]) @ rotate_y(r[0] * 3.0) @ scale(1.0 + 0.5 * r[1])
+        sb.add_object(prim, m, material=mats[k % len(mats)])
+        if k in (1, 4):                                                          # an opaque copy behind a masked one
+            sb.add_object(prim, translate(0.6, 0.0, -1.2) @ m, material=behind)
+    # a masked screen right in front of the camera: magnified texels, clipped by the near plane at the edges
+    pb = PrimitiveBuilder(sb.attributes)
+    pb.uv_scale = (3.0, 2.0)
+    f = np.array(front, dtype=np.float64) / np.linalg.norm(front)
+    side = np.cross(f, (0.0, 1.0, 0.0)); side /= np.linalg.norm(side)
+    org = np.array(position) + 0.9 * f - (0.7 * screen_scale) * side - np.array((0.0, 0.45 * screen_scale, 0.0))
+    pb.add_surface(plane_surface(tuple(org), tuple((1.4 * screen_scale) * side), (0.0, 0.9 * screen_scale, 0.0), seed + 5, 0.0, 1.0), 4, 4, 1)
+    sb.add_object(sb.add_primitive(pb), material=mats[1] if screen is None else screen)
+    cam = Camera(position, front, width, height)
+    return sb.build(), cam
+
+
 def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2, 6.0), front=(0.75, -0.22, -0.62), attributes=False):
     """small_test_scene's layout with alpha-tested, blended and white-fallback materials (mesh_raster.hlsl:34-38,107-112,
     198-204; mesh_raster.cpp:224): holes in the masked surfaces show the geometry behind them, blended objects draw
@@ -756,32 +819,85 @@ def masked_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2
             sb.add_material(0, T.ALPHA_BLEND),                                  # blended: draws nothing
             sb.add_material(0, T.ALPHA_MASK, 0xFFFFFFFF, 99, 0.5, 1.0),        # no texture: white fallback, opaque in effect
             sb.add_material(1, T.ALPHA_MASK, tex[0], smp[0], 0.5, 0.4)]        # alpha factor below the cut-off: nothing survives
-    pb = PrimitiveBuilder(sb.attributes)
-    pb.add_surface(plane_surface((-8, 0, 8), (16, 0, 0), (0, 0, -16), seed, 0.2, 0.7), 8, 8, lods)
-    sb.add_object(sb.add_primitive(pb))                                          # opaque ground
-    for k in range(8):
-        r = rand01(seed + 1, np.arange(k * 4, k * 4 + 4))
-        pb = PrimitiveBuilder(sb.attributes)
-        pb.uv_scale = (1.0 + 3.0 * r[3], 0.5 + 2.5 * r[2]) if k % 3 else (-2.0, 3.0)     # tiling, incl. negative coordinates
-        if k % 2 == 0:
-            _building(pb, 1.5 + r[0], 1.5 + r[1], 1.0 + 2.5 * r[2], seed * 100 + k * 8, lods)
-        else:
-            pb.add_surface(cylinder_surface((0, 0, 0), 0.3 + 0.4 * r[0], 1.0 + 2.0 * r[1], seed * 100 + k, 0.03), 4, 4, lods)
-        prim = sb.add_primitive(pb)
-        m = translate(-5.0 + 10.0 * r[2], 0.0, -5.0 + 10.0 * r[3]) @ rotate_y(r[0] * 3.0) @ scale(1.0 + 0.5 * r[1])
-        sb.add_object(prim, m, material=mats[k % len(mats)])
-        if k in (1, 4):                                                          # an opaque copy behind a masked one
-            sb.add_object(prim, translate(0.6, 0.0, -1.2) @ m, material=0)
-    # a masked screen right in front of the camera: magnified texels, clipped by the near plane at the edges
-    pb = PrimitiveBuilder(sb.attributes)
-    pb.uv_scale = (3.0, 2.0)
-    f = np.array(front, dtype=np.float64) / np.linalg.norm(front)
-    side = np.cross(f, (0.0, 1.0, 0.0)); side /= np.linalg.norm(side)
-    org = np.array(position) + 0.9 * f - 0.7 * side - np.array((0.0, 0.45, 0.0))
-    pb.add_surface(plane_surface(tuple(org), tuple(1.4 * side), (0.0, 0.9, 0.0), seed + 5, 0.0, 1.0), 4, 4, 1)
-    sb.add_object(sb.add_primitive(pb), material=mats[1])
-    cam = Camera(position, front, width, height)
-    return sb.build(), cam
+    return _masked_layout(sb, mats, lods, seed, position, front, width, height)
+
+
+def _pbr_textures(seed):
+    """Procedural RGBA8 textures of the material resolve: [0] a coloured brick albedo 64 x 64 with a checker in alpha, [1] an
+    odd-sized (37 x 21) colour noise, [2] a tangent-space normal map 64 x 32 with visible relief (round bumps, z reconstructed by
+    the consumer), [3] an occlusion (R) / roughness (G) / metallic (B) map 8 x 64 whose last levels are one texel wide, [4] an
+    emissive map 16 x 16 of coloured discs."""
+    yy, xx = np.mgrid[0:64, 0:64]
+    brick = ((xx + 16 * ((yy // 8) % 2)) % 32 < 30) & (yy % 8 < 7)
+    albedo = np.zeros((64, 64, 4), np.uint8)
+    albedo[..., 0] = np.where(brick, 150 + (xx * 3 + yy) % 90, 60)
+    albedo[..., 1] = np.where(brick, 60 + (yy * 2) % 50, 58)
+    albedo[..., 2] = np.where(brick, 40 + (xx ^ yy) % 40, 55)
+    albedo[..., 3] = np.where(((xx // 8) + (yy // 8)) % 2 == 0, 255, 90)
+    h = pcg_hash(np.arange(37 * 21 * 4, dtype=np.uint32) + np.uint32(seed * 7919))
+    noise = (h & 0xFF).astype(np.uint8).reshape(21, 37, 4)
+    yy, xx = np.mgrid[0:32, 0:64]
+    # height = a lattice of round bumps; the map stores the unit normal's xy, remapped to [0, 255]
+    hx = 0.9 * np.sin(xx * (2.0 * np.pi / 16.0)) * (0.6 + 0.4 * np.cos(yy * (2.0 * np.pi / 16.0)))
+    hy = 0.9 * np.sin(yy * (2.0 * np.pi / 16.0)) * (0.6 + 0.4 * np.cos(xx * (2.0 * np.pi / 16.0)))
+    ln = np.sqrt(hx * hx + hy * hy + 1.0)
+    nmap = np.zeros((32, 64, 4), np.uint8)
+    nmap[..., 0] = np.round((hx / ln * 0.5 + 0.5) * 255.0)
+    nmap[..., 1] = np.round((hy / ln * 0.5 + 0.5) * 255.0)
+    nmap[..., 2] = np.round((1.0 / ln * 0.5 + 0.5) * 255.0)
+    nmap[..., 3] = 255
+    yy, xx = np.mgrid[0:64, 0:8]
+    orm = np.zeros((64, 8, 4), np.uint8)
+    orm[..., 0] = 120 + (yy * 2) % 130
+    orm[..., 1] = 30 + (xx * 28 + yy * 3) % 220
+    orm[..., 2] = np.where((yy // 8) % 2 == 0, 230, 20)
+    orm[..., 3] = 255
+    yy, xx = np.mgrid[0:16, 0:16]
+    d = np.clip(1.0 - np.hypot(xx % 8 - 3.5, yy % 8 - 3.5) / 4.0, 0.0, 1.0)
+    emis = np.zeros((16, 16, 4), np.uint8)
+    emis[..., 0] = np.round(255.0 * d)
+    emis[..., 1] = np.round(180.0 * d * ((xx // 8) % 2))
+    emis[..., 2] = np.round(255.0 * d * ((yy // 8) % 2))
+    emis[..., 3] = 255
+    return [albedo, noise, nmap, orm, emis]
+
+
+def _pbr_materials(sb, seed, masked=False):
+    """Textures, samplers and materials of the material resolve's scenes: all three wrap modes and all six filter values across
+    the slots, a material with no textures at all, one with metallicFactor 1, one of another shading type, normalFactorScale
+    != 1, bExistOcclusion on and off.  masked: some of them alpha-tested.  Returns the material ids."""
+    al, no, nm, orm, em = [sb.add_texture(t) for t in _pbr_textures(seed)]
+    tri = sb.add_sampler(T.FILTER_LINEAR_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_REPEAT)
+    near = sb.add_sampler(T.FILTER_NEAREST, T.FILTER_NEAREST, T.WRAP_CLAMP_TO_EDGE, T.WRAP_MIRRORED_REPEAT)
+    lmn = sb.add_sampler(T.FILTER_LINEAR_MIPMAP_NEAREST, T.FILTER_NEAREST, T.WRAP_MIRRORED_REPEAT, T.WRAP_CLAMP_TO_EDGE)
+    nml = sb.add_sampler(T.FILTER_NEAREST_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_MIRRORED_REPEAT)
+    nmn = sb.add_sampler(T.FILTER_NEAREST_MIPMAP_NEAREST, T.FILTER_LINEAR, T.WRAP_MIRRORED_REPEAT, T.WRAP_REPEAT)
+    lin = sb.add_sampler(T.FILTER_LINEAR, T.FILTER_LINEAR, T.WRAP_CLAMP_TO_EDGE, T.WRAP_REPEAT)
+    mask = T.ALPHA_MASK if masked else 0
+    return [
+        sb.add_material(0, 0, al, tri, pbr=True, normal=(nm, tri), metallic_roughness=(orm, nml), emissive=(em, lmn),
+                        emissive_factor=(1.0, 0.5, 2.0), occlusion_strength=0.75, normal_scale=1.0),                  # everything, trilinear
+        sb.add_material(1, mask, no, near, 0.4, 0.9, pbr=True, normal=(nm, nmn), normal_scale=0.5,
+                        base_color_factor=(0.8, 1.0, 0.6), roughness_factor=0.35, metallic_factor=1.0),              # no MR texture, metallicFactor 1
+        sb.add_material(1, mask, al, lmn, 0.35, 1.0, pbr=True, metallic_roughness=(orm, lin), emissive=(em, nml),
+                        emissive_factor=(0.3, 0.3, 0.3)),                                                            # no normal map, occlusion off
+        sb.add_material(0, 0, pbr=True, roughness_factor=0.6, metallic_factor=0.25, base_color_factor=(0.5, 0.25, 0.125),
+                        emissive_factor=(1.0, 1.0, 1.0)),                                                            # no textures at all
+        sb.add_material(0, 0, al, tri, pbr=True, normal=(nm, tri), material_type=0),                                 # not a PBR material: zeros
+        sb.add_material(0, 0, no, nmn, pbr=True, normal=(nm, lin), normal_scale=2.0, metallic_roughness=(orm, lmn),
+                        occlusion_strength=1.0, emissive=(em, near), emissive_factor=(2.0, 2.0, 0.0)),               # nearest mips, scale 2
+    ]
+
+
+def material_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2.2, 6.0), front=(0.75, -0.22, -0.62), masked=True):
+    """masked_test_scene's layout under materials with all four texture slots (_pbr_materials), with normals and tangents: a
+    magnified screen near the camera (alpha-tested unless masked is False: the scene shows through its holes), far minified
+    buildings, tiled and negative texture coordinates, a ground under the trilinear material."""
+    sb = SceneBuilder("material_test_scene", True)
+    mats = _pbr_materials(sb, seed, masked)
+    order = [mats[3], mats[1], mats[2], mats[0], mats[4], mats[5], mats[3], mats[1]]
+    return _masked_layout(sb, order, lods, seed, position, front, width, height, ground=mats[0], behind=mats[3],
+                          ground_uv=(96.0, 96.0), screen_scale=0.55)
 
 
 def floor_under_camera(position=(0.3, 0.25, 0.2), front=(0.1, -0.6, -1.0), width=128, height=96):
@@ -1028,7 +1144,7 @@ def _camera_basis(position, front, world_up=(0.0, 1.0, 0.0)):
 
 
 def general_transform_scene(width=640, height=360, seed=11, masked=False, attributes=False, lods=3,
-                            position=(-7.0, 1.6, 6.5), front=(0.8, -0.12, -0.6), world_up=(0.22, 1.0, 0.13)):
+                            position=(-7.0, 1.6, 6.5), front=(0.8, -0.12, -0.6), world_up=(0.22, 1.0, 0.13), materials=False):
     """The primitives of small_test_scene / masked_test_scene under general object transforms, in motion.  Returns (scene, camera,
     local_to_world_last); the scene also carries transform_class (one of TILTED, STRETCHED, MIRRORED, SIZED per object), motion (a
     word per object) and local_to_world_at(t) (t = 1: the scene's frame, 0: the frame before, 2, 3 ..: the motion continued).
@@ -1040,10 +1156,17 @@ def general_transform_scene(width=640, height=360, seed=11, masked=False, attrib
       SIZED      instances of one building from large and near to small and far (the LOD cut picks different levels).
     Motion: "spin" rotates in place, "slide" translates across the view, "rescale" changes scale, "reveal" starts behind the wall (a
     large occluder in front of the camera) and ends beside it, "hide" does the reverse, "enter" comes into the frustum from outside,
-    "still" does not move.  masked: alpha-tested materials on every class and a masked quad that crosses the near plane."""
-    sb = SceneBuilder("general_transform_scene" + ("_masked" if masked else ""), attributes)
+    "still" does not move.  masked: alpha-tested materials on every class and a masked quad that crosses the near plane.
+    materials: the opaque scene under the textured materials of the material resolve (_pbr_materials), with normals and tangents
+    and masked's texture coordinates: mirrored and stretched objects carry the bitangent's sign through the TBN."""
+    assert not (masked and materials)
+    sb = SceneBuilder("general_transform_scene" + ("_masked" if masked else "_materials" if materials else ""), attributes or materials)
     P, f, r, u = _camera_basis(position, front, world_up)
-    if masked:
+    if materials:
+        pm = _pbr_materials(sb, seed)
+        one, two = [pm[0], pm[5]], [pm[1], pm[2]]
+        masked = "uv"                               # (the tiled texture coordinates of the masked variant; no alpha test)
+    elif masked:
         tex = [sb.add_texture(t) for t in _alpha_textures(seed)]
         smp = [sb.add_sampler(T.FILTER_LINEAR_MIPMAP_LINEAR, T.FILTER_LINEAR, T.WRAP_REPEAT, T.WRAP_REPEAT),
                sb.add_sampler(T.FILTER_NEAREST, T.FILTER_NEAREST, T.WRAP_CLAMP_TO_EDGE, T.WRAP_MIRRORED_REPEAT)]

@@ -559,6 +559,43 @@ typedef struct ChordSurfaceTargets {
  * scene without a stream read it as 0. */
 int chordvis_resolve_surface(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
                              const ChordResolveTargets* targets, const ChordSurfaceTargets* surface);
+/* The material of the visible triangle -- loadGLTFMetallicRoughnessPBRMaterial, material.hlsli:66-153: what a lighting pass reads
+ * after the surface frame.  Opt-in: chordvis_upload_scene keeps only the alpha of the textures its alpha test samples; this call,
+ * AFTER chordvis_upload_scene and with the same descriptor, keeps all four channels of every level of every texture that a
+ * material of the scene names in baseColorId / emissiveTexture / normalTexture / metallicRoughnessTexture (id < textureCount), and
+ * a per-material record with the four (texture, sampler) pairs resolved (sampler id >= samplerCount: REPEAT, NEAREST).  A named
+ * texture without data, wider or higher than 16384, or with more than 15 levels: CHORDVIS_E_INVALID, nothing kept (what an earlier
+ * call kept is dropped too).  Dropped by the next chordvis_upload_scene.  Frames, culls and the other resolves do not read it. */
+int chordvis_upload_material_textures(ChordCtx* ctx, const ChordSceneDesc* scene);
+/* Caller-owned device images as in ChordResolveTargets.  Empty pixels, pixels whose id is not below the list's count and pixels
+ * whose material's materialType is not kLightingType_GLTF_MetallicRoughnessPBR (1; base.h:423, lighting.hlsl:369) hold 0.
+ * Float32, source order, one rounding per operation; the texture sampler is the pinned one of DESIGN.md 2 item 9 (isotropic level
+ * of detail in 1/256 steps from the bit pattern of the squared footprint, the filters and wraps of the material's glTF samplers,
+ * sRGB texels decoded through a 256-entry table before filtering):
+ *   baseColor    = sample(baseColorId) * baseColorFactor, rgb then mul(sRGB_2_AP1, rgb); no texture: white (1, 1, 1, 1)
+ *   emissive     = sample(emissiveTexture).rgb * emissiveFactor; no texture: transparent black
+ *   pixelNormal  = no normal texture: the interpolated vertex normal.  Else xy = sample.xy * 2 - 1, z = sqrt(max(0, 1 - dot(xy, xy)))
+ *                  (departure: the reference's sqrt of a negative value is NaN), xy *= normalFactorScale,
+ *                  mul(normalize(xyz), float3x3(tangent, bitangent, vertexNormal)) with the values of ChordSurfaceTargets
+ *   roughMetalAO = metallic-roughness texture: (.g, .b, bExistOcclusion ? occlusionTextureStrength * .r : 1); none:
+ *                  (roughnessFactor, metallicFactor >= 1 ? 0 : metallicFactor, 1)                              (gltf.h:53-58) */
+typedef struct ChordMaterialTargets {
+    float* baseColor;      /* float4: AP1 rgb, alpha                      material.hlsli:66-72,84 */
+    float* emissive;       /* float4: rgb, 0                              :74-81                  */
+    float* pixelNormal;    /* float4: xyz, 0                              :91-120                 */
+    float* roughMetalAO;   /* float4: roughness, metallic, materialAO, 0  :122-153                */
+} ChordMaterialTargets;
+/* chordvis_resolve_surface plus the four material images: any subset of the fifteen in ONE launch on the same stream, under the
+ * same preconditions, waits and refusals; targets and surface may be NULL.  CHORDVIS_E_INVALID also when a material target is
+ * asked for and no chordvis_upload_material_textures came since the last chordvis_upload_scene; when pixelNormal is asked of a scene
+ * uploaded without normals; and when pixelNormal is asked, some material has an uploaded normal texture and the scene has no
+ * tangents. */
+int chordvis_resolve_material(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
+                              const ChordResolveTargets* targets, const ChordSurfaceTargets* surface,
+                              const ChordMaterialTargets* material);
+/* The two constant tables of the material resolve as the library holds them (host call, no context): the sRGB8 -> linear decode
+ * (256 floats) and sRGB_2_AP1 (9 floats, row-major).  Either may be NULL. */
+int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9]);
 /* The hipStream_t the context enqueues on (the one given to chordvis_create, or its own): a host that allocates targets on a
  * stream of its own orders the two against each other. */
 void* chordvis_stream(ChordCtx* ctx);
