@@ -1628,6 +1628,16 @@ int chordvis_resolve_material(ChordCtx* c, ChordCountAndCmd drawed, const ChordR
     return CHORDVIS_OK;
 }
 
+int chordvis_set_material_anisotropy(ChordCtx* c, uint32_t maxAnisotropy)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (maxAnisotropy != 1u && maxAnisotropy != 2u && maxAnisotropy != 4u && maxAnisotropy != 8u && maxAnisotropy != 16u)
+        return fail(c, CHORDVIS_E_INVALID, "set_material_anisotropy: the maximum anisotropy is 1 (off), 2, 4, 8 or 16");
+    c->matAnisotropy = maxAnisotropy;
+    return CHORDVIS_OK;
+}
+uint32_t chordvis_material_anisotropy(const ChordCtx* c) { return c ? c->matAnisotropy : 0u; }
+
 int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9])
 {
     static const uint32_t srgb[256] = {CHORD_SRGB_TABLE_BITS};

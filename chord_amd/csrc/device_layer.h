@@ -356,6 +356,7 @@ struct ChordCtx {
     uint32_t* dMatTexels = nullptr;           // RGBA8 texels of every level of every texture a material slot names, back to back
     bool matTexturesLoaded = false;
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
+    uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
     chord::DBVHNode* dBvhNodes = nullptr;   // every primitive's tree (or null: the scene came without)
     bool bvhComplete = false;         // every primitive has a validated tree

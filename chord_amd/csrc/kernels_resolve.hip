@@ -22,6 +22,10 @@
 //                               wave-uniformly (readlane index -> scalar loads), the lanes of that material sample its four
 //                               texture slots with the pinned sampler of DESIGN.md 2 item 9 and store their texels of the four
 //                               images inside the loop (no accumulators).  1 KB of LDS: the sRGB decode table.
+//     <3>                       chordvis_resolve_material after chordvis_set_material_anisotropy with N > 1: <2> whose slots are
+//                               sampled by sample_slot_aniso: up to N taps along the longer derivative, each
+//                               the whole per-level pipeline, averaged in index order.  A lane loops to its own tap count; the slot's
+//                               level records are read once, before the loop.  <2> is not touched: it is what N = 1 launches.
 
 // The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
 // does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
@@ -130,6 +134,7 @@ struct MaterialArgs {
 template <int kLevel> struct KernelArgs : ResolveArgs {};
 template <> struct KernelArgs<1> : ResolveArgs { SurfaceArgs e; };
 template <> struct KernelArgs<2> : ResolveArgs { SurfaceArgs e; MaterialArgs m; };
+template <> struct KernelArgs<3> : KernelArgs<2> { uint32_t kmax; };   // log2 of the context's maximum anisotropy (1 .. 4)
 
 // ---- the pinned sampler ------------------------------------------------------------------------------
 __device__ const uint32_t kSrgbBits[256] = {CHORD_SRGB_TABLE_BITS};
@@ -207,6 +212,72 @@ __device__ __forceinline__ float4 sample_slot(const uint32_t* __restrict__ texel
         c = make_float4(c.x + (c1.x - c.x) * f, c.y + (c1.y - c.y) * f, c.z + (c1.z - c.z) * f, c.w + (c1.w - c.w) * f);
     }
     return c;
+}
+
+// The anisotropic sampler, kmax = log2 N >= 1.  ra, rb, lmaj as footprint_lodq forms them.  The two
+// derivative lengths are the axes (no ellipse fit): k = min(kmax, ceil(lmaj - lmin), ceil(lmaj)) in whole octaves, n = 1 << k taps
+// at u + dmaj * t_i, t_i = (2i + 1 - n) / (2n), on level(s) lodq' = max(lmaj - (k << 8), 0); d = 0, d += c_i - c_0 in index order
+// (i >= 1), c_0 + d * (1 / n): equal taps give c_0 exactly, which a running sum of the taps does not (3c is not c's neighbour).
+// Powers of two make t_i, 1 / n and the level shift exact.  k = 0 (isotropic, magnified, not finite): sample_slot's path, no offset
+// formed, c_0 returned as it is.
+template <bool kSrgb>
+__device__ __forceinline__ float4 sample_slot_aniso(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g, uint32_t kmax,
+                                                    const float* srgb)
+{
+    const uint32_t d0 = S.levels[0].dims;
+    const float fW = (float)((d0 & 0xFFFFu) + 1u), fH = (float)((d0 >> 16) + 1u);
+    const float ax = g.x * fW, ay = g.y * fH, bx = g.z * fW, by = g.w * fH;
+    const float ra = ax * ax + ay * ay, rb = bx * bx + by * by;
+    const bool xMajor = ra >= rb;                                        // (a tie goes to x)
+    const float rmaj2 = fmaxf(ra, rb), rmin2 = fminf(ra, rb);
+    int32_t lmaj = 0, k = 0;
+    if (ra < __builtin_inff() && rb < __builtin_inff() && rmaj2 > 0.0f) {
+        lmaj = ((int32_t)(__float_as_uint(rmaj2) >> 15) - (127 << 8)) >> 1;
+        if (lmaj > 0) {
+            int32_t spread = (int32_t)kmax;
+            if (rmin2 > 0.0f) spread = (max(lmaj - (((int32_t)(__float_as_uint(rmin2) >> 15) - (127 << 8)) >> 1), 0) + 255) >> 8;
+            k = min(min((int32_t)kmax, spread), (lmaj + 255) >> 8);
+        }
+    }
+    const int32_t lodq = max(lmaj - (k << 8), 0);
+    const uint32_t filter = S.filter, last = S.mips - 1u;
+    uint32_t l0 = 0u, l1 = 0u;
+    bool linear = (filter & CHORD_MATSLOT_MAG_LINEAR) != 0u;
+    if (lmaj > 0) {
+        linear = (filter & CHORD_MATSLOT_MIN_LINEAR) != 0u;
+        if (filter & CHORD_MATSLOT_MIP_NEAREST) l0 = l1 = min((uint32_t)(lodq + 128) >> 8, last);
+        else if (filter & CHORD_MATSLOT_MIP_LINEAR) { l0 = min((uint32_t)lodq >> 8, last); l1 = min(l0 + 1u, last); }
+    }
+    // the level records depend on lodq', not on the tap
+    const DMatLevel L0 = S.levels[l0], L1 = S.levels[l1];
+    const float f = (float)(lodq & 255) * (1.0f / 256.0f);
+    const uint32_t wrapS = S.wrapS, wrapT = S.wrapT;
+    const float du = xMajor ? g.x : g.z, dv = xMajor ? g.y : g.w;
+    const int32_t n = 1 << k;
+    const float inv2n = __uint_as_float((uint32_t)(126 - k) << 23);      // 1 / (2n)
+    float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d = c0;
+    for (int32_t i = 0; i < n; i++) {
+        float ui = u, vi = v;
+        if (k) { const float t = (float)(2 * i + 1 - n) * inv2n; ui = u + du * t; vi = v + dv * t; }
+        float4 c = sample_level<kSrgb>(texels, L0, wrapS, wrapT, linear, ui, vi, srgb);
+        if (l1 != l0) {
+            const float4 c1 = sample_level<kSrgb>(texels, L1, wrapS, wrapT, linear, ui, vi, srgb);
+            c = make_float4(c.x + (c1.x - c.x) * f, c.y + (c1.y - c.y) * f, c.z + (c1.z - c.z) * f, c.w + (c1.w - c.w) * f);
+        }
+        if (i == 0) c0 = c;
+        else d = make_float4(d.x + (c.x - c0.x), d.y + (c.y - c0.y), d.z + (c.z - c0.z), d.w + (c.w - c0.w));
+    }
+    if (k) { const float s = __uint_as_float((uint32_t)(127 - k) << 23); c0 = make_float4(c0.x + d.x * s, c0.y + d.y * s, c0.z + d.z * s, c0.w + d.w * s); }
+    return c0;
+}
+
+// a slot of the material loop: <2> samples it with sample_slot, <3> with sample_slot_aniso
+template <int kLevel, bool kSrgb>
+__device__ __forceinline__ float4 sample_material_slot(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g,
+                                                       const KernelArgs<kLevel>& a, const float* srgb)
+{
+    if constexpr (kLevel >= 3) return sample_slot_aniso<kSrgb>(texels, S, u, v, g, a.kmax, srgb);
+    else return sample_slot<kSrgb>(texels, S, u, v, g, srgb);
 }
 
 template <int kLevel>
@@ -454,7 +525,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                 written = true;
                 if (a.m.want & MATERIAL_BASECOLOR) {
                     float4 c = make_float4(1.0f, 1.0f, 1.0f, 1.0f);    // the white fallback (asset_gltf.cpp:323-326)
-                    if (M.slot[CHORD_MATSLOT_BASECOLOR].mips) c = sample_slot<true>(texels, M.slot[CHORD_MATSLOT_BASECOLOR], u, v, g, sSrgb);
+                    if (M.slot[CHORD_MATSLOT_BASECOLOR].mips) c = sample_material_slot<kLevel, true>(texels, M.slot[CHORD_MATSLOT_BASECOLOR], u, v, g, a, sSrgb);
                     const float r = c.x * M.baseColorFactor[0], gg = c.y * M.baseColorFactor[1], b = c.z * M.baseColorFactor[2];
                     const float al = c.w * M.baseColorFactor[3];
                     float m[9];
@@ -465,13 +536,13 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                 }
                 if (a.m.want & MATERIAL_EMISSIVE) {
                     float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);    // the transparent-black fallback
-                    if (M.slot[CHORD_MATSLOT_EMISSIVE].mips) c = sample_slot<true>(texels, M.slot[CHORD_MATSLOT_EMISSIVE], u, v, g, sSrgb);
+                    if (M.slot[CHORD_MATSLOT_EMISSIVE].mips) c = sample_material_slot<kLevel, true>(texels, M.slot[CHORD_MATSLOT_EMISSIVE], u, v, g, a, sSrgb);
                     reinterpret_cast<float4*>(a.m.t.emissive)[pix] = make_float4(c.x * M.emissiveFactor[0], c.y * M.emissiveFactor[1], c.z * M.emissiveFactor[2], 0.0f);
                 }
                 if (a.m.want & MATERIAL_NORMAL) {
                     f3 nrm = Npx;
                     if (M.slot[CHORD_MATSLOT_NORMAL].mips) {
-                        const float4 c = sample_slot<false>(texels, M.slot[CHORD_MATSLOT_NORMAL], u, v, g, sSrgb);
+                        const float4 c = sample_material_slot<kLevel, false>(texels, M.slot[CHORD_MATSLOT_NORMAL], u, v, g, a, sSrgb);
                         float tx = c.x * 2.0f - 1.0f, ty = c.y * 2.0f - 1.0f;
                         const float tz = sqrtf(fmaxf(0.0f, 1.0f - (tx * tx + ty * ty)));    // (departure: no NaN from a filtered xy beyond the unit disc)
                         tx *= M.normalFactorScale; ty *= M.normalFactorScale;
@@ -484,7 +555,7 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
                 if (a.m.want & MATERIAL_RMA) {
                     float rough = M.roughnessFactor, metal = M.metallicFactor >= 1.0f ? 0.0f : M.metallicFactor, ao = 1.0f;   // gltf.h:53-58
                     if (M.slot[CHORD_MATSLOT_METALROUGH].mips) {
-                        const float4 c = sample_slot<false>(texels, M.slot[CHORD_MATSLOT_METALROUGH], u, v, g, sSrgb);
+                        const float4 c = sample_material_slot<kLevel, false>(texels, M.slot[CHORD_MATSLOT_METALROUGH], u, v, g, a, sSrgb);
                         rough = c.y; metal = c.z;
                         ao = M.bExistOcclusion ? M.occlusionTextureStrength * c.x : 1.0f;
                     }
@@ -544,7 +615,7 @@ void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const Ch
 void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                              const ChordResolveDesc& desc, const ChordResolveTargets& t, const MaterialLaunch& ml)
 {
-    KernelArgs<2> a;
+    KernelArgs<3> a;                                                     // (its KernelArgs<2> base is what N = 1 launches)
     static_cast<ResolveArgs&>(a) = resolve_args(c, vis, cmds, cmdCount, desc, t);
     const ChordSurfaceTargets& s = ml.surface;
     const ChordMaterialTargets& m = ml.material;
@@ -556,7 +627,12 @@ void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const C
     // pixelNormal reads the pixel's vertex normal, and its tangent and bitangent when some material has a normal texture
     a.m.needSurface = m.pixelNormal ? (SURFACE_NORMAL | (c->matAnyNormalTexture ? SURFACE_TANGENT | SURFACE_BITANGENT : 0u)) : 0u;
     const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
-    CHORD_LAUNCH(c, resolve_attributes_kernel<2>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+    if (c->matAnisotropy > 1u) {                                         // chordvis_set_material_anisotropy: 2, 4, 8 or 16
+        a.kmax = (uint32_t)__builtin_ctz(c->matAnisotropy);
+        CHORD_LAUNCH(c, resolve_attributes_kernel<3>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+    } else {
+        CHORD_LAUNCH(c, resolve_attributes_kernel<2>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, static_cast<const KernelArgs<2>&>(a));
+    }
 }
 
 } // namespace chord

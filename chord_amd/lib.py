@@ -215,6 +215,8 @@ def _load():
         "chordvis_resolve_surface": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets)]),
         "chordvis_upload_material_textures": (i32, [vp, P(R.SceneDesc)]),
         "chordvis_resolve_material": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets), P(MaterialTargets)]),
+        "chordvis_set_material_anisotropy": (i32, [vp, u32]),
+        "chordvis_material_anisotropy": (u32, [vp]),
         "chordvis_material_constants": (i32, [vp, vp]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),

@@ -61,6 +61,14 @@ class VisibilityRenderer:
         scene = self.scene if scene is None else scene
         self._check(L.lib.chordvis_upload_material_textures(self._ctx, C.byref(scene.desc)), "upload_material_textures")
 
+    def set_material_anisotropy(self, n):
+        """Maximum anisotropy of the material resolve's sampler: 1 (default: the isotropic sampler), 2, 4, 8 or 16 taps along the
+        longer derivative.  Per context; kept across upload_scene and upload_material_textures."""
+        self._check(L.lib.chordvis_set_material_anisotropy(self._ctx, int(n)), "set_material_anisotropy")
+
+    def material_anisotropy(self):
+        return int(L.lib.chordvis_material_anisotropy(self._ctx))
+
     def update_objects(self, objects):
         objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
         self._check(L.lib.chordvis_update_objects(self._ctx, objects.ctypes.data, len(objects)), "update_objects")

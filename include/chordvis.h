@@ -593,6 +593,23 @@ typedef struct ChordMaterialTargets {
 int chordvis_resolve_material(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
                               const ChordResolveTargets* targets, const ChordSurfaceTargets* surface,
                               const ChordMaterialTargets* material);
+/* Opt-in anisotropic filtering of chordvis_resolve_material's sampler: maxAnisotropy N = 1 (the default: the isotropic sampler
+ * above, the same kernel and the same bits as without this call), 2, 4, 8 or 16; any other value: CHORDVIS_E_INVALID, the setting
+ * unchanged, chordvis_last_error names the allowed values.  Per context (each rank of a sharded set-up sets its own); kept across
+ * chordvis_upload_scene and chordvis_upload_material_textures; read by no other entry point (the visibility pass's alpha test keeps
+ * its own sampler, so frames are the same at every N).  The definition, per texture slot of a pixel, with
+ * ra = ax * ax + ay * ay and rb = bx * bx + by * by the squared lengths of the x and y derivatives in level-0 texels:
+ *   axes    rmaj2 = max(ra, rb), rmin2 = min(ra, rb); the major axis is (dudx, dvdx) when ra >= rb, else (dudy, dvdy)
+ *   logs    lmaj = lodq of rmaj2 (the isotropic sampler's lodq, same bits), lmin = lodq of rmin2, kmax = log2 N
+ *   k       0 when ra or rb is not finite, rmaj2 is not above 0, or lmaj <= 0 (magnified); else
+ *           min(kmax, (max(lmaj - lmin, 0) + 255) >> 8 [kmax when rmin2 is not above 0], (lmaj + 255) >> 8)
+ *   level   lodq' = max(lmaj - (k << 8), 0) takes lodq's place in the levels, their fraction and clamps; min / mag still asks lmaj > 0
+ *   taps    n = 1 << k; t_i = float(2i + 1 - n) * (1 / (2n)); u_i = u + dmaj_u * t_i, v_i = v + dmaj_v * t_i; each tap is the whole
+ *           per-level pipeline (decode, nearest / bilinear, wraps, the two-level lerp); d = 0, d = d + (c_i - c_0) for i = 1 .. n - 1
+ *           in index order, result c_0 + d * (1 / n) (equal taps give c_0 exactly).  k = 0 forms no offset: the isotropic sampler's
+ *           path and bits. */
+int chordvis_set_material_anisotropy(ChordCtx* ctx, uint32_t maxAnisotropy);
+uint32_t chordvis_material_anisotropy(const ChordCtx* ctx);   /* the last accepted value (1 after chordvis_create) */
 /* The two constant tables of the material resolve as the library holds them (host call, no context): the sRGB8 -> linear decode
  * (256 floats) and sRGB_2_AP1 (9 floats, row-major).  Either may be NULL. */
 int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9]);

@@ -4,13 +4,19 @@ targets of chordvis_resolve_surface (vertexNormal, tangent, bitangent), bytes mo
 6.3 TB/s (achievable).  Times N resolves between two events on the context's stream (a torch stream handed to the context).
 
     python tools/resolve_time.py [N] [WARMUP]
-    python tools/resolve_time.py [N] [WARMUP] --materials [--sets a,b] [--compare OTHER_LIB [ROUNDS]]
+    python tools/resolve_time.py [N] [WARMUP] --materials [--sets a,b] [--compare OTHER_LIB [ROUNDS]] [--compare-sets a,b]
+    python tools/resolve_time.py [N] [WARMUP] --materials --sets material --anisotropy 1,8,16 [--taps]
 
 --materials: config 3 under the textured materials (scenes.config3_street(materials=True)) and two more sets: `material` (the four
 images of chordvis_resolve_material) and `everything` (all fifteen).  Their bytes column counts the image bytes only (the texels
 fetched come on top: a gather, see profiles/resolve_material_config3_4k_time.txt).
 --compare OTHER_LIB: the sets `all` and `surface` measured in fresh processes that alternate this library, OTHER_LIB and OTHER_LIB
 again (ROUNDS times, default 3): this library against the other one, and the other one against itself (the spread of the run).
+--compare-sets a,b: the sets compared (default all,surface), e.g. `material` at the default anisotropy of 1.
+--anisotropy A,B,...: every chosen set that holds a material image is timed once per value, under
+chordvis_set_material_anisotropy (its line is named set@value); the other sets are timed once.
+--taps: per value, the sampler taps and the texel fetches the pinned sampler requests per PBR pixel of the frame, counted on the
+host by tests/spec_material_aniso_np.py's tap_plan from the uv gradients the device resolved (no texel is read).
 """
 import json
 import os
@@ -31,22 +37,57 @@ MATERIAL_SETS = {"material": list(MATERIAL), "everything": list(L.RESOLVE_CHANNE
 CHANNELS = dict(L.RESOLVE_CHANNELS, **L.SURFACE_CHANNELS, **MATERIAL)
 
 
-def compare(argv, other, rounds):
-    """alternating fresh processes: (this, other, other) x rounds over the existing sets"""
+def count_taps(r, scene, values):
+    """{value: (sampler taps, texel fetches) per PBR pixel} over the textured slots of the frame r holds"""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import spec_material_aniso_np as SA
+    import spec_material_np as SM
+    g = r.resolve_attributes(names=["uvGrad"])["uvGrad"]
+    torch.cuda.synchronize()
+    grad = g.cpu().numpy().reshape(-1, 4)
+    mat = SM.material_of_pixels(scene, r.read_visibility(), r.read_cmds(r.last_frame_cmds()))
+    out = {}
+    for n in values:
+        taps = fetches = pbr = 0
+        for m in np.unique(mat[mat >= 0]):
+            M = scene.materials[m]
+            if int(M["materialType"]) != SM.PBR_TYPE:
+                continue
+            pix = np.nonzero(mat == m)[0]
+            pbr += len(pix)
+            for slot in SM.SLOTS:
+                levels, smp = SM.slot_texture(scene, M, slot)
+                if levels is None:
+                    continue
+                p = SA.tap_plan(grad[pix], levels[0].shape[1], levels[0].shape[0], n)
+                minified, last = p["lmaj"] > 0, len(levels) - 1
+                lin = lambda f: f in (SM.LINEAR, SM.LINEAR_MIPMAP_NEAREST, SM.LINEAR_MIPMAP_LINEAR)
+                per_level = np.where(minified, 4 if lin(smp[0]) else 1, 4 if lin(smp[1]) else 1)
+                two = minified & (smp[0] in (SM.NEAREST_MIPMAP_LINEAR, SM.LINEAR_MIPMAP_LINEAR)) & ((p["lodq"] >> 8) < last)
+                n_taps = np.int64(1) << p["k"]
+                taps += int(n_taps.sum())
+                fetches += int((n_taps * per_level * np.where(two, 2, 1)).sum())
+        out[n] = (taps / max(pbr, 1), fetches / max(pbr, 1), pbr)
+    return out
+
+
+def compare(argv, other, rounds, names):
+    """alternating fresh processes: (this, other, other) x rounds over `names`"""
     import subprocess
     libs = [("this", L.LIB_PATH), ("otherA", other), ("otherB", other)]
-    ms = {k: {"all": [], "surface": []} for k, _ in libs}
+    ms = {k: {n: [] for n in names} for k, _ in libs}
     for _ in range(rounds):
         for key, path in libs:
             env = dict(os.environ, CHORDVIS_LIB=path, CHORDVIS_AB_OLD_LIB="1")
-            out = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--materials", "--sets", "all,surface"], env=env,
+            out = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--materials", "--sets", ",".join(names)], env=env,
                                  capture_output=True, text=True, timeout=600)
             if out.returncode != 0:
                 raise SystemExit("child failed (%s): %s" % (key, out.stderr[-2000:]))
             for ln in json.loads(out.stdout.strip().splitlines()[-1])["results"]:
                 ms[key][ln["targets"]].append(ln["ms"])
     med = lambda v: sorted(v)[len(v) // 2]
-    for name in ("all", "surface"):
+    for name in names:
         a, b, t = med(ms["otherA"][name]), med(ms["otherB"][name]), med(ms["this"][name])
         print("%-8s this %.4f ms | other %.4f / %.4f ms (itself against itself: %+.2f %%) | this against other %+.2f %%   runs this %s other %s" % (
             name, t, a, b, 100.0 * (b - a) / a, 100.0 * (t - min(a, b)) / min(a, b), ms["this"][name], ms["otherA"][name] + ms["otherB"][name]))
@@ -55,7 +96,7 @@ def compare(argv, other, rounds):
 
 def main():
     argv = sys.argv[1:]
-    pos = [a for a in argv if a.isdigit()]
+    pos = [a for i, a in enumerate(argv) if a.isdigit() and (i == 0 or argv[i - 1] != "--anisotropy")]
     n = int(pos[0]) if len(pos) > 0 else 50
     warm = int(pos[1]) if len(pos) > 1 else 5
     materials = "--materials" in argv
@@ -66,6 +107,7 @@ def main():
         i = argv.index("--compare")
         rounds = int(argv[i + 2]) if len(argv) > i + 2 and argv[i + 2].isdigit() else 3
         sets = {k: v for k, v in sets.items() if k in MATERIAL_SETS}
+    aniso = [int(x) for x in argv[argv.index("--anisotropy") + 1].split(",")] if "--anisotropy" in argv else [None]
     flags = R.FLAG_FRUSTUM_CULL | R.FLAG_CONE_CULL | R.FLAG_HZB_CULL
     scene, cam = scenes.config3_street(3840, 2160, materials=True) if materials else scenes.config3_street(3840, 2160, masked=True, attributes=True)
     L.fill_objects(scene, cam)
@@ -83,7 +125,11 @@ def main():
         r.sync()
         covered = int(((r.read_visibility() & 0xFFFFFFFF) != 0).sum())
         lines = []
-        for name, names in sets.items():
+        runs = [(name, names, a) for name, names in sets.items() for a in (aniso if any(k in MATERIAL for k in names) else [None])]
+        for name, names, a in runs:
+            if a is not None:
+                r.set_material_anisotropy(a)
+                name = "%s@%d" % (name, a)
             out = r.resolve_attributes(names=names)                  # the targets, allocated once
             for _ in range(warm):
                 r.resolve_attributes(names=names, out=out)
@@ -105,10 +151,16 @@ def main():
         print("%-20s %8.4f ms  %3d B/px  %6.1f MB  bound %.4f ms @8 TB/s, %.4f ms @6.3 TB/s  -> %.1f %% of 8 TB/s" % (
             ln["targets"], ln["ms"], ln["bytes_per_pixel"], ln["bytes"] / 1e6, ln["bytes_bound_ms_8tbs"], ln["bytes_bound_ms_6p3tbs"],
             100.0 * ln["share_of_8tbs"]))
+    if "--taps" in argv:
+        info["taps"] = {}
+        for a, (taps, fetches, pbr) in count_taps(r, scene, [1 if a is None else a for a in aniso]).items():
+            print("anisotropy %2d: %.2f sampler taps, %.2f texel fetches per PBR pixel (%d PBR pixels)" % (a, taps, fetches, pbr))
+            info["taps"][a] = dict(sampler_taps_per_pbr_pixel=round(taps, 3), texel_fetches_per_pbr_pixel=round(fetches, 3), pbr_pixels=pbr)
     print(json.dumps(dict(info, results=lines)))
     r.close()
     if "--compare" in argv:
-        compare([str(n), str(warm)], argv[argv.index("--compare") + 1], rounds)
+        names = argv[argv.index("--compare-sets") + 1].split(",") if "--compare-sets" in argv else ["all", "surface"]
+        compare([str(n), str(warm)], argv[argv.index("--compare") + 1], rounds, names)
 
 
 if __name__ == "__main__":
