@@ -50,6 +50,64 @@ int dalloc(ChordCtx* c, T** p, size_t count)
 template <typename T>
 void dfree(T*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } }
 
+// ---- block-compressed textures (ChordTexture::format; kernels_texture.hip) ----
+uint32_t tex_block_bytes(uint32_t format)      // of a CHORD_TEXFMT_BC* format; 0: RGBA8 (or none of them)
+{
+    if (format == CHORD_TEXFMT_BC1_RGB || format == CHORD_TEXFMT_BC4) return 8u;
+    if (format == CHORD_TEXFMT_BC3 || format == CHORD_TEXFMT_BC5) return 16u;
+    return 0u;
+}
+#define CHORD_TEXFMT_NAMES "0 (RGBA8), 1 (BC1_RGB), 2 (BC3), 3 (BC4), 4 (BC5)"
+
+// The compressed levels one upload expands: their bytes go to ONE staging buffer (every chain 16-byte aligned in it), one record
+// per level to a small device table, one kernel launch decodes them all; buffer and table are freed after the synchronise.
+struct TexDecodeJob {
+    struct Copy { const uint8_t* host; uint64_t offset, bytes; };
+    std::vector<chord::DTexLevelRec> recs;
+    std::vector<Copy> copies;
+    uint64_t stagingBytes = 0;
+    uint32_t blocks = 0;
+
+    // dst: where level 0 goes (a texel index of dMatTexels / a byte index of dTexAlpha); the levels follow as an RGBA8 chain's do
+    void add(const ChordTexture& tx, uint32_t dst)
+    {
+        const uint32_t bb = tex_block_bytes(tx.format);
+        const uint64_t offset = (stagingBytes + 15ull) & ~15ull;
+        uint64_t bytes = 0;
+        for (uint32_t l = 0; l < tx.mipCount; l++) {
+            const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l), bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
+            recs.push_back(chord::DTexLevelRec{blocks, (uint32_t)((offset + bytes) / 8u), dst, w, h, bw, tx.format, 0u});
+            blocks += bw * bh; bytes += (uint64_t)bw * bh * bb; dst += w * h;
+        }
+        copies.push_back(Copy{tx.rgba8, offset, bytes});
+        stagingBytes = offset + bytes;
+    }
+
+    int run(ChordCtx* c, const char* who, uint32_t* texels, uint8_t* alpha, bool alphaOnly)
+    {
+        if (recs.empty()) return CHORDVIS_OK;
+        if (stagingBytes / 8u > 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "texture decode: more than 32 GiB of compressed texture levels in one upload");
+        const uint32_t count = (uint32_t)recs.size();
+        recs.push_back(chord::DTexLevelRec{blocks, 0u, 0u, 0u, 0u, 1u, 0u, 0u});      // closes the table
+        uint8_t* dStaging = nullptr;
+        chord::DTexLevelRec* dRecs = nullptr;
+        hipError_t e = hipMalloc((void**)&dStaging, stagingBytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&dRecs, recs.size() * sizeof(recs[0]));
+        if (e == hipSuccess) e = hipMemcpy(dRecs, recs.data(), recs.size() * sizeof(recs[0]), hipMemcpyHostToDevice);
+        for (size_t i = 0; i < copies.size() && e == hipSuccess; i++)
+            e = hipMemcpy(dStaging + copies[i].offset, copies[i].host, copies[i].bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            chord::launch_texture_decode(c, dRecs, count, blocks, dStaging, texels, alpha, alphaOnly);
+            e = hipGetLastError();
+            const hipError_t es = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = es;
+        }
+        if (dStaging) (void)hipFree(dStaging);
+        if (dRecs) (void)hipFree(dRecs);
+        return e == hipSuccess ? CHORDVIS_OK : fail(c, CHORDVIS_E_HIP, who, e);
+    }
+};
+
 void record(ChordCtx* c, int tag) { chord::stamp(c, tag); }
 
 void begin_frame_stamps(ChordCtx* c)
@@ -664,7 +722,12 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     // what the masked buckets sample: alpha channels of every texture level, materials with texture + sampler resolved,
     // the per-vertex texture coordinates (mesh_raster.hlsl:107-112,198-204)
     std::vector<DMaterial> dmats(s->materialCount);
-    std::vector<uint8_t> alpha;
+    // (the alpha of an RGBA8 texture is picked out on the host, per texture; a block-compressed one is expanded on the device)
+    struct AlphaCopy { size_t base; std::vector<uint8_t> bytes; };
+    std::vector<AlphaCopy> alphaCopies;
+    std::vector<std::pair<size_t, size_t>> alphaOpaque;                    // (first byte, bytes) of BC1_RGB / BC4 / BC5 chains: 255 throughout
+    TexDecodeJob alphaDecode;                                              // BC3 chains: their alpha blocks
+    size_t alphaTexels = 0;
     std::vector<uint32_t> texOffset(s->textureCount, 0xFFFFFFFFu);
     bool anyMasked = false;
     for (uint32_t m = 0; m < s->materialCount; m++) anyMasked = anyMasked || s->materials[m].alphaMode == CHORD_ALPHA_MASK;
@@ -677,15 +740,23 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t t = 0; t < s->textureCount; t++) {
             if (!sampled[t]) continue;
             const ChordTexture& tx = s->textures[t];
+            if (tx.format != CHORD_TEXFMT_RGBA8 && !tex_block_bytes(tx.format))
+                return fail(c, CHORDVIS_E_INVALID, "upload_scene: unknown ChordTexture::format on a texture a masked material samples; allowed: " CHORD_TEXFMT_NAMES);
             if (!tx.rgba8 || tx.width == 0 || tx.height == 0 || tx.mipCount == 0 || tx.width > 16384u || tx.height > 16384u || tx.mipCount > 15u)
                 return fail(c, CHORDVIS_E_INVALID, "upload_scene: texture without data, or larger than 16384 / 15 levels");
             size_t texels = 0;
             for (uint32_t l = 0; l < tx.mipCount; l++) texels += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
-            if (alpha.size() + texels >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_scene: more than 4 G texels of alpha");
-            texOffset[t] = (uint32_t)alpha.size();
-            const size_t base = alpha.size();
-            alpha.resize(base + texels);
-            for (size_t i = 0; i < texels; i++) alpha[base + i] = tx.rgba8[i * 4 + 3];
+            if (alphaTexels + texels >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_scene: more than 4 G texels of alpha");
+            texOffset[t] = (uint32_t)alphaTexels;
+            const size_t base = alphaTexels;
+            alphaTexels += texels;
+            if (tx.format == CHORD_TEXFMT_BC3) alphaDecode.add(tx, (uint32_t)base);
+            else if (tx.format != CHORD_TEXFMT_RGBA8) alphaOpaque.push_back({base, texels});
+            else {
+                alphaCopies.push_back(AlphaCopy{base, std::vector<uint8_t>(texels)});
+                uint8_t* a8 = alphaCopies.back().bytes.data();
+                for (size_t i = 0; i < texels; i++) a8[i] = tx.rgba8[i * 4 + 3];
+            }
         }
     }
     for (uint32_t m = 0; m < s->materialCount; m++) {
@@ -771,14 +842,20 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod)
     if (!bvh.empty()) { UP(c->dBvhNodes, bvh) } else dfree(c->dBvhNodes);
     c->bvhComplete = bvhComplete;
-    if (!alpha.empty()) { UP(c->dTexAlpha, alpha) } else dfree(c->dTexAlpha);
+    if (alphaTexels) {
+        if ((rc = dalloc(c, &c->dTexAlpha, alphaTexels))) return rc;
+        for (const AlphaCopy& a : alphaCopies) CHORD_HIP(c, hipMemcpy(c->dTexAlpha + a.base, a.bytes.data(), a.bytes.size(), hipMemcpyHostToDevice));
+        for (const auto& o : alphaOpaque) CHORD_HIP(c, hipMemsetAsync(c->dTexAlpha + o.first, 0xFF, o.second, c->stream));
+        if ((rc = alphaDecode.run(c, "upload_scene: texture decode", nullptr, c->dTexAlpha, true))) return rc;
+        if (!alphaOpaque.empty()) CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    } else dfree(c->dTexAlpha);
     if (!uvs.empty()) { UP(c->dTexcoords, uvs) } else dfree(c->dTexcoords);
     if (!nrm.empty()) { UP(c->dNormals, nrm) } else dfree(c->dNormals);
     if (!tng.empty()) { UP(c->dTangents, tng) } else dfree(c->dTangents);
 #undef UP
     c->instTriangles = instTriangles;
     dfree(c->dMatRecords); dfree(c->dMatTexels);                           // (chordvis_upload_material_textures is per scene upload)
-    c->matTexturesLoaded = false; c->matAnyNormalTexture = false;
+    c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }       // (it aliased the old scene buffers)
     if ((rc = chord::alloc_scene_work_buffers(c))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dObjectsOwned, s->objects, sizeof(ChordObject) * s->objectCount, hipMemcpyHostToDevice));
@@ -804,7 +881,7 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     (void)hipSetDevice(c->device);
     CHORD_HIP(c, hipStreamSynchronize(c->stream));                         // (a resolve in flight may read the records being replaced)
     dfree(c->dMatRecords); dfree(c->dMatTexels);
-    c->matTexturesLoaded = false; c->matAnyNormalTexture = false;
+    c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
 
     const uint32_t nTex = s->textures ? s->textureCount : 0u;
     std::vector<uint8_t> named(nTex, 0);
@@ -819,20 +896,24 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         slot_ids(s->materials[m], tex, smp);
         for (int k = 0; k < 4; k++) if (tex[k] < nTex) named[tex[k]] = 1;
     }
-    std::vector<uint32_t> texels;
+    // RGBA8 chains are copied to their place in dMatTexels as they are (little-endian: R is the low byte of the word);
+    // block-compressed ones are expanded there by one kernel launch
+    size_t texelCount = 0;
+    TexDecodeJob decode;
     std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu);
     for (uint32_t t = 0; t < nTex; t++) {
         if (!named[t]) continue;
         const ChordTexture& tx = s->textures[t];
+        if (tx.format != CHORD_TEXFMT_RGBA8 && !tex_block_bytes(tx.format))
+            return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: unknown ChordTexture::format on a texture a material names; allowed: " CHORD_TEXFMT_NAMES);
         if (!tx.rgba8 || tx.width == 0 || tx.height == 0 || tx.mipCount == 0 || tx.width > 16384u || tx.height > 16384u || tx.mipCount > CHORD_MAX_TEX_LEVELS)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
         size_t count = 0;
         for (uint32_t l = 0; l < tx.mipCount; l++) count += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
-        if (texels.size() + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
-        texBase[t] = (uint32_t)texels.size();
-        const size_t base = texels.size();
-        texels.resize(base + count);
-        std::memcpy(texels.data() + base, tx.rgba8, count * 4);            // (little-endian: R is the low byte of the word)
+        if (texelCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
+        texBase[t] = (uint32_t)texelCount;
+        if (tx.format != CHORD_TEXFMT_RGBA8) decode.add(tx, (uint32_t)texelCount);
+        texelCount += count;
     }
     auto wrap_consts = [](uint32_t n, uint32_t mode, uint32_t& magic, uint32_t& bias) {   // (DMatLevel; as chordvis_upload_scene's)
         magic = 0u; bias = 0u;
@@ -880,12 +961,53 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     int rc;
     if ((rc = dalloc(c, &c->dMatRecords, recs.size()))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dMatRecords, recs.data(), recs.size() * sizeof(recs[0]), hipMemcpyHostToDevice));
-    if (!texels.empty()) {
-        if ((rc = dalloc(c, &c->dMatTexels, texels.size()))) { dfree(c->dMatRecords); return rc; }
-        hipError_t e = hipMemcpy(c->dMatTexels, texels.data(), texels.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { dfree(c->dMatRecords); dfree(c->dMatTexels); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
+    if (texelCount) {
+        if ((rc = dalloc(c, &c->dMatTexels, texelCount))) { dfree(c->dMatRecords); return rc; }
+        for (uint32_t t = 0; t < nTex; t++) {
+            const ChordTexture& tx = s->textures[t];
+            if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8) continue;
+            size_t count = 0;
+            for (uint32_t l = 0; l < tx.mipCount; l++) count += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
+            hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8, count * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { dfree(c->dMatRecords); dfree(c->dMatTexels); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
+        }
+        if ((rc = decode.run(c, "upload_material_textures: texture decode", c->dMatTexels, nullptr, false))) { dfree(c->dMatRecords); dfree(c->dMatTexels); return rc; }
     }
+    c->matTex.resize(nTex);
+    for (uint32_t t = 0; t < nTex; t++) c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, s->textures[t].mipCount};
     c->matTexturesLoaded = true; c->matAnyNormalTexture = anyNormal;
+    return CHORDVIS_OK;
+}
+
+int chordvis_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t height, uint32_t mipCount, uint64_t* bytes)
+{
+    const uint32_t bb = tex_block_bytes(format);
+    if (!bytes || (format != CHORD_TEXFMT_RGBA8 && !bb) || width == 0 || height == 0 || mipCount == 0) return CHORDVIS_E_INVALID;
+    unsigned __int128 total = 0;
+    for (uint32_t l = 0; l < mipCount && l < 32u; l++) {
+        const uint64_t w = std::max(1u, width >> l), h = std::max(1u, height >> l);
+        total += bb ? (unsigned __int128)((w + 3u) / 4u) * ((h + 3u) / 4u) * bb : (unsigned __int128)w * h * 4u;
+    }
+    if (mipCount > 32u) total += (unsigned __int128)(mipCount - 32u) * (bb ? bb : 4u);     // (1 x 1 from level 32 on)
+    if (total > 0xFFFFFFFFFFFFFFFFull) return CHORDVIS_E_INVALID;
+    *bytes = (uint64_t)total;
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_material_texture(ChordCtx* c, uint32_t textureId, uint32_t level, uint8_t* hostRgba8)
+{
+    if (!c || !hostRgba8) return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: null argument");
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (textureId >= c->matTex.size() || c->matTex[textureId].base == 0xFFFFFFFFu)
+        return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: no material of the scene names this texture");
+    const ChordCtx::MatTexInfo& t = c->matTex[textureId];
+    if (level >= t.mipCount) return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: the level is not below the texture's mipCount");
+    size_t off = t.base;
+    for (uint32_t l = 0; l < level; l++) off += (size_t)std::max(1u, t.width >> l) * std::max(1u, t.height >> l);
+    const size_t count = (size_t)std::max(1u, t.width >> level) * std::max(1u, t.height >> level);
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    CHORD_HIP(c, hipMemcpy(hostRgba8, c->dMatTexels + off, count * 4, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }
 
@@ -1824,7 +1946,8 @@ int chordvis_debug_graph_frames(ChordCtx* c, uint32_t pairs, float* msPerFrameSt
 }
 
 // Debugging aid: raw read of an internal buffer.  which: 0 tile counts (FrameState::tileCount), 1 fixed bins, 2 chunk table,
-// 3 bin pool, 4 compact records, 5 wide records, 6 the fused cull kernel's look-back words.  offset / bytes in bytes.
+// 3 bin pool, 4 compact records, 5 wide records, 6 the fused cull kernel's look-back words, 7 the alpha plane (dTexAlpha).
+// offset / bytes in bytes.
 int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes, void* host)
 {
     if (!c || !host) return fail(c, CHORDVIS_E_INVALID, "debug_read: null argument");
@@ -1838,6 +1961,9 @@ int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes,
     case 4: base = (const char*)c->dTrisC; break;
     case 5: base = (const char*)c->dTris; break;
     case 6: base = (const char*)c->dCullLookback; break;       // look-back words of frame_cull_fused_kernel (profile build: stage clocks behind them)
+    case 7: base = (const char*)c->dTexAlpha;                  // the alpha plane of the masked buckets
+        if (!base) return fail(c, CHORDVIS_E_INVALID, "debug_read: the scene has no alpha plane (no masked material samples a texture)");
+        break;
     default: return fail(c, CHORDVIS_E_INVALID, "debug_read: unknown buffer");
     }
     CHORD_HIP(c, hipMemcpy(host, base + offset, bytes, hipMemcpyDeviceToHost));

@@ -125,6 +125,20 @@ struct DMatRecord {            // 64 + 4 x 392 B
 };
 static_assert(sizeof(DMatSlot) == 392 && sizeof(DMatRecord) == 64 + 4 * 392, "DMatRecord");
 
+// One level of a block-compressed texture (CHORD_TEXFMT_BC*) for texture_decode_kernel (kernels_texture.hip): an upload packs one
+// record per (texture, level) it expands, in the order of their blocks in the flat grid, plus a closing record whose firstBlock is
+// the total.  A workgroup finds the record of its first block by bisection over firstBlock.
+struct DTexLevelRec {          // 32 B
+    uint32_t firstBlock;       // blocks of all records before this one
+    uint32_t src;              // first block of the level in the staging buffer, in units of 8 bytes
+    uint32_t dst;              // first texel of the level in dMatTexels / first alpha byte in dTexAlpha (DMatLevel::base)
+    uint32_t width, height;    // of the level, in texels
+    uint32_t blocksPerRow;     // ceil(width / 4)
+    uint32_t format;           // CHORD_TEXFMT_BC*
+    uint32_t pad;
+};
+static_assert(sizeof(DTexLevelRec) == 32, "DTexLevelRec");
+
 // extension of a masked triangle's 48-byte record, in the TWO slots behind it.  Everything a row unit of the tile kernel needs to
 // sample the triangle's alpha is in here -- the chosen level's first byte and size, the wraps, the material's factor and cut-off --
 // so a unit's set-up is one round trip (this record), not three dependent ones (extension -> material -> level offsets).
@@ -355,6 +369,8 @@ struct ChordCtx {
     chord::DMatRecord* dMatRecords = nullptr; // per material
     uint32_t* dMatTexels = nullptr;           // RGBA8 texels of every level of every texture a material slot names, back to back
     bool matTexturesLoaded = false;
+    struct MatTexInfo { uint32_t base, width, height, mipCount; };   // base: first texel in dMatTexels, 0xFFFFFFFF: no material names it
+    std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
@@ -568,6 +584,10 @@ void launch_resolve_surface(ChordCtx* c, const unsigned long long* vis, const Ch
 struct MaterialLaunch { ChordSurfaceTargets surface; ChordMaterialTargets material; };
 void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                              const ChordResolveDesc& desc, const ChordResolveTargets& targets, const MaterialLaunch& m);
+// kernels_texture.hip: expands the blocks of `count` levels (recs[count] closes the table) from `staging` into RGBA8 words of
+// `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.
+void launch_texture_decode(ChordCtx* c, const DTexLevelRec* recs, uint32_t count, uint32_t totalBlocks, const void* staging,
+                           uint32_t* texels, uint8_t* alpha, bool alphaOnly);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -214,6 +214,8 @@ def _load():
         "chordvis_resolve_attributes": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets)]),
         "chordvis_resolve_surface": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets)]),
         "chordvis_upload_material_textures": (i32, [vp, P(R.SceneDesc)]),
+        "chordvis_texture_chain_bytes": (i32, [u32, u32, u32, u32, P(u64)]),
+        "chordvis_readback_material_texture": (i32, [vp, u32, u32, vp]),
         "chordvis_resolve_material": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets), P(MaterialTargets)]),
         "chordvis_set_material_anisotropy": (i32, [vp, u32]),
         "chordvis_material_anisotropy": (u32, [vp]),
@@ -286,6 +288,15 @@ def hzb_desc(width, height):
     if rc != OK:
         raise ChordvisError("chordvis_hzb_desc(%d, %d) -> %d" % (width, height, rc))
     return d
+
+
+def texture_chain_bytes(format, width, height, mips):
+    """Bytes of a texture chain in the layout of ChordTexture (chordvis_texture_chain_bytes): RGBA8 or a TEXFMT_BC* format."""
+    n = C.c_uint64(0)
+    rc = lib.chordvis_texture_chain_bytes(format, width, height, mips, C.byref(n))
+    if rc != OK:
+        raise ChordvisError("chordvis_texture_chain_bytes(%d, %d, %d, %d) -> %d" % (format, width, height, mips, rc))
+    return n.value
 
 
 def material_constants():

@@ -117,7 +117,12 @@ class SceneDesc(C.Structure):
 
 
 class Texture(C.Structure):
-    _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("mipCount", C.c_uint32), ("pad", C.c_uint32)]
+    _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("mipCount", C.c_uint32), ("format", C.c_uint32)]
+
+
+# ChordTexture::format (CHORD_TEXFMT_*) and the bytes of a 4 x 4 block of the block formats
+TEXFMT_RGBA8, TEXFMT_BC1_RGB, TEXFMT_BC3, TEXFMT_BC4, TEXFMT_BC5 = 0, 1, 2, 3, 4
+BC_BLOCK_BYTES = {TEXFMT_BC1_RGB: 8, TEXFMT_BC3: 16, TEXFMT_BC4: 8, TEXFMT_BC5: 16}
 
 
 SAMPLER = np.dtype([("minFilter", u32), ("magFilter", u32), ("wrapS", u32), ("wrapT", u32)])
@@ -148,6 +153,112 @@ def mip_chain_rgba8(level0):
     return np.concatenate([l.reshape(-1) for l in levels]), len(levels)
 
 
+class TextureChain:
+    """A texture handed to Scene(textures=...) as a finished chain: `data` holds every level back to back in the layout of
+    ChordTexture (RGBA8 texels for format 0, 4 x 4 blocks for the TEXFMT_BC* formats), level 0 is width x height."""
+
+    def __init__(self, data, width, height, mips, format=TEXFMT_RGBA8):
+        self.data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        self.width, self.height, self.mips, self.format = int(width), int(height), int(mips), int(format)
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 4)
+
+
+def level_dims(width, height, mips):
+    """[(w, h)] of the levels of a chain."""
+    return [(max(1, width >> l), max(1, height >> l)) for l in range(mips)]
+
+
+def _channel_palette(a0, a1):
+    """(n, 8) values of alpha / single-channel blocks with endpoints a0, a1 (int64 arrays)."""
+    pal = np.zeros((len(a0), 8), dtype=np.int64)
+    pal[:, 0], pal[:, 1] = a0, a1
+    for k in range(2, 8):
+        six = ((6 - k) * a0 + (k - 1) * a1) // 5 if k < 6 else np.full_like(a0, 0 if k == 6 else 255)
+        pal[:, k] = np.where(a0 > a1, ((8 - k) * a0 + (k - 1) * a1) // 7, six)
+    return pal
+
+
+def _encode_channel(v, flip):
+    """v (n, 16) one channel of n blocks -> (n, 8) block bytes: a0 = the block's maximum and a1 = its minimum (the eight-value
+    mode), the other way round where `flip` (the six-value mode with its 0 and 255), every texel the nearest value."""
+    v = v.astype(np.int64)
+    hi, lo = v.max(axis=1), v.min(axis=1)
+    a0, a1 = np.where(flip, lo, hi), np.where(flip, hi, lo)
+    idx = np.abs(v[:, :, None] - _channel_palette(a0, a1)[:, None, :]).argmin(axis=2).astype(np.uint64)
+    bits = np.zeros(len(v), dtype=np.uint64)
+    for i in range(16):
+        bits |= idx[:, i] << np.uint64(3 * i)
+    out = np.zeros((len(v), 8), dtype=np.uint8)
+    out[:, 0], out[:, 1] = a0, a1
+    for j in range(6):
+        out[:, 2 + j] = (bits >> np.uint64(8 * j)) & np.uint64(0xFF)
+    return out
+
+
+def _encode_colour(rgb):
+    """rgb (n, 16, 3) -> (n, 8) colour block bytes: c0 = the block's per-channel maximum and c1 = its minimum in 5:6:5 (always
+    c0 > c1: the four-colour mode), every texel the nearest of the four colours."""
+    rgb = rgb.astype(np.int64)
+    q = lambda c: ((c[:, 0] >> 3) << 11) | ((c[:, 1] >> 2) << 5) | (c[:, 2] >> 3)
+    c0, c1 = q(rgb.max(axis=1)), q(rgb.min(axis=1))
+    same = c0 == c1
+    c1 = np.where(same & (c0 > 0), c0 - 1, c1)          # (a solid block: any second endpoint below the first)
+    c0 = np.where(same & (c0 == 0), 1, c0)
+
+    def expand(c):
+        r, g, b = c >> 11, (c >> 5) & 63, c & 31
+        return np.stack([(r << 3) | (r >> 2), (g << 2) | (g >> 4), (b << 3) | (b >> 2)], axis=1)
+    p0, p1 = expand(c0), expand(c1)
+    pal = np.stack([p0, p1, (2 * p0 + p1) // 3, (p0 + 2 * p1) // 3], axis=1)
+    idx = ((rgb[:, :, None, :] - pal[:, None, :, :]) ** 2).sum(axis=3).argmin(axis=2).astype(np.uint32)
+    bits = np.zeros(len(rgb), dtype=np.uint32)
+    for i in range(16):
+        bits |= idx[:, i] << np.uint32(2 * i)
+    out = np.zeros((len(rgb), 8), dtype=np.uint8)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = c0 & 0xFF, c0 >> 8, c1 & 0xFF, c1 >> 8
+    for j in range(4):
+        out[:, 4 + j] = (bits >> np.uint32(8 * j)) & np.uint32(0xFF)
+    return out
+
+
+def encode_bc(level_rgba8, format):
+    """A simple encoder for tests: the blocks (uint8, row-major, ceil(w / 4) x ceil(h / 4) of them) of one (h, w, 4) uint8 level in
+    a TEXFMT_BC* format.  Bounding-box endpoints, nearest index; always well-formed, never the three-colour mode; quality is not a
+    goal.  Channel blocks (BC3 alpha, BC4, BC5) alternate the order of a0 and a1 from block to block, so both of their modes occur.
+    Edge blocks repeat the level's last row / column."""
+    img = np.ascontiguousarray(level_rgba8, dtype=np.uint8)
+    h, w = img.shape[:2]
+    bh, bw = (h + 3) // 4, (w + 3) // 4
+    img = np.pad(img, ((0, bh * 4 - h), (0, bw * 4 - w), (0, 0)), mode="edge")
+    blocks = img.reshape(bh, 4, bw, 4, 4).transpose(0, 2, 1, 3, 4).reshape(-1, 16, 4)
+    flip = (np.arange(len(blocks)) & 1).astype(bool)
+    if format == TEXFMT_BC1_RGB:
+        out = _encode_colour(blocks[:, :, :3])
+    elif format == TEXFMT_BC3:
+        out = np.concatenate([_encode_channel(blocks[:, :, 3], flip), _encode_colour(blocks[:, :, :3])], axis=1)
+    elif format == TEXFMT_BC4:
+        out = _encode_channel(blocks[:, :, 0], flip)
+    elif format == TEXFMT_BC5:
+        out = np.concatenate([_encode_channel(blocks[:, :, 0], flip), _encode_channel(blocks[:, :, 1], ~flip)], axis=1)
+    else:
+        raise ValueError("encode_bc: format %r is not a block format" % (format,))
+    return np.ascontiguousarray(out).reshape(-1)
+
+
+def bc_chain(image, format):
+    """TextureChain of an (H, W, 4) uint8 image in a TEXFMT_BC* format: every level of mip_chain_rgba8, encoded by encode_bc."""
+    chain, mips = mip_chain_rgba8(image)
+    h, w = image.shape[:2]
+    out, off = [], 0
+    for lw, lh in level_dims(w, h, mips):
+        out.append(encode_bc(chain[off:off + lw * lh * 4].reshape(lh, lw, 4), format))
+        off += lw * lh * 4
+    return TextureChain(np.concatenate(out), w, h, mips, format)
+
+
 class HZBDesc(C.Structure):
     _fields_ = [
         ("srcWidth", C.c_uint32), ("srcHeight", C.c_uint32),
@@ -174,7 +285,8 @@ class Scene:
 
     def __init__(self, objects, primitives, materials, meshlets, groups, group_indices, meshlet_data, positions,
                  name="scene", texcoord0=None, textures=(), samplers=None, bvh_nodes=None, normals=None, tangents=None):
-        """textures: sequence of (H, W, 4) uint8 images (mip chains are built here); samplers: SAMPLER records; normals (n, 3) and
+        """textures: sequence of (H, W, 4) uint8 images (mip chains are built here) or TextureChain entries (finished chains, also
+        block-compressed: handed over as they are); samplers: SAMPLER records; normals (n, 3) and
         tangents (n, 4, w = handedness) float32 per vertex, or None (read only by chordvis_resolve_surface)."""
         self.name = name
         self.objects = np.ascontiguousarray(objects, dtype=OBJECT)
@@ -190,10 +302,11 @@ class Scene:
         self.normals = None if normals is None else np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
         self.tangents = None if tangents is None else np.ascontiguousarray(tangents, dtype=f32).reshape(-1, 4)
         self.texture_images = list(textures)
-        self._tex_chains = [mip_chain_rgba8(t) for t in self.texture_images]
+        self._tex_chains = [(t.data, t.mips) if isinstance(t, TextureChain) else mip_chain_rgba8(t) for t in self.texture_images]
         self._textures = (Texture * max(1, len(self._tex_chains)))()
         for i, (chain, mips) in enumerate(self._tex_chains):
-            self._textures[i] = Texture(chain.ctypes.data, self.texture_images[i].shape[1], self.texture_images[i].shape[0], mips, 0)
+            t = self.texture_images[i]
+            self._textures[i] = Texture(chain.ctypes.data, t.shape[1], t.shape[0], mips, t.format if isinstance(t, TextureChain) else TEXFMT_RGBA8)
         self.samplers = np.zeros(0, dtype=SAMPLER) if samplers is None else np.ascontiguousarray(samplers, dtype=SAMPLER)
         self._asset = AssetDesc(
             self.meshlets.ctypes.data, len(self.meshlets),

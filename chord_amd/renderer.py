@@ -61,6 +61,21 @@ class VisibilityRenderer:
         scene = self.scene if scene is None else scene
         self._check(L.lib.chordvis_upload_material_textures(self._ctx, C.byref(scene.desc)), "upload_material_textures")
 
+    def readback_material_texture(self, texture, level=0):
+        """(h, w, 4) uint8: the expanded texels of one level of a texture as chordvis_resolve_material reads them (after
+        upload_material_textures; block-compressed textures as the library decoded them)."""
+        t = self.scene.texture_images[texture]
+        h, w = max(1, t.shape[0] >> level), max(1, t.shape[1] >> level)
+        out = np.zeros((h, w, 4), dtype=np.uint8)
+        self._check(L.lib.chordvis_readback_material_texture(self._ctx, int(texture), int(level), out.ctypes.data), "readback_material_texture")
+        return out
+
+    def read_alpha_plane(self, count, offset=0):
+        """`count` bytes of the alpha plane the masked buckets sample, from byte `offset` (chordvis_debug_read 7)."""
+        out = np.zeros(int(count), dtype=np.uint8)
+        self._check(L.lib.chordvis_debug_read(self._ctx, 7, int(offset), int(count), out.ctypes.data), "debug_read")
+        return out
+
     def set_material_anisotropy(self, n):
         """Maximum anisotropy of the material resolve's sampler: 1 (default: the isotropic sampler), 2, 4, 8 or 16 taps along the
         longer derivative.  Per context; kept across upload_scene and upload_material_textures."""

@@ -900,6 +900,20 @@ def material_test_scene(width=320, height=200, lods=2, seed=3, position=(-6.5, 2
                           ground_uv=(96.0, 96.0), screen_scale=0.55)
 
 
+def with_textures(scene, textures):
+    """`scene` under other texture entries, one per texture of the scene: (H, W, 4) images or records.TextureChain (a finished
+    chain, e.g. records.bc_chain(image, T.TEXFMT_BC3): the texture block-compressed as the reference's material import stores
+    it).  Everything else is shared with `scene`."""
+    textures = list(textures)
+    assert len(textures) == len(scene.texture_images)
+    out = T.Scene(scene.objects, scene.primitives, scene.materials, scene.meshlets, scene.groups, scene.group_indices,
+                  scene.meshlet_data, scene.positions, name=scene.name, texcoord0=scene.texcoord0, textures=textures,
+                  samplers=scene.samplers, bvh_nodes=scene.bvh_nodes, normals=scene.normals, tangents=scene.tangents)
+    if hasattr(scene, "local_to_world"):
+        out.local_to_world = scene.local_to_world
+    return out
+
+
 def floor_under_camera(position=(0.3, 0.25, 0.2), front=(0.1, -0.6, -1.0), width=128, height=96):
     """One coarse 16 m floor patch (2 m cells) with the camera just above it: its triangles straddle
     the w = 0 plane and exercise the homogeneous clipper."""

@@ -567,6 +567,21 @@ int chordvis_resolve_surface(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, c
  * texture without data, wider or higher than 16384, or with more than 15 levels: CHORDVIS_E_INVALID, nothing kept (what an earlier
  * call kept is dropped too).  Dropped by the next chordvis_upload_scene.  Frames, culls and the other resolves do not read it. */
 int chordvis_upload_material_textures(ChordCtx* ctx, const ChordSceneDesc* scene);
+/* Block-compressed textures (ChordTexture::format = CHORD_TEXFMT_BC1_RGB / BC3 / BC4 / BC5).  Both upload calls take them: the
+ * compressed bytes of the textures they look at go to one staging buffer on the device, ONE kernel launch on the context's stream
+ * expands every level of every such texture into the texel store RGBA8 textures are copied to (chordvis_upload_material_textures:
+ * all four channels; chordvis_upload_scene: the alpha the masked buckets test -- BC3 decodes its alpha block, the other block
+ * formats are 255 throughout), and the staging buffer is freed after the synchronise: the calls stay synchronous, the offsets of
+ * every level are those of an RGBA8 texture of the same size, and nothing downstream knows the difference.  The decode is pinned
+ * (DESIGN.md 2 item 9(h)).  A format other than 0..4 on a texture a call looks at: CHORDVIS_E_INVALID, chordvis_last_error names
+ * the allowed values; textures nothing names are ignored, their format included.
+ * Size in bytes of a chain in the layout ChordTexture wants (host call, no context), for RGBA8 as well.  An unknown format, a zero
+ * width, height or mipCount, or NULL `bytes`: CHORDVIS_E_INVALID. */
+int chordvis_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t height, uint32_t mipCount, uint64_t* bytes);
+/* The expanded texels of one level of a texture as chordvis_resolve_material reads them (RGBA8, width x height of the level,
+ * row-major; RGBA8 textures too); synchronises.  CHORDVIS_E_INVALID when no material textures are uploaded, when no material of the
+ * scene names the texture, or when the level is not below its mipCount. */
+int chordvis_readback_material_texture(ChordCtx* ctx, uint32_t textureId, uint32_t level, uint8_t* hostRgba8);
 /* Caller-owned device images as in ChordResolveTargets.  Empty pixels, pixels whose id is not below the list's count and pixels
  * whose material's materialType is not kLightingType_GLTF_MetallicRoughnessPBR (1; base.h:423, lighting.hlsl:369) hold 0.
  * Float32, source order, one rounding per operation; the texture sampler is the pinned one of DESIGN.md 2 item 9 (isotropic level
@@ -655,7 +670,9 @@ int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 /* measurement / test aid: fills EVERY rank's chunk of the cull exchange buffer on this context for the current view (what the
  * all-gather would deliver), so that one rank of a sharded frame can be timed alone on one device (tools/shard_time.py) */
 int chordvis_debug_fill_cull_exchange(ChordCtx* ctx);
-/* debugging aid: raw read of an internal buffer (0 tile counts, 1 fixed bins, 2 chunk table, 3 bin pool, 4 / 5 32- / 48-byte records) */
+/* debugging aid: raw read of an internal buffer (0 tile counts, 1 fixed bins, 2 chunk table, 3 bin pool, 4 / 5 32- / 48-byte records,
+ * 7 the alpha plane the masked buckets sample: one byte per texel, every level of every texture a masked material samples, in
+ * texture order; CHORDVIS_E_INVALID when the scene has none) */
 int chordvis_debug_read(ChordCtx* ctx, int which, uint64_t offset, uint64_t bytes, void* host);
 /* debugging aid: non-zero words in the split-tile accumulation slabs (must be 0 between raster passes) */
 int chordvis_debug_slab_nonzero(ChordCtx* ctx, uint64_t* count);

@@ -218,9 +218,20 @@ typedef struct ChordSampler {
  * RGBA8, `mipCount` levels back to back starting with level 0 (level l is max(1, width >> l) x max(1, height >> l)).
  * ChordMaterial::baseColorId / baseColorSampler index ChordSceneDesc::textures / samplers (the reference's bindless ids);
  * an id >= textureCount reads as the reference's white fallback (alpha 1, asset_gltf.cpp:374). */
+/* ChordTexture::format.  0 is the layout above.  1..4 are the block formats the reference's material import stores its textures in
+ * (asset_gltf_material.cpp:80-110; written by mipmapCompressBC1/3/4/5, asset_texture_helper.cpp, through stb_dxt): `rgba8` then
+ * points at the blocks.  Level l is stored as ceil(w / 4) x ceil(h / 4) blocks, row-major, the levels back to back from level 0;
+ * texels of an edge block that fall outside the level are ignored.  The library expands the blocks on the GPU at upload into the
+ * same texel stores RGBA8 textures go to, by the pinned integer decode of DESIGN.md 2 item 9(h) (a fixed-function decoder may
+ * differ by one code in the interpolated values); the format says nothing about sRGB (the resolve decides that per slot). */
+#define CHORD_TEXFMT_RGBA8    0u
+#define CHORD_TEXFMT_BC1_RGB  1u  /*  8 bytes per block: colour; alpha always 255 (the reference uses the _RGB_ formats) */
+#define CHORD_TEXFMT_BC3      2u  /* 16 bytes per block: alpha block, then a colour block (always four-colour mode)      */
+#define CHORD_TEXFMT_BC4      3u  /*  8 bytes per block: one channel block -> (v, 0, 0, 255)                             */
+#define CHORD_TEXFMT_BC5      4u  /* 16 bytes per block: two channel blocks -> (r, g, 0, 255)                            */
 typedef struct ChordTexture {
-    const uint8_t* rgba8;
-    uint32_t width, height, mipCount, pad;
+    const uint8_t* rgba8;      /* the texels, or the blocks of a CHORD_TEXFMT_BC* chain */
+    uint32_t width, height, mipCount, format;
 } ChordTexture;
 
 /* One GLTFPrimitiveDatasBuffer (gltf.h:94-116): bindless ids -> host pointers. */
