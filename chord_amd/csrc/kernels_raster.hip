@@ -62,13 +62,10 @@ namespace chord {
 // block path: a block's bin slot and the block count travel in a single atomic), 2 = ticket of the slices of a split tile
 #define TC_BLOCKS 1u
 #define TC_TICKET 2u
-// Where alpha-tested triangles are scan-converted: 0 = in raster_masked_tile_kernel, a pass of their own in front of the tile kernel
-// (whose only instantiations are then the opaque ones); 1 = inside the tile kernel's MASKED instantiations, in a pass of their own
-// over the batch's units (the form of rounds 2-4, kept as a build switch for the A/B: profiles/r05_masked_variants.txt)
-#ifndef CHORD_MASKED_FUSED
-#define CHORD_MASKED_FUSED 1
-#endif
-#define TC_MASKED 3u            // 3 = the bin holds entries of alpha-tested triangles (a flag, plain stores: raster_masked_tile_kernel's work list)
+// 3 = the bin holds entries of alpha-tested triangles (a flag, plain stores).  Nothing reads it any more: it was the work list of a
+// masked pass of its own in front of the tile kernel, 37 % slower than the tile kernel's MASKED instantiations and deleted
+// (profiles/r05_masked_variants.txt).  The stores are part of live instruction streams; a later change can drop them.
+#define TC_MASKED 3u
 
 struct RasterParams {
     const uint32_t* count; const ChordDrawCmd* cmds;
@@ -389,9 +386,6 @@ template <class P>
 __device__ __forceinline__ void bin_alloc(const P& p, uint32_t tile, uint32_t slot)
 {
     if (slot == 0u && p.tileTouched) atomicOr(&p.tileTouched[tile >> 5], 1u << (tile & 31u));
-#ifdef EXP_NO_CHUNKS
-    return;
-#endif
     if (slot < p.binCap) return;
     const uint32_t o = slot - p.binCap, j = o >> CHORD_BIN_CHUNK_SHIFT;
     if (j >= p.binMaxChunks || (o & (CHORD_BIN_CHUNK - 1u)) != 0u) return;
@@ -409,9 +403,6 @@ template <class P>
 __device__ __forceinline__ void bin_put(const P& p, uint32_t tile, uint32_t slot, uint32_t gi)
 {
     // (tile < 4096 and the fixed part of a bin at most 2^20 entries: the index is a full-rate 24-bit multiply and fits 32 bits)
-#ifdef EXP_NO_CHUNKS
-    slot &= p.binCap - 1u;                                      // measurement only (wrong image): no entry ever lives in a pool chunk
-#endif
     if (slot < p.binCap) { p.tileBins[__umul24(tile, p.binCap) + slot] = gi; return; }
     const uint32_t o = slot - p.binCap, j = o >> CHORD_BIN_CHUNK_SHIFT;
     if (j >= p.binMaxChunks) { atomicOr(&p.counters->overflow, 1u); return; }
@@ -817,6 +808,61 @@ __device__ __forceinline__ void wave_bin_large(const P& e, const LargeLds& L, bo
     }
 }
 
+// ---- the vertex and triangle arithmetic of the set-up kernels --------------------------------------------------------------
+// The pieces that the record kernel (raster_setup_body), the block kernel (raster_setup_blocks_body) and the wide kernel
+// (raster_setup_wide_kernel) share: cluster header, draw command, object matrix (the wide kernel keeps its own loop), snap.  The three are bit-exact against the oracle
+// only while they say the same thing, and which of them a cluster meets is a run-time choice of the host.  The vertex transform, the
+// culls and the clip-or-set-up tail (mesh_raster.hlsl:84-179) are still written out in each of the three: as shared functions they
+// changed the register allocation of the wave-per-cluster bodies, which sit at 106 SGPRs, and the record kernel, held to 96 VGPRs by
+// its fifth wave per SIMD, spilled (16-28 bytes of scratch per lane) -- profiles/raster_kernel_resources.md.
+enum { K_NONE = 0, K_EMIT = 1, K_CLIP = 2 };
+#define WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+
+// Wave-uniform header of a cluster: its draw command and what the meshlet and object records say of it.
+// (scalar loads through the constant address space: the addresses are wave-uniform, and a vector load + v_readfirstlane per
+// dword was 26 VALU instructions per header -- the record kernel is bound by VALU issue on dense scenes like the block kernel)
+struct SetupHeader { uint32_t objectId, meshletId, slot, V, T, dataOffset, vertexBase, matFlags; };
+// meshlets / objStatic: the caller says where the scene's pointers come from -- the wave-per-cluster bodies re-read them from the
+// kernel-argument segment at each use (kernel_args: not held across the cluster loop), the wide kernel takes them from its parameters
+__device__ __forceinline__ SetupHeader load_setup_header(const DMeshlet* __restrict__ meshlets, const DObjStatic* __restrict__ objStatic,
+                                                         uint32_t objectId, uint32_t meshletId, uint32_t slot)
+{
+    SetupHeader h;
+    h.objectId = objectId; h.meshletId = meshletId; h.slot = slot;
+    const DMeshlet* __restrict__ mm = &meshlets[meshletId];
+    const uint32_t vt = scalar_load(&mm->vertexTriangleCount);
+    h.V = vt & 0xFFu; h.T = (vt >> 8) & 0xFFu;
+    h.dataOffset = scalar_load(&mm->dataOffset);
+    h.vertexBase = scalar_load(&mm->vertexBase);
+    h.matFlags = scalar_load(&objStatic[objectId].matFlags);
+    if (CHORD_MATFLAG_ALPHA(h.matFlags) >= CHORD_ALPHA_BLEND) h.T = 0u;   // blended: in no bucket of renderMesh (mesh_raster.cpp:224)
+    return h;
+}
+// the three words of command min(i, count - 1) of a list (a wave asks for headers past the end of its list: the last one again)
+__device__ __forceinline__ ChordDrawCmd load_command(const ChordDrawCmd* __restrict__ cmds, uint32_t count, uint32_t i)
+{
+    const uint32_t k = __builtin_amdgcn_readfirstlane(min(i, count - 1u));
+    const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(cmds + k);
+    ChordDrawCmd c;
+    c.objectId = scalar_load(cw); c.meshletId = scalar_load(cw + 1); c.slot = scalar_load(cw + 2);
+    return c;
+}
+// the object's matrix (wave-uniform: sixteen scalar loads)
+__device__ __forceinline__ Mat4 load_mvp(const DObjFrame* __restrict__ frames, uint32_t objectId)
+{
+    Mat4 m;
+    const float* __restrict__ mv = frames[objectId].mvp;
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int cc = 0; cc < 4; cc++) m.r[r][cc] = scalar_load(mv + r * 4 + cc);
+    return m;
+}
+
+// u or v -> 24.8 fixed-point pixels (extent: the target's width or height).  A vertex outside the guard band may overflow the
+// conversion: its triangles take the clipper and never read the result.
+__device__ __forceinline__ int32_t snap(float u, float extent) { return (int32_t)rintf((u * extent) * 256.0f); }
+
 // ---- clipper kernel (rare path) ---------------------------------------------------------------
 __device__ __forceinline__ float clip_dist(const f4& v, int k)
 {
@@ -910,8 +956,8 @@ __device__ __forceinline__ int clip_triangle(const Prm& p, const ClipLds<STRIDE>
         if (!(h.w > 0.0f)) return 0;
         const float u = h.x / fabsf(h.w) * 0.5f + 0.5f;
         const float v = h.y / fabsf(h.w) * -0.5f + 0.5f;
-        L.X(i) = (int32_t)rintf((u * p.W) * 256.0f);
-        L.Y(i) = (int32_t)rintf((v * p.H) * 256.0f);
+        L.X(i) = snap(u, p.W);
+        L.Y(i) = snap(v, p.H);
         L.D(i) = h.z / h.w;
     }
     return np;
@@ -994,7 +1040,8 @@ static_assert(2u * CLIP_MAXV * CLIP_SETUP_LANES * 4u <= LDS_VERTS && 4u * CLIP_M
               "a set-up wave's clip polygons fit its slices of sVert");
 
 // ---- the per-cluster setup kernel -------------------------------------------------------------
-enum { K_NONE = 0, K_EMIT = 1, K_CLIP = 2 };
+// phase clocks of the wave-per-cluster bodies (profile builds: RASTER_PROFILE and DBG_SETUP_CLOCKS; their locals sprof, sph, stp)
+#define SPHASE(i) do { if (sprof) { const unsigned long long tn = wall_clock64(); sph[i] += tn - stp; stp = tn; } } while (0)
 #define WIN CHORD_BLOCK_WIN
 #define DBG_NO_BLOCKS 32768u     // small clusters take the record path too (A/B of the pixel blocks; results identical)
 #define DBG_FORCE_BLOCKS 65536u  // the setup kernel takes its BLOCKS body whatever the cluster count (tests: small scenes)
@@ -1014,46 +1061,21 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
 
     const uint32_t listShard = (blockIdx.x * 4u + wave) % CHORD_LIST_SHARDS;
 
-    // Wave-uniform header of a cluster (scalar loads: the addresses are uniform).  The chain command -> meshlet /
-    // object records -> index stream -> positions is four dependent memory round trips per cluster; the header of
-    // the NEXT cluster is fetched while the current one is processed (command at the top of the iteration, records
+    // The chain command -> meshlet / object records -> index stream -> positions is four dependent memory round trips per cluster;
+    // the header of the NEXT cluster is fetched while the current one is processed (command at the top of the iteration, records
     // after the vertex phase), which takes two of them off the critical path.
-    struct Header {
-        uint32_t objectId, meshletId, slot, V, T, dataOffset, vertexBase, matFlags;
-        bool twoSided;
+    // (scene pointers: read from the kernel-argument segment where they are used, not held across the loop)
+    auto header_of = [&](uint32_t objectId, uint32_t meshletId, uint32_t slot) -> SetupHeader {
+        const RasterParams* q = kernel_args();
+        return load_setup_header(scalar_load(&q->meshlets), scalar_load(&q->objStatic), objectId, meshletId, slot);
     };
-    // (scalar loads through the constant address space: the addresses are wave-uniform, and a vector load + v_readfirstlane per
-    // dword was 26 VALU instructions per header -- the record kernel is bound by VALU issue on dense scenes like the block kernel)
-    auto header_of = [&](uint32_t objectId, uint32_t meshletId, uint32_t slot) -> Header {
-        Header h;
-        h.objectId = objectId; h.meshletId = meshletId; h.slot = slot;
-        const RasterParams* q = kernel_args();                  // (scene pointers: read where they are used, not held across the loop)
-        const DMeshlet* __restrict__ mm = &scalar_load(&q->meshlets)[h.meshletId];
-        const uint32_t vt = scalar_load(&mm->vertexTriangleCount);
-        h.V = vt & 0xFFu; h.T = (vt >> 8) & 0xFFu;
-        h.dataOffset = scalar_load(&mm->dataOffset);
-        h.vertexBase = scalar_load(&mm->vertexBase);
-        h.matFlags = scalar_load(&scalar_load(&q->objStatic)[h.objectId].matFlags);
-        h.twoSided = (h.matFlags & CHORD_MATFLAG_TWO_SIDED) != 0u;
-        if (CHORD_MATFLAG_ALPHA(h.matFlags) >= CHORD_ALPHA_BLEND) h.T = 0u;   // blended: in no bucket of renderMesh (mesh_raster.cpp:224)
-        return h;
-    };
-    auto load_header = [&](uint32_t i) -> Header {
-        const uint32_t k = __builtin_amdgcn_readfirstlane(min(i, count - 1u));
-        const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(cmds + k);
-        return header_of(scalar_load(cw), scalar_load(cw + 1), scalar_load(cw + 2));
+    auto load_header = [&](uint32_t i) -> SetupHeader {
+        const ChordDrawCmd cmd = load_command(cmds, count, i);
+        return header_of(cmd.objectId, cmd.meshletId, cmd.slot);
     };
     // (the object's matrix is fetched where the cluster's vertex phase starts, not an iteration ahead with the header: sixteen
     // more scalars alive across a whole cluster are lane spills -- a v_readlane each -- in a loop that sits at its 102 SGPRs)
-    auto mvp_of = [&](uint32_t objectId) -> Mat4 {
-        Mat4 m;
-        const float* __restrict__ mv = scalar_load(&kernel_args()->objFrame)[objectId].mvp;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int cc = 0; cc < 4; cc++) m.r[r][cc] = scalar_load(mv + r * 4 + cc);
-        return m;
-    };
+    auto mvp_of = [&](uint32_t objectId) -> Mat4 { return load_mvp(scalar_load(&kernel_args()->objFrame), objectId); };
     // Software pipeline over clusters (a wave's clusters k, k+1, ... are `stride` apart in the list).  While cluster k is
     // processed, k+1's header is resident, its vertex indices + triangle words are fetched after k's vertex phase, its
     // positions after k's triangle arithmetic, and k+2's header at the end -- so that at the top of an iteration the
@@ -1062,8 +1084,8 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
     const uint32_t stride = gridDim.x * 4u;
     uint32_t c = blockIdx.x * 4u + wave;
     if (c >= count) return;
-    Header hdr = firstCmdValid ? header_of(firstCmd0, firstCmd1, firstCmd2) : load_header(c);
-    Header hdrN = load_header(c + stride);
+    SetupHeader hdr = firstCmdValid ? header_of(firstCmd0, firstCmd1, firstCmd2) : load_header(c);
+    SetupHeader hdrN = load_header(c + stride);
     // (the first cluster's matrix travels with its index stream: behind it, a cluster's matrix is asked for while the cluster before it
     // stores its records -- see the end of the loop)
     Mat4 mvpNext = mvp_of(hdr.objectId);
@@ -1083,7 +1105,6 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
     }
     const bool sprof = RASTER_PROFILE && (p.debug & DBG_SETUP_CLOCKS) != 0;
     unsigned long long sph[5] = {0, 0, 0, 0, 0}, stp = sprof ? wall_clock64() : 0ull;
-#define SPHASE(i) do { if (sprof) { const unsigned long long tn = wall_clock64(); sph[i] += tn - stp; stp = tn; } } while (0)
     const uint32_t laneTop = lane;
     if (lane == 0u) sClip[0] = 0u;
     for (; c < count; c += stride) {
@@ -1092,7 +1113,7 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
         uint32_t lane = laneTop;
         asm volatile("" : "+v"(lane));
         const uint32_t slot = hdr.slot, V = hdr.V, T = hdr.T, dataOffset = hdr.dataOffset, vertexBase = hdr.vertexBase;
-        const bool twoSided = hdr.twoSided || p.depthOnly != 0u;                       // depth passes: cull mode NONE (mesh_raster.cpp:188-190)
+        const bool twoSided = (hdr.matFlags & CHORD_MATFLAG_TWO_SIDED) != 0u || p.depthOnly != 0u;                       // depth passes: cull mode NONE (mesh_raster.cpp:188-190)
         const bool masked = MASKED && CHORD_MATFLAG_ALPHA(hdr.matFlags) == CHORD_ALPHA_MASK;      // (wave-uniform)
         const Mat4 mvp = mvpNext;
         const uint32_t triWord[2] = {t0, t1};
@@ -1118,9 +1139,7 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
             vertex(i, pp[0], pp[1], pp[2]);
         }
         const bool allFast = __ballot(notFast) == 0ull;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        WAVE_LDS_SYNC();
         SPHASE(1);
         // next cluster: indices and triangle words now (its header has been resident for an iteration)
         const uint32_t* __restrict__ mdN = scalar_load(&kernel_args()->meshletData);
@@ -1180,9 +1199,9 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
                         // (snapped per use: keeping the snapped pair per vertex in LDS, as the block kernel does, makes the workgroup
                         // 32 KB -- this kernel holds 256 vertices per wave -- and costs it its fifth wave per SIMD: config 4's set-up
                         // 154 -> 227 us per frame, measured)
-                        ts.X[0] = (int32_t)rintf((u0 * p.W) * 256.0f); ts.Y[0] = (int32_t)rintf((v0 * p.H) * 256.0f);
-                        ts.X[1] = (int32_t)rintf((u1 * p.W) * 256.0f); ts.Y[1] = (int32_t)rintf((v1 * p.H) * 256.0f);
-                        ts.X[2] = (int32_t)rintf((u2 * p.W) * 256.0f); ts.Y[2] = (int32_t)rintf((v2 * p.H) * 256.0f);
+                        ts.X[0] = snap(u0, p.W); ts.Y[0] = snap(v0, p.H);
+                        ts.X[1] = snap(u1, p.W); ts.Y[1] = snap(v1, p.H);
+                        ts.X[2] = snap(u2, p.W); ts.Y[2] = snap(v2, p.H);
                         if (tri_setup(ts, twoSided, p.Wi, p.Hi) && owns_rect(p.shard, ts.px0, ts.py0, ts.px1, ts.py1)) {
                             kind = K_EMIT;
                             if (p.biasConst != 0.0f || p.biasSlope != 0.0f) { const float o = depth_bias(ts, d, p.biasConst, p.biasSlope); d[0] += o; d[1] += o; d[2] += o; }
@@ -1309,9 +1328,7 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
     }
     // the clip triangles of the wave's clusters: clipped, emitted and binned now, CLIP_SETUP_LANES at a time in the wave's slice of sVert
     // (in the loop, the clipper's registers came on top of the pipeline's: the kernel spilled)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    WAVE_LDS_SYNC();
     if (const uint32_t ranges = __builtin_amdgcn_readfirstlane(sClip[0])) {
         const SetupClipParams q = load_setup_clip_params();
         const ClipLds<CLIP_SETUP_LANES> L = {reinterpret_cast<float4*>(lX), lY, lY + 2u * CLIP_MAXV * CLIP_SETUP_LANES,
@@ -1327,7 +1344,6 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
         const uint32_t w = blockIdx.x * 4u + wave;
         if (w < CHORD_MAX_TILES * 8u / 5u) for (int i = 0; i < 5; i++) p.tilePhase[(size_t)w * 5u + i] = sph[i];
     }
-#undef SPHASE
 }
 
 // ---- the BLOCKS body, round 3: the same clusters -> the same blocks, organised around registers --------------------------
@@ -1342,7 +1358,6 @@ __device__ __forceinline__ void raster_setup_body(const RasterParams& p, const C
 // Wave-uniform records (draw command, meshlet header, object matrix) come through the scalar cache (constant address space:
 // s_load instead of a vector load + v_readfirstlane per dword), and a block leaves the wave as 16-byte stores of consecutive
 // word pairs (header | word 0, word 1 | word 2, ...): half the store instructions, whole 16-byte granules.
-struct SetupHeader { uint32_t objectId, meshletId, slot, V, T, dataOffset, vertexBase, matFlags; };
 
 // What the block kernel needs only when a cluster's blocks are written (a few lanes, once per cluster).  Kept in scalar
 // registers across the whole loop these 22 dwords push the kernel past its 102 SGPRs, and every scalar the compiler parks in a
@@ -1370,10 +1385,8 @@ __device__ __forceinline__ BlockEmitParams load_block_emit_params()
     return e;
 }
 
-#define WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
 // classification of one triangle of the cluster in LDS: kind, and for K_EMIT its pixel bounds (x0 | x1 << 16, y0 | y1 << 16)
-// and whether it is narrow (fits_compact).  The same culls and the same integers as cluster_records / raster_setup_body.
+// and whether it is narrow (fits_compact).  The same culls and the same integers as raster_setup_body.
 __device__ __forceinline__ int classify_triangle(const RasterParams& p, uint32_t t, uint32_t T, uint32_t packedIdx, bool twoSided, bool allFast,
                                                  const float* lX, const float* lY, const float* lW, const float* lU, const float* lV, const float* lD,
                                                  const int32_t* lSX, const int32_t* lSY, uint32_t& boxX, uint32_t& boxY, bool& narrow)
@@ -1508,28 +1521,9 @@ __device__ __forceinline__ void raster_setup_blocks_body(const RasterParams& p, 
     // registers -- the "hot parameters" variant of profiles/r03_block_kernel_variants.txt -- cost 3 %)
     auto kq = [&]() -> const RasterParams* { return kernel_args(); };
     auto header_at = [&](uint32_t i) -> SetupHeader {
-        const uint32_t k = __builtin_amdgcn_readfirstlane(min(i, count - 1u));
-        SetupHeader h;
         const RasterParams* q = kq();
-        const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(scalar_load(&q->cmds) + k);
-        h.objectId = scalar_load(cw); h.meshletId = scalar_load(cw + 1); h.slot = scalar_load(cw + 2);
-        const DMeshlet* __restrict__ mm = &scalar_load(&q->meshlets)[h.meshletId];
-        const uint32_t vt = scalar_load(&mm->vertexTriangleCount);
-        h.V = vt & 0xFFu; h.T = (vt >> 8) & 0xFFu;
-        h.dataOffset = scalar_load(&mm->dataOffset);
-        h.vertexBase = scalar_load(&mm->vertexBase);
-        h.matFlags = scalar_load(&scalar_load(&q->objStatic)[h.objectId].matFlags);
-        if (CHORD_MATFLAG_ALPHA(h.matFlags) >= CHORD_ALPHA_BLEND) h.T = 0u;   // blended: in no bucket of renderMesh (mesh_raster.cpp:224)
-        return h;
-    };
-    auto mvp_of = [&](uint32_t objectId) -> Mat4 {
-        Mat4 m;
-        const float* __restrict__ mv = scalar_load(&kq()->objFrame)[objectId].mvp;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int cc = 0; cc < 4; cc++) m.r[r][cc] = scalar_load(mv + r * 4 + cc);
-        return m;
+        const ChordDrawCmd cmd = load_command(scalar_load(&q->cmds), count, i);
+        return load_setup_header(scalar_load(&q->meshlets), scalar_load(&q->objStatic), cmd.objectId, cmd.meshletId, cmd.slot);
     };
     const uint32_t stride = gridDim.x * 4u;
     uint32_t c = blockIdx.x * 4u + wave;
@@ -1551,7 +1545,6 @@ __device__ __forceinline__ void raster_setup_blocks_body(const RasterParams& p, 
     }
     const bool sprof = RASTER_PROFILE && (p.debug & DBG_SETUP_CLOCKS) != 0;
     unsigned long long sph[5] = {0, 0, 0, 0, 0}, stp = sprof ? wall_clock64() : 0ull;
-#define SPHASE(i) do { if (sprof) { const unsigned long long tn = wall_clock64(); sph[i] += tn - stp; stp = tn; } } while (0)
     // (the per-cluster opaque lane index of raster_setup_body was measured here too: 78 -> 76 VGPRs, but 928 -> 946 VALU wave-instructions
     // per cluster -- this kernel is bound by VALU issue, and what was hoisted out of its loop was arithmetic it now repeats; not kept)
     for (; c < count; c += stride) {
@@ -1567,7 +1560,7 @@ __device__ __forceinline__ void raster_setup_blocks_body(const RasterParams& p, 
         if (!tooBig) {
             // (fetched here, not an iteration ahead: sixteen more scalar registers alive across the whole cluster cost more
             // lane spills than the other resident waves cover of this one scalar-cache round trip)
-            const Mat4 mvp = mvp_of(hdr.objectId);
+            const Mat4 mvp = load_mvp(scalar_load(&kq()->objFrame), hdr.objectId);
             auto vertex = [&](uint32_t i, float x, float y, float z) {
                 const f4 h = mul_mv(mvp, x, y, z, 1.0f);
                 const float aw = fabsf(h.w);
@@ -1576,7 +1569,7 @@ __device__ __forceinline__ void raster_setup_blocks_body(const RasterParams& p, 
                 lU[i] = u; lV[i] = v;
                 // snapped 24.8 coordinates of the vertex (mesh_raster setup: the values every triangle on it uses; a vertex outside
                 // the guard band may overflow the conversion -- its triangles take the clipper and never read them)
-                lSX[i] = (int32_t)rintf((u * p.W) * 256.0f); lSY[i] = (int32_t)rintf((v * p.H) * 256.0f);
+                lSX[i] = snap(u, p.W); lSY[i] = snap(v, p.H);
                 const bool fast = p.depthClamp ? in_fast_volume_xy(h) : in_fast_volume(h);
                 lD[i] = fast ? h.z / h.w : __builtin_nanf("");
                 notFast = notFast || !fast;
@@ -1857,28 +1850,15 @@ __global__ __launch_bounds__(256, SETUP_WIDE_WAVES) void raster_setup_wide_kerne
     }
     if (blockIdx.x >= count) return;
 
-    auto header_of = [&](uint32_t objectId, uint32_t meshletId, uint32_t slot) -> SetupHeader {
-        SetupHeader h;
-        h.objectId = objectId; h.meshletId = meshletId; h.slot = slot;
-        const DMeshlet* __restrict__ mm = &p.meshlets[meshletId];
-        const uint32_t vt = scalar_load(&mm->vertexTriangleCount);
-        h.V = vt & 0xFFu; h.T = (vt >> 8) & 0xFFu;
-        h.dataOffset = scalar_load(&mm->dataOffset);
-        h.vertexBase = scalar_load(&mm->vertexBase);
-        h.matFlags = scalar_load(&p.objStatic[objectId].matFlags);
-        if (CHORD_MATFLAG_ALPHA(h.matFlags) >= CHORD_ALPHA_BLEND) h.T = 0u;      // blended: in no bucket of renderMesh
-        return h;
-    };
     auto load_header = [&](uint32_t i) -> SetupHeader {
-        const uint32_t k = __builtin_amdgcn_readfirstlane(min(i, count - 1u));
-        const uint32_t* __restrict__ cw = reinterpret_cast<const uint32_t*>(cmds + k);
-        return header_of(scalar_load(cw), scalar_load(cw + 1), scalar_load(cw + 2));
+        const ChordDrawCmd cmd = load_command(cmds, count, i);
+        return load_setup_header(p.meshlets, p.objStatic, cmd.objectId, cmd.meshletId, cmd.slot);
     };
     float* lX = sV[0]; float* lY = sV[1]; float* lW = sV[2]; float* lU = sV[3]; float* lV = sV[4]; float* lD = sV[5];
     const LargeLds LL = {{sV[6], sV[7], sV[8], sV[9], sV[10]}};
     const uint32_t listShard = blockIdx.x % CHORD_LIST_SHARDS;
     const uint32_t t = wave * 32u + lane;                                        // this thread's triangle (lanes 0..31 of each wave)
-    SetupHeader hdr = firstValid ? header_of(f0, f1, f2) : load_header(blockIdx.x);
+    SetupHeader hdr = firstValid ? load_setup_header(p.meshlets, p.objStatic, f0, f1, f2) : load_header(blockIdx.x);
     if (tid == 0u) sClip[0] = 0u;
     for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {
         // the next cluster's header is on its way while this one is processed
@@ -1889,6 +1869,8 @@ __global__ __launch_bounds__(256, SETUP_WIDE_WAVES) void raster_setup_wide_kerne
         const uint32_t* __restrict__ md = p.meshletData;
         const bool hasTri = lane < 32u && t < T;
         const uint32_t triWord = hasTri ? md[dataOffset + V + t] : 0u;
+        // (not load_mvp: through the helper the compiler commutes and reorders nine instructions of this kernel's vertex transform;
+        // the loop is left as it was so that the kernel stays the program that was measured)
         Mat4 mvp;
         {
             const float* __restrict__ mv = p.objFrame[hdr.objectId].mvp;
@@ -1946,9 +1928,9 @@ __global__ __launch_bounds__(256, SETUP_WIDE_WAVES) void raster_setup_wide_kerne
                 if (d[0] != d[0] || d[1] != d[1] || d[2] != d[2]) {          // (NaN: a vertex outside the fast volume)
                     kind = K_CLIP;
                 } else {
-                    ts.X[0] = (int32_t)rintf((u0 * p.W) * 256.0f); ts.Y[0] = (int32_t)rintf((v0 * p.H) * 256.0f);
-                    ts.X[1] = (int32_t)rintf((u1 * p.W) * 256.0f); ts.Y[1] = (int32_t)rintf((v1 * p.H) * 256.0f);
-                    ts.X[2] = (int32_t)rintf((u2 * p.W) * 256.0f); ts.Y[2] = (int32_t)rintf((v2 * p.H) * 256.0f);
+                    ts.X[0] = snap(u0, p.W); ts.Y[0] = snap(v0, p.H);
+                    ts.X[1] = snap(u1, p.W); ts.Y[1] = snap(v1, p.H);
+                    ts.X[2] = snap(u2, p.W); ts.Y[2] = snap(v2, p.H);
                     if (tri_setup(ts, twoSided, p.Wi, p.Hi) && owns_rect(p.shard, ts.px0, ts.py0, ts.px1, ts.py1)) {
                         kind = K_EMIT;
                         if (p.biasConst != 0.0f || p.biasSlope != 0.0f) { const float o = depth_bias(ts, d, p.biasConst, p.biasSlope); d[0] += o; d[1] += o; d[2] += o; }
@@ -2252,9 +2234,6 @@ __global__ __launch_bounds__(256) void raster_clip_and_bin_large_kernel(RasterPa
 #ifndef TILE_ORDER_KEEP
 #define TILE_ORDER_KEEP 1          // 0: the schedule kernel runs in every pass whatever chordvis_set_tile_schedule_keep says (A/B builds)
 #endif
-#ifndef TILE_MAKE_NEXT
-#define TILE_MAKE_NEXT 1            // 0: the tile kernel's workgroup 0 does not make the next frame's schedule (compile experiments only: launch_raster still relies on it)
-#endif
 #ifndef TILE_DIRECT
 #define TILE_DIRECT 1              // 0: later passes of a frame keep their schedule kernel (A/B builds)
 #endif
@@ -2274,8 +2253,8 @@ __device__ __forceinline__ void tile_order_part(const RasterParams& p, uint2* __
     __syncthreads();
     // A tile's word: bin entries (clamped to the capacity) | bit 31: the bin holds pixel blocks (the tile kernel's block pass; it used to
     // ask the counter line itself, a dependent round trip per tile in front of its first bin fetch) | bit 30: the bin holds alpha-tested
-    // triangles -- on the first pass of a frame the masked pass (raster_masked_tile_kernel) has written the tile already and the tile
-    // kernel starts from those words instead of from zero.  ~0: not a work item of this rank (sharded frames: another rank's tiles --
+    // triangles (TC_MASKED; nothing reads the bit any more -- it told the tile kernel that the deleted masked pass had written the
+    // tile -- and a later change can drop it with the flag).  ~0: not a work item of this rank (sharded frames: another rank's tiles --
     // their bins are empty, and the clear pass must not touch them).
     // (Every thread asks for the lines of all its tiles at once and keeps ONE word per tile -- bucket, slices and position are worked out
     // again where they are needed: as a workgroup of the tile kernel this part is out of line and its registers are its own, but three
@@ -2582,7 +2561,7 @@ __device__ __forceinline__ uint32_t block_scan_tb(uint32_t v, uint32_t* waveSums
 #define SEG_SHIFT 6             // 64: one unit per row (16 / 32 were measured 3 % / 1 % slower on config 3: more units, same trips)
 #endif
 #define SEG (1 << SEG_SHIFT)
-// Units of masked (alpha-tested) triangles: MASKED_ROWS pixel rows x segments of MASKED_SEG pixels, MASKED_PIXELS_PER_TRIP pixels
+// Units of masked (alpha-tested) triangles: MASKED_ROWS pixel rows x segments of MASKED_SEG pixels, one pixel
 // per trip of the row loop.  Measured on street_4k_masked (profiles/r04_masked_variants.txt; tile kernel per frame): one row x 64
 // px x 1 pixel per trip 418 us; segments of 32 / 16 / 8 px 419 / 421 / 498 (and no different once a unit's set-up is one round
 // trip); two pixels per trip (taps of both in flight) 488: the masked instantiation sits at 128 VGPRs with scratch, more live taps
@@ -2595,9 +2574,6 @@ __device__ __forceinline__ uint32_t block_scan_tb(uint32_t v, uint32_t* waveSums
 #define MASKED_SEG_SHIFT 6
 #endif
 #define MASKED_SEG (1 << MASKED_SEG_SHIFT)
-#ifndef MASKED_PIXELS_PER_TRIP
-#define MASKED_PIXELS_PER_TRIP 1
-#endif
 #define ENTRY_WORDS 13            // word 12: record index of a masked triangle (its extension follows it)
 // entries per batch of the tile kernel's triangle pipeline (the first TILE_BATCH threads fetch and set up one bin entry each) and units
 // per round of its unit list: 512 / 4096 = 26 + 16 KB of LDS beside the 33-KB tile = two workgroups per CU; 256 / 1536 = 13 + 6 KB =
@@ -2805,19 +2781,10 @@ __device__ __forceinline__ void masked_rows(const RasterParams& p, unsigned long
         return keep ? (((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)u.payload) : 0ull;
     };
     unsigned long long* px = tileRow + lx0 + k0;
-#if MASKED_PIXELS_PER_TRIP == 2
-    for (int32_t k = k0; k <= k1; k += 2, E0 += 2 * st0, E1 += 2 * st1, E2 += 2 * st2, px += 2) {
-        const unsigned long long va = pixel(E0, E1, E2);
-        const unsigned long long vb = k + 1 <= k1 ? pixel(E0 + st0, E1 + st1, E2 + st2) : 0ull;
-        atomicMax(px, va);                                                        // ds_max_u64 (0 changes nothing)
-        atomicMax(px + 1, vb);                                                    // (at most the row's padding word when k + 1 > lx1)
-    }
-#else
     for (int32_t k = k0; k <= k1; k++, E0 += st0, E1 += st1, E2 += st2, px++) {
         if ((E0 | E1 | E2) < 0) continue;
-        atomicMax(px, pixel(E0, E1, E2));
+        atomicMax(px, pixel(E0, E1, E2));                                         // ds_max_u64 (0 changes nothing)
     }
-#endif
     }
 }
 
@@ -3135,28 +3102,8 @@ __device__ __forceinline__ void merge_blocks(unsigned long long* tile, const uns
             if (2u * g < N[j]) merge_block_word(tile, v.y, 2u * g, H[j], R[j]);                                           \
         }
     if (!todo) return;
-#ifndef MB_GROUPS
-#define MB_GROUPS 2
-#endif
-#if MB_GROUPS == 3
-    // three groups of four in flight (a build switch, measured in round 5 once the tile kernel had the registers: a group's loads
-    // covered by the merges of the two groups before it -- the tile kernel of a rank of the 8-rank config-5 frame 0.267 -> 0.291 ms,
-    // one GPU on subpixel_64m 136 -> 147 us: the third group's 20 scalars are lane spills inside the merge loop; not the default).
-    // An exhausted group picks nothing (n = 0), loads nothing and merges nothing, so the rotation needs no bookkeeping.
-    uint32_t hA[4], rA[4], nA[4], hB[4], rB[4], nB[4], hC[4], rC[4], nC[4];
-    const ulonglong2* srcA[4];
-    const ulonglong2* srcB[4];
-    const ulonglong2* srcC[4];
-    ulonglong2 aA[4], aB[4], aC[4];
-    MB_PICK(hA, rA, nA, srcA) MB_LOAD(aA, nA, srcA)
-    MB_PICK(hB, rB, nB, srcB) MB_LOAD(aB, nB, srcB)
-    MB_PICK(hC, rC, nC, srcC) MB_LOAD(aC, nC, srcC)
-    do {
-        MB_MERGE(aA, hA, rA, nA, srcA) MB_PICK(hA, rA, nA, srcA) MB_LOAD(aA, nA, srcA)
-        MB_MERGE(aB, hB, rB, nB, srcB) MB_PICK(hB, rB, nB, srcB) MB_LOAD(aB, nB, srcB)
-        MB_MERGE(aC, hC, rC, nC, srcC) MB_PICK(hC, rC, nC, srcC) MB_LOAD(aC, nC, srcC)
-    } while ((nA[0] | nB[0] | nC[0]) != 0u);
-#else
+    // two groups of four in flight (three were measured in round 5: the third group's 20 scalars are lane spills inside the merge
+    // loop, subpixel_64m 136 -> 147 us -- profiles/r05_tile_kernel_experiments.txt)
     uint32_t hA[4], rA[4], nA[4], hB[4], rB[4], nB[4];
     const ulonglong2* srcA[4];
     const ulonglong2* srcB[4];
@@ -3173,15 +3120,11 @@ __device__ __forceinline__ void merge_blocks(unsigned long long* tile, const uns
         MB_MERGE(aB, hB, rB, nB, srcB)
         if (!moreA) break;
     }
-#endif
 #undef MB_PICK
 #undef MB_LOAD
 #undef MB_MERGE
 }
 
-#ifndef TILE_DEEP_FETCH
-#define TILE_DEEP_FETCH 0               // 1: opaque instantiations fetch records two batches ahead (two register sets, batch loop unrolled by two) -- measured in round 5, no gain (profiles/r05_tile_kernel_experiments.txt item 9); 0: the round-2 form
-#endif
 // Direct passes that take only touched tiles (RasterParams::tileTouched): of the pass's mask, the tile of set bit k and the tile
 // behind set bit g - 1 (bits in tile order), and the number of set bits.  One 8-byte load per lane covers 4 096 tiles
 // (launch_raster takes this form for targets of at most that many); every wave of the workgroup works it out for itself -- no LDS,
@@ -3247,9 +3190,7 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     const uint32_t tilesAll = p.tilesX * p.tilesY;
     const uint32_t wg0 = blockIdx.x - (p.tileOrderNext != nullptr ? 1u : 0u);
     if (p.tileOrderNext && blockIdx.x == 0u) {
-#if TILE_MAKE_NEXT
         tile_order_next_part(kernel_args());
-#endif
         return;
     }
     const bool direct = p.orderKept == 2u;
@@ -3313,7 +3254,6 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     }
     if (p.orderAll && !p.clearTiles && nAll == 0u) continue;     // (a later pass's schedule that lists every tile: the untouched ones end here)
     const bool hasBlocks = (countWord >> 31) != 0u;               // (the order kernel saw pixel blocks in the tile's bin)
-    const bool preloaded = !CHORD_MASKED_FUSED && p.clearTiles && (countWord & 0x40000000u) != 0u;   // the masked pass wrote this tile (first pass of a frame)
     const int32_t tinyArea = nAll >= TINY_DENSE_MIN ? TINY_AREA_DENSE : TINY_AREA;
     // entries [lo, n) of the bin are this item's
     // (equal parts rounded up to whole batches: with the schedule's slice count -- ceil(entries / slice length), slice length
@@ -3351,7 +3291,10 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
 
     // ---- tile in: zero (first pass: this is the clear; un-fused later passes merge by max at tile-out), or the
     //      current words when a later pass must leave the finished tile in LDS for the fused HZB reduction ----
-    const bool rmw = (p.hzbFused && !p.clearTiles) || preloaded;
+    // (an assignment under a branch, not `p.hzbFused && !p.clearTiles`: the same value, but the expression form moves two of the kernel's
+    // scalar lane spills -- this spelling keeps the instruction stream the deleted `|| preloaded` term left behind)
+    bool rmw = false;
+    if (p.hzbFused && !p.clearTiles) rmw = true;
     // slices of a split tile start from zero; when the tile must leave this kernel complete (first pass, fused HZB)
     // they meet in memory and the last one to arrive merges them (below)
     const bool mergeSlices = slices > 1u && (p.clearTiles || rmw);
@@ -3384,8 +3327,8 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     } while (0)
     uint32_t idxNext = 0xFFFFFFFFu, nameNext = 0xFFFFFFFFu;
     uint4 nq0 = make_uint4(0, 0, 0, 0), nq1 = nq0, nq2 = nq0;
-    // (pixel blocks have a pass of their own below, alpha-tested triangles a kernel of their own: neither is a record of this pipeline)
-    auto record_name = [](uint32_t w) -> uint32_t { return (w >= CHORD_REC_BLOCK || (!(MASKED && CHORD_MASKED_FUSED) && (w & 0xE0000000u) == CHORD_REC_MASKED)) ? 0xFFFFFFFFu : w; };
+    // (pixel blocks have a pass of their own below; alpha-tested triangles are records of the MASKED instantiations' pipeline only)
+    auto record_name = [](uint32_t w) -> uint32_t { return (w >= CHORD_REC_BLOCK || (!MASKED && (w & 0xE0000000u) == CHORD_REC_MASKED)) ? 0xFFFFFFFFu : w; };
     if (early) {
         nameNext = record_name(word0);                                          // (binEntry of an entry of the fixed bin)
         if (nameNext != 0xFFFFFFFFu) FETCH_REC(nameNext, nq0, nq1, nq2);        // record of batch 0
@@ -3584,37 +3527,6 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
         PHASE(4);
     };
     uint32_t batchNo = 0;
-    if constexpr (TILE_DEEP_FETCH && !MASKED) {
-        // (a build switch, off: measured and not kept)  Records TWO batches ahead (opaque instantiations: 103 VGPRs leave room for a
-        // second set of record registers; the masked ones sit at 128).  The phase clocks of the profiling build put 44 % of the time
-        // of config 4's dense tiles into the wait for a batch's records (profiles/r05_tile_profile_config4.txt) -- with two batches
-        // of cover instead of one the product kernel takes exactly as long (config 4: tile 161.6 vs 161.3 us per frame; config 3
-        // +1 %: 115 VGPRs and 30 % more code), so that wait is the profiling build's own barrier in front of every clock, not latency
-        // the product kernel is exposed to.  Two register sets alternate, unrolled by two: a copy from set to set would make the
-        // compiler wait for the younger load at the copy.  Set A holds the record of batch 0 (fetched above), set B takes batch
-        // 1's, the bin entries run three batches ahead.
-        uint32_t nameA = nameNext, nameB = idxNext;
-        uint4 b0 = make_uint4(0, 0, 0, 0), b1 = b0, b2 = b0;
-        if (nameB != 0xFFFFFFFFu) FETCH_REC(nameB, b0, b1, b2);                  // record of batch 1
-        uint32_t idx = entryThread && k0 + 2u * TILE_BATCH < n ? binEntry(k0 + 2u * TILE_BATCH) : 0xFFFFFFFFu;   // bin entry of batch 2
-        for (uint32_t base = lo; base < n;) {
-            window_advance(base);
-            uint32_t rows = batch_setup(nq0, nq1, nq2, nameA);
-            nameA = idx;
-            if (nameA != 0xFFFFFFFFu) FETCH_REC(nameA, nq0, nq1, nq2);          // record of batch b + 2 into the set just read
-            idx = entryThread && base + tix + 3u * TILE_BATCH < n ? binEntry(base + tix + 3u * TILE_BATCH) : 0xFFFFFFFFu;
-            batch_units(rows, batchNo);
-            base += TILE_BATCH; batchNo++;
-            if (base >= n) break;
-            window_advance(base);
-            rows = batch_setup(b0, b1, b2, nameB);
-            nameB = idx;
-            if (nameB != 0xFFFFFFFFu) FETCH_REC(nameB, b0, b1, b2);
-            idx = entryThread && base + tix + 3u * TILE_BATCH < n ? binEntry(base + tix + 3u * TILE_BATCH) : 0xFFFFFFFFu;
-            batch_units(rows, batchNo);
-            base += TILE_BATCH; batchNo++;
-        }
-    } else
     for (uint32_t base = lo; base < n; base += TILE_BATCH, batchNo++) {
         window_advance(base);
         const uint32_t k = base + tix;
@@ -3693,140 +3605,6 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
 #undef wgs
 #undef TILE_SKEW
 
-// ---- alpha-tested (masked) triangles: a pass of their own (mesh_raster.hlsl:34-38,107-112,198-204) ---------------------------------
-// Until round 4 the masked row units ran inside raster_tile_kernel: every masked instantiation of it sat at 128 VGPRs with
-// 144-240 bytes of scratch per lane (the texture fetch next to the whole opaque batch pipeline), the opaque triangles of a masked
-// scene paid for the pass structure (no tiny-triangle path, an extension fetch per unit: 37 us per frame on street_4k_masked), and
-// nothing that keeps a second pixel's taps in flight fitted.  Now a bin entry says by itself that it names an alpha-tested
-// triangle (CHORD_REC_MASKED), the tile kernel skips such entries -- its only instantiations are the opaque ones --, and this
-// kernel, launched between the binning and the tile schedule, scan-converts them: one workgroup per tile whose counter line
-// carries the TC_MASKED flag, the tile in LDS from zero, the entries set up exactly as before (entry_store, masked_rows: the
-// arithmetic is untouched), row units dealt out densely.  On the first pass of a frame the finished tile is WRITTEN (plain
-// 16-byte stores) and the tile kernel, told by the tile schedule (bit 30 of the work item), starts from those words instead of
-// from zero; on later passes the touched pixels are merged with device-scope atomicMax and the tile kernel reads the tile back
-// as it does anyway.  The 64-bit max is order-independent, so which kernel merges a fragment first changes nothing.
-// Price: a masked tile's 32 KB once out and once in on the first pass, and one more launch per pass of a scene with alpha-tested
-// materials; scenes without them launch nothing of this.
-#if !CHORD_MASKED_FUSED && TILE_BATCH != TB
-#error "the separate masked pass sets up one entry per thread of its workgroup: TILE_BATCH must be TB"
-#endif
-#if TILE_BATCH == TB
-template <bool SH, bool DEPTH>
-__global__ __launch_bounds__(TB, 4) void raster_masked_tile_kernel(RasterParams p)
-{
-    __shared__ __align__(16) unsigned long long tile[TILE * TPITCH];   // 32.5 KB
-    __shared__ EntrySoA prm;                                     // 26 KB
-    __shared__ uint32_t unitList[UNIT_CAP];                      // 16 KB
-    __shared__ uint32_t waveSums[2][TB / 64];
-    __shared__ uint32_t chunkTab[64];
-    // work items: the tile schedule's (heaviest bins first: the masked pass ends with light tiles, like the tile kernel); an item
-    // without the masked flag -- or a further slice of a split tile -- is none of this pass's business
-    // (one workgroup per tile of the target strides over the list: a frame with split tiles has more items than tiles)
-    const uint32_t active = p.tileOrder[0].x;
-    for (uint32_t oi = blockIdx.x; oi < active; oi += gridDim.x) {
-    const uint2 item = p.tileOrder[1u + oi];
-    if ((item.y & 0x40000000u) == 0u || ((item.x >> 12) & 0x3FFu) != 0u) continue;
-    const uint32_t tileId = item.x & 0xFFFu;
-    const uint32_t n = item.y & 0x3FFFFFFFu;                      // (clamped to the bin capacity by the schedule)
-    const int32_t ox = (int32_t)(tileId % p.tilesX) * TILE, oy = (int32_t)(tileId / p.tilesX) * TILE;
-    const int32_t tw = min(TILE, p.Wi - ox), th = min(TILE, p.Hi - oy);
-    const bool noPixels = ABL(p, DBG_NO_PIXELS);
-    for (uint32_t i = threadIdx.x; i < TILE * TPITCH / 2; i += TB) reinterpret_cast<ulonglong2*>(tile)[i] = make_ulonglong2(0ull, 0ull);
-    const uint32_t* bin = p.tileBins + (size_t)tileId * p.binCap;
-    const uint32_t wideLimit = min(p.triCap * CHORD_LIST_SHARDS, CHORD_REC_WIDE_INDEX);
-    uint32_t batch = 0;
-    // the bin in segments: its fixed part, then windows of 64 pool chunks (their names through chunkTab, as in the tile kernel)
-    for (uint32_t segLo = 0; segLo < n;) {
-        uint32_t segHi, chunk0 = 0;
-        if (segLo < p.binCap) segHi = min(n, p.binCap);
-        else {
-            chunk0 = (segLo - p.binCap) >> CHORD_BIN_CHUNK_SHIFT;
-            segHi = min(n, segLo + 64u * CHORD_BIN_CHUNK);
-            __syncthreads();                                      // (the previous window's readers are done)
-            for (uint32_t j = threadIdx.x; j < 64u; j += TB) {
-                const unsigned long long e = chunk0 + j < p.binMaxChunks ? p.binChunkTab[(size_t)tileId * p.binMaxChunks + chunk0 + j] : 0ull;
-                chunkTab[j] = (uint32_t)(e >> 32) == p.binStamp ? (uint32_t)e : CHORD_BIN_CHUNK_INVALID;
-            }
-        }
-        __syncthreads();                                          // the zeroed tile / the chunk names are visible
-        auto binWord = [&](uint32_t k) -> uint32_t {
-            if (k < p.binCap) return bin[k];
-            const uint32_t o = k - p.binCap, cj = (o >> CHORD_BIN_CHUNK_SHIFT) - chunk0;
-            const uint32_t id = cj < 64u ? chunkTab[cj] : CHORD_BIN_CHUNK_INVALID;
-            return id == CHORD_BIN_CHUNK_INVALID ? 0xFFFFFFFFu : p.binPool[(size_t)id * CHORD_BIN_CHUNK + (o & (CHORD_BIN_CHUNK - 1u))];
-        };
-        uint32_t wNext = segLo + threadIdx.x < segHi ? binWord(segLo + threadIdx.x) : 0xFFFFFFFFu;
-        for (uint32_t base = segLo; base < segHi; base += TB, batch++) {
-            const uint32_t w = wNext;
-            wNext = base + TB + threadIdx.x < segHi ? binWord(base + TB + threadIdx.x) : 0xFFFFFFFFu;
-            const uint32_t idx = w & CHORD_REC_WIDE_INDEX;
-            uint32_t units = 0;
-            if ((w & 0xE0000000u) == CHORD_REC_MASKED && idx < wideLimit) {
-                const uint4* src = reinterpret_cast<const uint4*>(&p.tris[idx]);
-                const uint4 q0 = src[0], q1 = src[1], q2 = src[2];
-                TriRec r;
-                r.X[0] = (int32_t)q0.x; r.X[1] = (int32_t)q0.y; r.X[2] = (int32_t)q0.z; r.Y[0] = (int32_t)q0.w;
-                r.Y[1] = (int32_t)q1.x; r.Y[2] = (int32_t)q1.y;
-                r.d[0] = __uint_as_float(q1.z); r.d[1] = __uint_as_float(q1.w); r.d[2] = __uint_as_float(q2.x);
-                r.payload = q2.y; r.twoSided = q2.z; r.pad = q2.w;
-                TriSetup ts;
-                tri_setup_from_record(ts, r, p.Wi, p.Hi);
-                const int32_t x0 = max(ts.px0, ox), y0 = max(ts.py0, oy);
-                const int32_t x1 = min(ts.px1, ox + tw - 1), y1 = min(ts.py1, oy + th - 1);
-                if (x1 >= x0 && y1 >= y0) units = entry_store(prm, threadIdx.x, ts, narrow_extent(ts), ox, oy, x0, y0, x1, y1, true, idx);
-            }
-            uint32_t total;
-            const uint32_t off = block_scan_tb(units, waveSums[batch & 1u], &total);   // (its barrier also publishes the entries)
-            for (uint32_t r0 = 0; r0 < total; r0 += UNIT_CAP) {
-                if (units) {
-                    const uint32_t box = prm.w[11][threadIdx.x];
-                    const uint32_t nseg = ((((box >> 12) & 63u) - (box & 63u)) >> MASKED_SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
-                    const uint32_t lo2 = max(off, r0), hi2 = min(off + units, r0 + UNIT_CAP);
-                    if (lo2 < hi2) {
-                        const uint32_t j = lo2 - off, g = j / nseg;
-                        uint32_t row = y0l + g * MASKED_ROWS, seg = j - g * nseg;
-                        for (uint32_t u = lo2; u < hi2; u++) {
-                            unitList[u - r0] = threadIdx.x | (row << 9) | (seg << 15);
-                            if (++seg == nseg) { seg = 0u; row += MASKED_ROWS; }
-                        }
-                    }
-                }
-                __syncthreads();
-                const uint32_t nr = min(total - r0, (uint32_t)UNIT_CAP);
-                for (uint32_t ui = threadIdx.x; ui < nr; ui += TB) {
-                    const uint32_t d = unitList[ui];
-                    entry_unit_masked<DEPTH>(p, prm, tile, d & 511u, (d >> 9) & 63u, (d >> 15) & 7u, ox, oy, noPixels);
-                }
-                if (r0 + UNIT_CAP < total) __syncthreads();       // the list is rewritten by the next round
-            }
-            if (total) __syncthreads();                           // prm / the unit list are rewritten by the next batch
-        }
-        segLo = segHi;
-    }
-    __syncthreads();
-    // ---- tile out: the whole tile on the first pass of a frame (the tile kernel starts from it), the touched pixels otherwise ----
-    const uint32_t visBase = SH ? p.shard.tileSlot[tileId] << (2 * TILE_SHIFT) : (uint32_t)oy * (uint32_t)p.Wi + (uint32_t)ox;
-    const uint32_t visPitch = SH ? (uint32_t)TILE : (uint32_t)p.Wi;
-    if (p.clearTiles) {
-        for (uint32_t i = threadIdx.x; i < TILE * TILE / 2; i += TB) {
-            const int32_t ly = (int32_t)(i >> (TILE_SHIFT - 1)), lx = (int32_t)(i & (TILE / 2 - 1)) * 2;
-            if (ly >= th || lx >= tw) continue;
-            const ulonglong2 v = make_ulonglong2(tile[ly * TPITCH + lx], tile[ly * TPITCH + lx + 1]);
-            unsigned long long* dst = p.vis + (size_t)(visBase + (uint32_t)ly * visPitch + (uint32_t)lx);
-            if (lx + 1 < tw) *reinterpret_cast<ulonglong2*>(dst) = v;
-            else dst[0] = v.x;
-        }
-    } else {
-        for (uint32_t i = threadIdx.x; i < TILE * TILE; i += TB) {
-            const int32_t ly = (int32_t)(i >> TILE_SHIFT), lx = (int32_t)(i & (TILE - 1));
-            const unsigned long long v = tile[ly * TPITCH + lx];
-            if (v != 0ull && ly < th && lx < tw) atomicMax(p.vis + (size_t)(visBase + (uint32_t)ly * visPitch + (uint32_t)lx), v);
-        }
-    }
-    __syncthreads();                                              // the LDS tile is reused by the next item
-    }
-}
-#endif
 
 // ---- launcher ---------------------------------------------------------------------------------
 hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
@@ -3963,7 +3741,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     static const bool directOn = [] { const char* e = getenv("CHORDVIS_TILE_DIRECT"); return !e || atoi(e) != 0; }();
     // (laterOk: a read-modify-write pass of a frame with the HZB fused into its tile-out -- what the direct form and the kept schedule of
     // a later pass are written for)
-    const bool laterOk = c->inFrame && !clearTiles && p.hzbFused && !c->depthOnly && CHORD_MASKED_FUSED && c->dBinHint && !(c->debugFlags & ~(DBG_NO_BLOCKS | DBG_FORCE_BLOCKS | DBG_FORCE_HOT | 524288u));
+    const bool laterOk = c->inFrame && !clearTiles && p.hzbFused && !c->depthOnly && c->dBinHint && !(c->debugFlags & ~(DBG_NO_BLOCKS | DBG_FORCE_BLOCKS | DBG_FORCE_HOT | 524288u));
     if (laterOk) p.heavyHint = c->dBinHint + 4 + pass;
     if (TILE_DIRECT && directOn && laterOk) {
         const uint32_t heavySeen = c->hBinHint[4 + pass], lightSeen = c->hBinHint[6 + pass];
@@ -4043,7 +3821,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     p.orderAll = 0u; p.tileOrderNext = nullptr;
     static const bool keepLaterOn = [] { const char* e = getenv("CHORDVIS_TILE_KEEP_LATER"); return !e || atoi(e) != 0; }();
     static const bool nextOn = [] { const char* e = getenv("CHORDVIS_TILE_NEXT"); return !e || atoi(e) != 0; }();
-    const bool keepOk = TILE_ORDER_KEEP && c->orderKeepFrames && CHORD_MASKED_FUSED && c->inFrame && !c->depthOnly && !(c->debugFlags & ~524288u);
+    const bool keepOk = TILE_ORDER_KEEP && c->orderKeepFrames && c->inFrame && !c->depthOnly && !(c->debugFlags & ~524288u);
     int slot = -1;
     if (keepOk && clearTiles && pass == 0u && c->dTileOrderKeep) slot = 0;
     else if (keepOk && keepLaterOn && laterOk && pass == 1u && c->dTileOrderKeep1) slot = 1;
@@ -4069,15 +3847,6 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
         } else p.orderAll = 0u;
     }
     if (makeOrder) CHORD_LAUNCH(c, raster_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, p);
-#if !CHORD_MASKED_FUSED
-    if (c->anyMasked) {
-        // alpha-tested triangles: their own pass over the scheduled tiles whose bins hold any (raster_masked_tile_kernel)
-        const uint32_t items = tiles;                                     // (the workgroups stride over the device-side item list)
-        if (c->depthClamp && !sh) CHORD_LAUNCH(c, (raster_masked_tile_kernel<false, true>), dim3(items), dim3(TB), 0, c->stream, p);
-        else if (sh)              CHORD_LAUNCH(c, (raster_masked_tile_kernel<true, false>), dim3(items), dim3(TB), 0, c->stream, p);
-        else                      CHORD_LAUNCH(c, (raster_masked_tile_kernel<false, false>), dim3(items), dim3(TB), 0, c->stream, p);
-    }
-#endif
     stamp(c, S_R_CLIP);
     // first pass of a frame: every tile is written, one block each, dispatched heaviest first; later passes touch
     // few tiles: one resident wave of blocks strides over the (device-side) active list
@@ -4090,15 +3859,13 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     const uint32_t slots = (uint32_t)c->numCUs * (CHORD_TILE_SHIFT == 6 ? 2u : 6u);
     const uint32_t tileBlocks = (p.tileOrderNext ? 1u : 0u) + ((clearTiles || (p.orderKept == 2u && !p.tileTouched) || p.orderAll) ? ((sh && clearTiles) ? min(tiles, max(c->shard.slotsPerRank, p.tileSlots + p.tileSlots / 2u)) : tiles)
                                                                : min(tiles, p.tileTouched && touchedEnv > 1 ? (uint32_t)touchedEnv : slots));
-    // (the tile kernel's instantiations are the opaque ones: alpha-tested triangles were scan-converted by the masked pass above)
-#if CHORD_MASKED_FUSED
+    // (scenes with alpha-tested materials take the MASKED instantiations, which scan-convert those triangles in a pass of their own
+    // over the batch's units)
     if (c->anyMasked) {
         if (c->depthClamp && !sh) CHORD_LAUNCH(c, (raster_tile_kernel<false, true, true>), dim3(tileBlocks), dim3(TB), 0, c->stream, p);
         else if (sh)              CHORD_LAUNCH(c, (raster_tile_kernel<true, true, false>), dim3(tileBlocks), dim3(TB), 0, c->stream, p);
         else                      CHORD_LAUNCH(c, (raster_tile_kernel<false, true, false>), dim3(tileBlocks), dim3(TB), 0, c->stream, p);
-    } else
-#endif
-    if (c->depthClamp && !sh) {
+    } else if (c->depthClamp && !sh) {
         CHORD_LAUNCH(c, (raster_tile_kernel<false, false, true>), dim3(tileBlocks), dim3(TB), 0, c->stream, p);
     } else {
         if (sh) CHORD_LAUNCH(c, (raster_tile_kernel<true, false, false>), dim3(tileBlocks), dim3(TB), 0, c->stream, p);
