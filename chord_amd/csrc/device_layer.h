@@ -243,8 +243,8 @@ struct TriRecC {
 #define CHORD_REC_BLOCK 0xC0000000u
 #define CHORD_REC_INDEX_MASK 0x3FFFFFFFu
 // A bin entry that names the 48-byte record of an alpha-tested (masked) triangle: CHORD_REC_WIDE with bit 29 set.  Such entries are
-// scan-converted by a pass of their own (raster_masked_tile_kernel) and skipped by the tile kernel, which therefore needs to look at
-// nothing but the bin word.  Indices of the 48-byte list stay below 2^29 (chordvis_set_limits caps the list at 0x7FFFFFC0 / 4 records).
+// scan-converted, alpha test included, by the MASKED instantiation of the tile kernel in the bin's order; the other instantiation
+// skips them, and needs to look at nothing but the bin word to do so.  Indices of the 48-byte list stay below 2^29 (chordvis_set_limits caps the list at 0x7FFFFFC0 / 4 records).
 #define CHORD_REC_MASKED 0xA0000000u
 #define CHORD_REC_WIDE_INDEX 0x1FFFFFFFu
 #define CHORD_BLOCK_WIN 16
