@@ -236,3 +236,150 @@ def moving_sequence(scene, cams, flags=ALL_FLAGS, frames=None):
         want = orc.frame(scene, view, iv, flags, prev_hzb_min=prev_hzb)
         yield k, view, iv, want
         prev_view, prev_hzb = view, want["hzb_min"]
+
+
+# ---- synthetic, caller-owned visibility images: what the image-reading kernels are never shown by a rasterised frame ----
+
+F32_ONE = 0x3F800000
+# per region kind, the weights of the value classes (zero, one, wide, normal, tie, subnormal, tiny) of synthetic_depth
+_DEPTH_KINDS = np.array([[0.40, 0.08, 0.12, 0.10, 0.15, 0.08, 0.07],      # 1: the full mix
+                         [0.00, 0.00, 0.00, 0.55, 0.45, 0.00, 0.00],      # 2: binary16 normals, no 0.0 and no 1.0
+                         [0.00, 0.00, 0.00, 0.20, 0.20, 0.60, 0.00],      # 3: mostly binary16 subnormals, nothing that rounds to 0 but a tie
+                         [0.00, 0.13, 0.00, 0.45, 0.42, 0.00, 0.00]])     # 4: just under 1.0, and 1.0
+
+
+def synthetic_depth(w, h, seed):
+    """float32[(h, w)] depths in [0, 1], seeded.  Every pixel draws its value from one of seven classes:
+      zero       exactly 0.0                                         one   exactly 1.0
+      wide       random mantissa, exponent 2^-57 .. 2^-1 (far below the binary16 subnormal range up to just under 1.0)
+      normal     random mantissa, exponent inside the binary16 normal range, between the floor and the top of the pixel's 64-pixel
+                 block and region kind
+      tie        a binary16 normal's float bits with bit 12 set and the lower bits clear -- exactly half way to the next binary16 --
+                 or the float one ulp below or above it: round-to-nearest-even differs from truncation on the tie and above, and
+                 from round-half-up on the tie after an even binary16
+      subnormal  2^-24 .. 2^-14 with a random mantissa, or the tie (k + 1/2) 2^-24 between two binary16 subnormals (k = 0: between
+                 0 and the smallest) and its two float neighbours
+      tiny       2^-87 .. 2^-25: below half of the smallest binary16 subnormal
+    The class weights are not the same everywhere: about 10 % of all pixels are 0.0 and about 5 % are 1.0, but they sit in some
+    regions only (a 4 x 4 grid of cells of different kinds, one kind a patchwork of 16-pixel blocks), and the normals of a 64-pixel
+    block share an exponent range.  With the same weights at every pixel every texel from level 2 up would be min 0.0 / max 1.0
+    and the upper levels of a chain would be checked on one value."""
+    rng = np.random.default_rng([int(seed), int(w), int(h)])
+    ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+    coarse = rng.permutation(np.arange(16) % 5).reshape(4, 4)               # every kind in at least three cells
+    fine = rng.integers(1, 5, ((h + 15) // 16, (w + 15) // 16))
+    kind = coarse[ys * 4 // h, xs * 4 // w]
+    kind = np.where(kind == 0, fine[ys // 16, xs // 16], kind).ravel()
+    floor = rng.integers(113, 126, ((h + 63) // 64, (w + 63) // 64))[ys // 64, xs // 64].ravel().astype(np.uint32)
+    top = np.minimum(floor + np.uint32(3), np.uint32(126))                  # kind 2: a block's normals span four exponents
+    top[kind == 1] = 126
+    floor[kind == 3], top[kind == 3] = 113, 115
+    floor[kind == 4], top[kind == 4] = 125, 126
+    n = w * h
+    u = rng.random(n, dtype=np.float32)
+    cls = np.zeros(n, dtype=np.uint8)
+    for k in range(1, 5):
+        at = np.flatnonzero(kind == k)
+        cls[at] = np.minimum(np.searchsorted(np.cumsum(_DEPTH_KINDS[k - 1]).astype(np.float32), u[at], side="right"), 6)
+    r1 = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+    r2 = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+    mant, step = r1 & np.uint32(0x7FFFFF), ((r2 >> np.uint32(16)) % np.uint32(3)).astype(np.int64) - 1
+    span = top + np.uint32(1) - floor
+    exp_n = floor + (r2 & np.uint32(0xFFFF)) % span                          # float exponent field, floor .. top
+    tie_n = (exp_n << np.uint32(23) | (r1 & np.uint32(0x3FF)) << np.uint32(13) | np.uint32(0x1000)).astype(np.int64) + step
+    sub_tie = ((2 * (r1 & np.uint32(0x3FF)).astype(np.float64) + 1) * 2.0 ** -25).astype(np.float32).view(np.uint32).astype(np.int64) + step
+    sub_rnd = (np.uint32(103) + (r2 & np.uint32(0xFFFF)) % np.uint32(10)) << np.uint32(23) | mant
+    bits = np.select(
+        [cls == 0, cls == 1, cls == 2, cls == 3, cls == 4, cls == 5],
+        [0, F32_ONE, ((np.uint32(70) + (r2 & np.uint32(0xFFFF)) % np.uint32(57)) << np.uint32(23) | mant).astype(np.int64),
+         (exp_n << np.uint32(23) | mant).astype(np.int64), tie_n,
+         np.where((r2 >> np.uint32(31)) != 0, sub_tie, sub_rnd.astype(np.int64))],
+        ((np.uint32(40) + (r2 & np.uint32(0xFFFF)) % np.uint32(62)) << np.uint32(23) | mant).astype(np.int64))
+    depth = bits.astype(np.uint32).view(np.float32).reshape(h, w)
+    assert (depth >= 0).all() and (depth <= 1).all()
+    return depth
+
+
+def depth_classes(depth):
+    """How many pixels of a depth image are (exact binary16-normal ties after an even / after an odd binary16, in the binary16
+    subnormal range, below half of the smallest subnormal, 0.0, 1.0): what synthetic_depth promises to contain."""
+    d = np.asarray(depth, dtype=np.float32).ravel()
+    b = d.view(np.uint32)
+    tie = (d >= np.float32(2.0 ** -14)) & (d < 1) & ((b & np.uint32(0x1FFF)) == np.uint32(0x1000))
+    odd = (b & np.uint32(0x2000)) != 0
+    return dict(tie_even=int((tie & ~odd).sum()), tie_odd=int((tie & odd).sum()),
+                subnormal=int(((d >= np.float32(2.0 ** -24)) & (d < np.float32(2.0 ** -14))).sum()),
+                tiny=int(((d > 0) & (d < np.float32(2.0 ** -25))).sum()), zero=int((b == 0).sum()), one=int((b == F32_ONE).sum()))
+
+
+def synthetic_words(depth, low):
+    """Visibility words depth_bits << 32 | low, flattened row-major."""
+    bits = np.ascontiguousarray(depth, dtype=np.float32).ravel().view(np.uint32).astype(np.uint64)
+    return (bits << np.uint64(32)) | (np.asarray(low, dtype=np.uint64).ravel() & np.uint64(0xFFFFFFFF))
+
+
+def valid_range_of(depth):
+    """{min bits, max bits} of hzb_mip0_kernel's valid range, from its definition: the smallest bit pattern among 0 < d < 1, the
+    largest among d > 0; {0xFFFFFFFF, 0} where no pixel qualifies."""
+    d = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+    b = d.view(np.uint32)
+    inner, pos = b[(d > 0) & (d < 1)], b[d > 0]
+    return np.array([inner.min() if len(inner) else 0xFFFFFFFF, pos.max() if len(pos) else 0], dtype=np.uint32)
+
+
+class CallerVisibility:
+    """A visibility image the caller owns: a torch int64 tensor of w * h words on the renderer's device, handed to
+    chordvis_allocate_gbuffer as deviceVisibility.  The context runs on a stream of its own, so every write into the tensor is
+    followed by a device-wide synchronise before the library may be called, and the context is synchronised before the tensor is
+    read.  The renderer keeps the tensor alive (the library holds only its address)."""
+
+    def __init__(self, r, w, h):
+        import torch
+        self.r, self.w, self.h = r, w, h
+        self.tensor = torch.zeros(w * h, dtype=torch.int64, device=torch.device("cuda", r.device))
+        torch.cuda.synchronize()
+        self.attach()
+        r._caller_visibility = self.tensor
+
+    def attach(self):
+        self.r.allocate_gbuffer(self.w, self.h, device_visibility=self.tensor.data_ptr())
+
+    def write(self, words):
+        import torch
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        assert words.size == self.w * self.h
+        self.r.sync()                                      # (nothing of the context's still reads the old image)
+        self.tensor.copy_(torch.from_numpy(words.view(np.int64)))
+        torch.cuda.synchronize()
+
+    def read(self):
+        self.r.sync()
+        return self.tensor.cpu().numpy().view(np.uint64)
+
+
+def marker_from_definition(scene, vis, w, h, cmds):
+    """Per 8 x 8 pixels the set of shading types present, from the definition and for ANY low word: 0 -> type 0; an id field of 0
+    or an id past the command list -> type 0 (no cluster); else the material type of the id's command's object."""
+    low = (np.asarray(vis, dtype=np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32).reshape(h, w)
+    ident = ((low >> 8) & 0xFFFFFF).astype(np.int64)
+    hit = (ident >= 1) & (ident <= len(cmds))
+    typ = np.zeros((h, w), dtype=np.uint32)
+    obj = np.asarray(cmds["objectId"], dtype=np.int64)
+    typ[hit] = scene.materials["materialType"][scene.objects["GLTFMaterialData"][obj[ident[hit] - 1]]]
+    marker = np.zeros(((h + 7) // 8, (w + 7) // 8, 4), dtype=np.uint32)
+    ys, xs = np.nonzero(np.ones((h, w), dtype=bool))
+    np.bitwise_or.at(marker, (ys // 8, xs // 8, (typ.ravel() // 32).astype(np.int64)), np.uint32(1) << (typ.ravel() % 32))
+    return marker
+
+
+# image sizes of the synthetic-image tests, chosen for what they do to the chain's layout (tests/test_synthetic_images_spec.py
+# asserts each property from the descriptor)
+HZB_SIZES = [(64, 64), (65, 64), (64, 127), (129, 67), (257, 64), (66, 2049), (2049, 65), (1237, 701)]
+HZB_FULL_TAIL_SIZE = (4096, 4096)
+DEPTH_VIEW_DIMS = [64, 96, 160]
+
+
+def range_partial_count(w, h):
+    """Blocks of hzb_mip0_kernel (64 x 4 mip-0 texels each) = valid-range partials the tail reduces."""
+    vw, vh = ((w - 1) >> 1) + 1, ((h - 1) >> 1) + 1
+    return ((vw + 63) // 64) * ((vh + 3) // 4)
