@@ -108,6 +108,116 @@ struct TexDecodeJob {
     }
 };
 
+// ---- mip chains made at upload (chordvis_set_texture_mips; kernels_texture.hip) ----
+#define CHORD_TEXMIPS_NAMES "flags: 0, 1 (SRGB), 2 (COVERAGE) or 3; pad: 0; alphaCutoff8 with COVERAGE: 1..255"
+
+// The levels texture `t` ends up with under the context's setting (`ms`: that setting, zero where there is none)
+uint32_t tex_levels(const ChordCtx* c, uint32_t t, const ChordTexture& tx, ChordTextureMips& ms)
+{
+    ms = t < c->texMips.size() ? c->texMips[t] : ChordTextureMips{0u, 0u, 0u, 0u};
+    if (!ms.levels) return tx.mipCount;
+    uint32_t full = 0;
+    for (uint32_t m = std::max(tx.width, tx.height); m; m >>= 1) full++;
+    return std::max(tx.mipCount, std::min(ms.levels, full));
+}
+
+size_t tex_chain_texels(uint32_t width, uint32_t height, uint32_t levels)
+{
+    size_t n = 0;
+    for (uint32_t l = 0; l < levels; l++) n += (size_t)std::max(1u, width >> l) * std::max(1u, height >> l);
+    return n;
+}
+
+// The levels one upload makes: one launch per level step over every texture that has that step, then one launch whose workgroups
+// finish the chains from 64 x 64 down, then the coverage passes; the record tables go to ONE device buffer, freed after the
+// synchronise.  Runs after the copies and the decode, on the same stream: it reads what they wrote.
+struct TexMipJob {
+    std::vector<std::vector<chord::DTexMipRec>> steps;     // [k]: the k-th step of every texture that has one
+    std::vector<uint32_t> stepUnits;
+    std::vector<chord::DTexTailRec> tails;
+    std::vector<chord::DTexCovRec> cov;
+    uint32_t covGroups = 0, covScaleGroups = 0;
+    bool anySrgb = false;
+
+    // base: where level 0 is (a texel index of dMatTexels / a byte index of dTexAlpha); the first `supplied` levels are there
+    // when the job runs, levels supplied .. L-1 are made.  coverage: rescale their alpha (not asked for an alpha of 255 throughout)
+    void add(uint32_t base, uint32_t width, uint32_t height, uint32_t supplied, uint32_t L, const ChordTextureMips& ms, bool coverage)
+    {
+        if (L <= supplied) return;
+        const uint32_t flags = ms.flags & CHORD_TEXMIPS_SRGB;
+        anySrgb = anySrgb || flags;
+        uint32_t l = supplied - 1u, sw = std::max(1u, width >> l), sh = std::max(1u, height >> l);
+        uint32_t src = base + (uint32_t)tex_chain_texels(width, height, l);
+        for (size_t k = 0; l + 1u < L && (sw > CHORD_TEXMIPS_TAIL || sh > CHORD_TEXMIPS_TAIL); k++, l++) {
+            if (steps.size() <= k) { steps.emplace_back(); stepUnits.push_back(0u); }
+            const uint32_t dw = std::max(1u, sw >> 1), dh = std::max(1u, sh >> 1), perRow = (dw + 3u) / 4u;
+            steps[k].push_back(chord::DTexMipRec{stepUnits[k], src, src + sw * sh, sw, sh, perRow, flags, 0u});
+            stepUnits[k] += perRow * dh;
+            src += sw * sh; sw = dw; sh = dh;
+        }
+        if (l + 1u < L) tails.push_back(chord::DTexTailRec{src, sw, sh, L - 1u - l, flags, {0u, 0u, 0u}});
+        if (!coverage) return;
+        const uint32_t level0 = (uint32_t)cov.size();
+        uint32_t off = base;
+        for (uint32_t k = 0; k < L; k++) {
+            const uint32_t n = std::max(1u, width >> k) * std::max(1u, height >> k), groups = (n + CHORD_TEXCOV_GROUP - 1u) / CHORD_TEXCOV_GROUP;
+            if (k == 0u || k >= supplied) {
+                cov.push_back(chord::DTexCovRec{covGroups, covScaleGroups, off, n, level0, ms.alphaCutoff8, {0u, 0u}});
+                covGroups += groups;
+                if (k >= supplied) covScaleGroups += groups;
+            }
+            off += n;
+        }
+    }
+
+    int run(ChordCtx* c, const char* who, uint32_t* texels, uint8_t* alpha, bool alphaOnly)
+    {
+        if (steps.empty() && tails.empty()) return CHORDVIS_OK;
+        // the tables, 32-byte records all: every step's (each closed), the tails, the coverage levels (closed)
+        std::vector<uint32_t> words;
+        auto put = [&words](const void* p, size_t bytes) { const size_t at = words.size(); words.resize(at + bytes / 4u); if (bytes) std::memcpy(words.data() + at, p, bytes); return at * 4u; };
+        std::vector<size_t> stepAt(steps.size());
+        for (size_t k = 0; k < steps.size(); k++) {
+            steps[k].push_back(chord::DTexMipRec{stepUnits[k], 0u, 0u, 1u, 1u, 1u, 0u, 0u});
+            stepAt[k] = put(steps[k].data(), steps[k].size() * sizeof(chord::DTexMipRec));
+        }
+        const size_t tailAt = put(tails.data(), tails.size() * sizeof(chord::DTexTailRec));
+        const uint32_t covCount = (uint32_t)cov.size();
+        cov.push_back(chord::DTexCovRec{covGroups, covScaleGroups, 0u, 0u, 0u, 0u, {0u, 0u}});
+        const size_t covAt = put(cov.data(), cov.size() * sizeof(chord::DTexCovRec));
+        const bool srgb = anySrgb && !alphaOnly;
+        float tables[512];
+        if (srgb) {
+            chordvis_material_constants(tables, nullptr);
+            tables[256] = 0.0f;
+            for (int k = 1; k < 256; k++) tables[256 + k] = (tables[k - 1] + tables[k]) * 0.5f;
+        }
+        uint8_t* dTables = nullptr;
+        float* dSrgb = nullptr;
+        uint32_t* dWork = nullptr;
+        const size_t workWords = (size_t)covCount * 257u;
+        hipError_t e = hipMalloc((void**)&dTables, words.size() * 4u);
+        if (e == hipSuccess) e = hipMemcpy(dTables, words.data(), words.size() * 4u, hipMemcpyHostToDevice);
+        if (e == hipSuccess && srgb) e = hipMalloc((void**)&dSrgb, sizeof(tables));
+        if (e == hipSuccess && srgb) e = hipMemcpy(dSrgb, tables, sizeof(tables), hipMemcpyHostToDevice);
+        if (e == hipSuccess && covCount) e = hipMalloc((void**)&dWork, workWords * 4u);
+        if (e == hipSuccess && covCount) e = hipMemsetAsync(dWork, 0, workWords * 4u, c->stream);
+        if (e == hipSuccess) {
+            for (size_t k = 0; k < steps.size(); k++)
+                chord::launch_texture_mips_step(c, (const chord::DTexMipRec*)(dTables + stepAt[k]), (uint32_t)steps[k].size() - 1u, stepUnits[k], dSrgb, texels, alpha, alphaOnly);
+            chord::launch_texture_mips_tail(c, (const chord::DTexTailRec*)(dTables + tailAt), (uint32_t)tails.size(), dSrgb, texels, alpha, alphaOnly);
+            if (covCount) chord::launch_texture_coverage(c, (const chord::DTexCovRec*)(dTables + covAt), covCount, covGroups, covScaleGroups, dWork, texels, alpha, alphaOnly);
+            e = hipGetLastError();
+            const hipError_t es = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = es;
+        }
+        if (dTables) (void)hipFree(dTables);
+        if (dSrgb) (void)hipFree(dSrgb);
+        if (dWork) (void)hipFree(dWork);
+        return e == hipSuccess ? CHORDVIS_OK : fail(c, CHORDVIS_E_HIP, who, e);
+    }
+};
+
 void record(ChordCtx* c, int tag) { chord::stamp(c, tag); }
 
 void begin_frame_stamps(ChordCtx* c)
@@ -723,12 +833,13 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     // the per-vertex texture coordinates (mesh_raster.hlsl:107-112,198-204)
     std::vector<DMaterial> dmats(s->materialCount);
     // (the alpha of an RGBA8 texture is picked out on the host, per texture; a block-compressed one is expanded on the device)
-    struct AlphaCopy { size_t base; std::vector<uint8_t> bytes; };
+    struct AlphaCopy { size_t base; std::vector<uint8_t> bytes; const uint8_t* rgba8; size_t texels; };
     std::vector<AlphaCopy> alphaCopies;
     std::vector<std::pair<size_t, size_t>> alphaOpaque;                    // (first byte, bytes) of BC1_RGB / BC4 / BC5 chains: 255 throughout
     TexDecodeJob alphaDecode;                                              // BC3 chains: their alpha blocks
+    TexMipJob alphaMips;                                                   // chordvis_set_texture_mips: the levels made here
     size_t alphaTexels = 0;
-    std::vector<uint32_t> texOffset(s->textureCount, 0xFFFFFFFFu);
+    std::vector<uint32_t> texOffset(s->textureCount, 0xFFFFFFFFu), texLevels(s->textureCount, 0u);
     bool anyMasked = false;
     for (uint32_t m = 0; m < s->materialCount; m++) anyMasked = anyMasked || s->materials[m].alphaMode == CHORD_ALPHA_MASK;
     if (anyMasked && s->textures) {
@@ -744,19 +855,21 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
                 return fail(c, CHORDVIS_E_INVALID, "upload_scene: unknown ChordTexture::format on a texture a masked material samples; allowed: " CHORD_TEXFMT_NAMES);
             if (!tx.rgba8 || tx.width == 0 || tx.height == 0 || tx.mipCount == 0 || tx.width > 16384u || tx.height > 16384u || tx.mipCount > 15u)
                 return fail(c, CHORDVIS_E_INVALID, "upload_scene: texture without data, or larger than 16384 / 15 levels");
-            size_t texels = 0;
-            for (uint32_t l = 0; l < tx.mipCount; l++) texels += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
+            ChordTextureMips ms;
+            const uint32_t L = tex_levels(c, t, tx, ms);                   // (>= mipCount; the levels beyond it are made on the device)
+            const size_t texels = tex_chain_texels(tx.width, tx.height, L), supplied = tex_chain_texels(tx.width, tx.height, tx.mipCount);
             if (alphaTexels + texels >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_scene: more than 4 G texels of alpha");
-            texOffset[t] = (uint32_t)alphaTexels;
+            texOffset[t] = (uint32_t)alphaTexels; texLevels[t] = L;
             const size_t base = alphaTexels;
             alphaTexels += texels;
+            if (tx.format != CHORD_TEXFMT_RGBA8 && tx.format != CHORD_TEXFMT_BC3) { alphaOpaque.push_back({base, texels}); continue; }
             if (tx.format == CHORD_TEXFMT_BC3) alphaDecode.add(tx, (uint32_t)base);
-            else if (tx.format != CHORD_TEXFMT_RGBA8) alphaOpaque.push_back({base, texels});
-            else {
-                alphaCopies.push_back(AlphaCopy{base, std::vector<uint8_t>(texels)});
-                uint8_t* a8 = alphaCopies.back().bytes.data();
-                for (size_t i = 0; i < texels; i++) a8[i] = tx.rgba8[i * 4 + 3];
-            }
+            else alphaCopies.push_back(AlphaCopy{base, std::vector<uint8_t>(), tx.rgba8, supplied});
+            alphaMips.add((uint32_t)base, tx.width, tx.height, tx.mipCount, L, ms, (ms.flags & CHORD_TEXMIPS_COVERAGE) != 0u);
+        }
+        for (AlphaCopy& a : alphaCopies) {                                 // (once the whole table is known to fit: no texel is read before)
+            a.bytes.resize(a.texels);
+            for (size_t i = 0; i < a.texels; i++) a.bytes[i] = a.rgba8[i * 4 + 3];
         }
     }
     for (uint32_t m = 0; m < s->materialCount; m++) {
@@ -766,7 +879,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         d.texOffset = 0xFFFFFFFFu;
         if (s->textures && mat.baseColorId < s->textureCount && texOffset[mat.baseColorId] != 0xFFFFFFFFu) {
             const ChordTexture& tx = s->textures[mat.baseColorId];
-            d.texOffset = texOffset[mat.baseColorId]; d.texWidth = tx.width; d.texHeight = tx.height; d.texMips = tx.mipCount;
+            d.texOffset = texOffset[mat.baseColorId]; d.texWidth = tx.width; d.texHeight = tx.height; d.texMips = texLevels[mat.baseColorId];
         }
         if (s->samplers && mat.baseColorSampler < s->samplerCount) {
             const ChordSampler& sm = s->samplers[mat.baseColorSampler];
@@ -847,6 +960,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         for (const AlphaCopy& a : alphaCopies) CHORD_HIP(c, hipMemcpy(c->dTexAlpha + a.base, a.bytes.data(), a.bytes.size(), hipMemcpyHostToDevice));
         for (const auto& o : alphaOpaque) CHORD_HIP(c, hipMemsetAsync(c->dTexAlpha + o.first, 0xFF, o.second, c->stream));
         if ((rc = alphaDecode.run(c, "upload_scene: texture decode", nullptr, c->dTexAlpha, true))) return rc;
+        if ((rc = alphaMips.run(c, "upload_scene: texture mips", nullptr, c->dTexAlpha, true))) return rc;
         if (!alphaOpaque.empty()) CHORD_HIP(c, hipStreamSynchronize(c->stream));
     } else dfree(c->dTexAlpha);
     if (!uvs.empty()) { UP(c->dTexcoords, uvs) } else dfree(c->dTexcoords);
@@ -900,19 +1014,25 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     // block-compressed ones are expanded there by one kernel launch
     size_t texelCount = 0;
     TexDecodeJob decode;
-    std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu);
+    TexMipJob mips;                                                        // chordvis_set_texture_mips: the levels made here
+    std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu), texLevels(nTex, 0u);
     for (uint32_t t = 0; t < nTex; t++) {
+        texLevels[t] = s->textures[t].mipCount;
         if (!named[t]) continue;
         const ChordTexture& tx = s->textures[t];
         if (tx.format != CHORD_TEXFMT_RGBA8 && !tex_block_bytes(tx.format))
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: unknown ChordTexture::format on a texture a material names; allowed: " CHORD_TEXFMT_NAMES);
         if (!tx.rgba8 || tx.width == 0 || tx.height == 0 || tx.mipCount == 0 || tx.width > 16384u || tx.height > 16384u || tx.mipCount > CHORD_MAX_TEX_LEVELS)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
-        size_t count = 0;
-        for (uint32_t l = 0; l < tx.mipCount; l++) count += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
+        ChordTextureMips ms;
+        const uint32_t L = tex_levels(c, t, tx, ms);                       // (>= mipCount; the levels beyond it are made on the device)
+        const size_t count = tex_chain_texels(tx.width, tx.height, L);
         if (texelCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
-        texBase[t] = (uint32_t)texelCount;
+        texBase[t] = (uint32_t)texelCount; texLevels[t] = L;
         if (tx.format != CHORD_TEXFMT_RGBA8) decode.add(tx, (uint32_t)texelCount);
+        // (BC1_RGB, BC4, BC5: alpha 255 at every level, which the rescale would leave as it is)
+        mips.add((uint32_t)texelCount, tx.width, tx.height, tx.mipCount, L, ms,
+                 (ms.flags & CHORD_TEXMIPS_COVERAGE) && (tx.format == CHORD_TEXFMT_RGBA8 || tx.format == CHORD_TEXFMT_BC3));
         texelCount += count;
     }
     auto wrap_consts = [](uint32_t n, uint32_t mode, uint32_t& magic, uint32_t& bias) {   // (DMatLevel; as chordvis_upload_scene's)
@@ -945,9 +1065,9 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
                        ((sm.minFilter == CHORD_FILTER_NEAREST_MIPMAP_LINEAR || sm.minFilter == CHORD_FILTER_LINEAR_MIPMAP_LINEAR) ? CHORD_MATSLOT_MIP_LINEAR : 0u);
             if (tex[k] >= nTex) continue;                                  // mips = 0: the slot's fallback
             const ChordTexture& tx = s->textures[tex[k]];
-            S.mips = tx.mipCount;
+            S.mips = texLevels[tex[k]];
             uint32_t off = texBase[tex[k]];
-            for (uint32_t l = 0; l < tx.mipCount; l++) {
+            for (uint32_t l = 0; l < S.mips; l++) {
                 const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l);
                 chord::DMatLevel& L = S.levels[l];
                 L.base = off; L.dims = (w - 1u) | (h - 1u) << 16;
@@ -966,15 +1086,15 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t t = 0; t < nTex; t++) {
             const ChordTexture& tx = s->textures[t];
             if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8) continue;
-            size_t count = 0;
-            for (uint32_t l = 0; l < tx.mipCount; l++) count += (size_t)std::max(1u, tx.width >> l) * std::max(1u, tx.height >> l);
+            const size_t count = tex_chain_texels(tx.width, tx.height, tx.mipCount);
             hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8, count * 4, hipMemcpyHostToDevice);
             if (e != hipSuccess) { dfree(c->dMatRecords); dfree(c->dMatTexels); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
         }
         if ((rc = decode.run(c, "upload_material_textures: texture decode", c->dMatTexels, nullptr, false))) { dfree(c->dMatRecords); dfree(c->dMatTexels); return rc; }
+        if ((rc = mips.run(c, "upload_material_textures: texture mips", c->dMatTexels, nullptr, false))) { dfree(c->dMatRecords); dfree(c->dMatTexels); return rc; }
     }
     c->matTex.resize(nTex);
-    for (uint32_t t = 0; t < nTex; t++) c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, s->textures[t].mipCount};
+    for (uint32_t t = 0; t < nTex; t++) c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, texLevels[t]};
     c->matTexturesLoaded = true; c->matAnyNormalTexture = anyNormal;
     return CHORDVIS_OK;
 }
@@ -1759,6 +1879,27 @@ int chordvis_set_material_anisotropy(ChordCtx* c, uint32_t maxAnisotropy)
     return CHORDVIS_OK;
 }
 uint32_t chordvis_material_anisotropy(const ChordCtx* c) { return c ? c->matAnisotropy : 0u; }
+
+int chordvis_set_texture_mips(ChordCtx* c, const ChordTextureMips* perTexture, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!perTexture || !count) { c->texMips.clear(); return CHORDVIS_OK; }
+    for (uint32_t t = 0; t < count; t++) {
+        const ChordTextureMips& m = perTexture[t];
+        if ((m.flags & ~(CHORD_TEXMIPS_SRGB | CHORD_TEXMIPS_COVERAGE)) || m.pad ||
+            ((m.flags & CHORD_TEXMIPS_COVERAGE) && (m.alphaCutoff8 < 1u || m.alphaCutoff8 > 255u)))
+            return fail(c, CHORDVIS_E_INVALID, "set_texture_mips: an entry is not allowed; " CHORD_TEXMIPS_NAMES);
+    }
+    c->texMips.assign(perTexture, perTexture + count);
+    return CHORDVIS_OK;
+}
+
+int chordvis_texture_mips(const ChordCtx* c, uint32_t textureId, ChordTextureMips* out)
+{
+    if (!c || !out) return CHORDVIS_E_INVALID;
+    *out = textureId < c->texMips.size() ? c->texMips[textureId] : ChordTextureMips{0u, 0u, 0u, 0u};
+    return CHORDVIS_OK;
+}
 
 int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9])
 {

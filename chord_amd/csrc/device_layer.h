@@ -139,6 +139,40 @@ struct DTexLevelRec {          // 32 B
 };
 static_assert(sizeof(DTexLevelRec) == 32, "DTexLevelRec");
 
+// Mip generation at upload (chordvis_set_texture_mips; kernels_texture.hip).  Offsets count texels of
+// dMatTexels or alpha bytes of dTexAlpha, as DMatLevel::base does.
+// One level step of one texture for texture_mips_step_kernel: a "unit" is four adjacent output texels of one row; the units of all
+// records of a launch form a flat grid, a closing record holds the total in firstUnit.
+struct DTexMipRec {            // 32 B
+    uint32_t firstUnit;        // units of all records before this one
+    uint32_t src, dst;         // first texel of the source level / of the level made from it
+    uint32_t sw, sh;           // of the source level; the made one is max(1, sw >> 1) x max(1, sh >> 1)
+    uint32_t unitsPerRow;      // ceil(max(1, sw >> 1) / 4)
+    uint32_t flags;            // CHORD_TEXMIPS_SRGB
+    uint32_t pad;
+};
+// The rest of one texture's chain for texture_mips_tail_kernel: a workgroup per record, from a source level of at most 64 x 64.
+struct DTexTailRec {           // 32 B
+    uint32_t src;              // first texel of the source level; the made levels follow it back to back
+    uint32_t sw, sh;
+    uint32_t levels;           // how many to make
+    uint32_t flags;            // CHORD_TEXMIPS_SRGB
+    uint32_t pad[3];
+};
+// One level of one CHORD_TEXMIPS_COVERAGE texture: level 0 as supplied (counted only) or a generated level (counted, then
+// rescaled).  Workgroups of 4096 texels; the histogram kernel's grid is flat over firstGroup, the rescale kernel's over
+// firstScaleGroup (level 0 records take none of it); a closing record holds the totals.
+struct DTexCovRec {            // 32 B
+    uint32_t firstGroup, firstScaleGroup;
+    uint32_t base, texels;     // of the level
+    uint32_t level0;           // index of the texture's level-0 record (its own index: this IS that record)
+    uint32_t cutoff;           // alphaCutoff8, 1..255
+    uint32_t pad[2];
+};
+static_assert(sizeof(DTexMipRec) == 32 && sizeof(DTexTailRec) == 32 && sizeof(DTexCovRec) == 32, "texture mip records");
+#define CHORD_TEXMIPS_TAIL 64u          // a source level of at most this size in both directions: the tail kernel takes the rest
+#define CHORD_TEXCOV_GROUP 4096u        // texels per workgroup of the coverage kernels
+
 // extension of a masked triangle's 48-byte record, in the TWO slots behind it.  Everything a row unit of the tile kernel needs to
 // sample the triangle's alpha is in here -- the chosen level's first byte and size, the wraps, the material's factor and cut-off --
 // so a unit's set-up is one round trip (this record), not three dependent ones (extension -> material -> level offsets).
@@ -373,6 +407,7 @@ struct ChordCtx {
     std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
+    std::vector<ChordTextureMips> texMips;    // chordvis_set_texture_mips: per texture id; kept across uploads, read by both
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
     chord::DBVHNode* dBvhNodes = nullptr;   // every primitive's tree (or null: the scene came without)
     bool bvhComplete = false;         // every primitive has a validated tree
@@ -588,6 +623,18 @@ void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const C
 // `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.
 void launch_texture_decode(ChordCtx* c, const DTexLevelRec* recs, uint32_t count, uint32_t totalBlocks, const void* staging,
                            uint32_t* texels, uint8_t* alpha, bool alphaOnly);
+// Mip generation in place in `texels` (RGBA8 words) or -- alphaOnly -- in `alpha` (bytes), on the context's stream.
+// step: one level step of `count` textures (recs[count] closes the table), one launch.  tail: the rest of `count` chains, a
+// workgroup each, one launch.  tables: the sRGB8 -> linear table and its 256 midpoints (512 floats; read where a record has
+// CHORD_TEXMIPS_SRGB; may be null for alphaOnly).
+void launch_texture_mips_step(ChordCtx* c, const DTexMipRec* recs, uint32_t count, uint32_t totalUnits, const float* tables,
+                              uint32_t* texels, uint8_t* alpha, bool alphaOnly);
+void launch_texture_mips_tail(ChordCtx* c, const DTexTailRec* recs, uint32_t count, const float* tables, uint32_t* texels,
+                              uint8_t* alpha, bool alphaOnly);
+// Alpha coverage of the generated levels: histograms of `count` levels (recs[count] closes the table) into work[count][256]
+// (zeroed by the caller), a wave per level picks its threshold into work[count * 256 + level], a pass rescales.  Three launches.
+void launch_texture_coverage(ChordCtx* c, const DTexCovRec* recs, uint32_t count, uint32_t groups, uint32_t scaleGroups,
+                             uint32_t* work, uint32_t* texels, uint8_t* alpha, bool alphaOnly);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -123,6 +123,257 @@ __global__ __launch_bounds__(256) void texture_decode_kernel(const DTexLevelRec*
     }
 }
 
+// ---- mip generation (chordvis_set_texture_mips) ----
+// Level l+1 is a 2 x 2 box of level l, in place in the texel store (RGBA8 words of dMatTexels, or ALPHA: bytes of dTexAlpha).
+// Levels whose source is larger than 64 x 64 take one launch per level step, shared by every texture of the upload
+// (texture_mips_step_kernel); from a source of at most 64 x 64 on, one workgroup finishes a texture's chain through LDS
+// (texture_mips_tail_kernel).  CHORD_TEXMIPS_COVERAGE then rescales the alpha of the made levels (the three coverage kernels).
+
+// (sum of four codes + 2) >> 2 in each byte of the word: two 16-bit fields per half, no carry between them (4 x 255 + 2 < 2^16)
+__device__ __forceinline__ uint32_t box_codes(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
+{
+    const uint32_t M = 0x00FF00FFu, R = 0x00020002u;
+    const uint32_t lo = (((a & M) + (b & M) + (c & M) + (d & M) + R) >> 2) & M;
+    const uint32_t hi = ((((a >> 8) & M) + ((b >> 8) & M) + ((c >> 8) & M) + ((d >> 8) & M) + R) >> 2) & M;
+    return lo | hi << 8;
+}
+
+// tab: the sRGB8 -> linear table T[256], then mid[256] with mid[k] = (T[k-1] + T[k]) * 0.5f.  The number of k in 1..255 with
+// mid[k] <= v (mid is strictly increasing): the nearest code in linear light
+__device__ __forceinline__ uint32_t linear_code(const float* tab, float v)
+{
+    uint32_t lo = 0u, hi = 255u;                            // mid[k] <= v for k in 1..lo, mid[k] > v for k > hi
+    while (lo < hi) {
+        const uint32_t m = (lo + hi + 1u) >> 1;
+        if (tab[256u + m] <= v) lo = m; else hi = m - 1u;
+    }
+    return lo;
+}
+
+// a = (2x, 2y), b = (2x+1, 2y), c = (2x, 2y+1), d = (2x+1, 2y+1)
+__device__ __forceinline__ uint32_t box_texel(bool srgb, const float* tab, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
+{
+    const uint32_t codes = box_codes(a, b, c, d);
+    if (!srgb) return codes;
+    uint32_t out = codes & 0xFF000000u;
+#pragma unroll
+    for (uint32_t s = 0; s < 24u; s += 8u) {
+        const float v = __fmul_rn(__fadd_rn(__fadd_rn(tab[(a >> s) & 0xFFu], tab[(b >> s) & 0xFFu]),
+                                            __fadd_rn(tab[(c >> s) & 0xFFu], tab[(d >> s) & 0xFFu])), 0.25f);
+        out |= linear_code(tab, v) << s;
+    }
+    return out;
+}
+
+// the last record whose first word is not above g (recs[0]'s is 0, the closing record's is above every g); FIELD: word of the record
+template <typename Rec, uint32_t Rec::*FIELD>
+__device__ __forceinline__ uint32_t find_record(const Rec* __restrict__ recs, uint32_t count, uint32_t g)
+{
+    uint32_t lo = 0u, hi = count;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (recs[mid].*FIELD <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// One level step of every texture that has one: the grid is flat over units of four adjacent output texels of a row; a lane
+// reads 2 x 8 source texels (two 16-byte loads per row; ALPHA: one 8-byte load) and writes 16 bytes (ALPHA: 4), where the
+// pieces are whole and aligned -- they are not behind a level of odd size, nor at the end of a row whose width is no multiple of 4.
+template <bool ALPHA>
+__global__ __launch_bounds__(256) void texture_mips_step_kernel(const DTexMipRec* __restrict__ recs, uint32_t count, uint32_t totalUnits,
+                                                                const float* __restrict__ tables, uint32_t* __restrict__ texels,
+                                                                uint8_t* __restrict__ alpha)
+{
+    __shared__ float tab[512];
+    if (!ALPHA && tables) {                                 // (null: no record of the upload has CHORD_TEXMIPS_SRGB)
+        tab[threadIdx.x] = tables[threadIdx.x]; tab[threadIdx.x + 256u] = tables[threadIdx.x + 256u];
+        __syncthreads();
+    }
+    const uint32_t first = blockIdx.x * 256u;
+    uint32_t lo = find_record<DTexMipRec, &DTexMipRec::firstUnit>(recs, count, first);
+    const uint32_t u = first + threadIdx.x;
+    if (u >= totalUnits) return;
+    while (recs[lo + 1u].firstUnit <= u) lo++;
+    const DTexMipRec R = recs[lo];
+
+    const uint32_t lu = u - R.firstUnit, y = lu / R.unitsPerRow, x0 = (lu - y * R.unitsPerRow) * 4u;
+    const uint32_t dw = max(1u, R.sw >> 1), n = min(4u, dw - x0);
+    const size_t s0 = (size_t)R.src + (size_t)min(2u * y, R.sh - 1u) * R.sw, s1 = (size_t)R.src + (size_t)min(2u * y + 1u, R.sh - 1u) * R.sw;
+    uint32_t p0[8], p1[8];
+    // (n == 4 means dw >= x0 + 4, so the eight source columns 2 x0 .. 2 x0 + 7 exist: sw >= 2 dw)
+    const size_t c0 = s0 + 2u * x0, c1 = s1 + 2u * x0;
+    if (ALPHA) {
+        if (n == 4u && ((c0 | c1) & 7u) == 0u) {
+            const uint2 q0 = *reinterpret_cast<const uint2*>(alpha + c0), q1 = *reinterpret_cast<const uint2*>(alpha + c1);
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++) {
+                p0[i] = (q0.x >> (8u * i)) & 0xFFu; p0[4u + i] = (q0.y >> (8u * i)) & 0xFFu;
+                p1[i] = (q1.x >> (8u * i)) & 0xFFu; p1[4u + i] = (q1.y >> (8u * i)) & 0xFFu;
+            }
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++) {
+                const uint32_t col = min(2u * x0 + i, R.sw - 1u);               // (the clamp acts only where sw == 1)
+                p0[i] = alpha[s0 + col]; p1[i] = alpha[s1 + col];
+            }
+        }
+    } else {
+        if (n == 4u && ((c0 | c1) & 3u) == 0u) {
+            const uint4 a0 = *reinterpret_cast<const uint4*>(texels + c0), a1 = *reinterpret_cast<const uint4*>(texels + c0 + 4u);
+            const uint4 b0 = *reinterpret_cast<const uint4*>(texels + c1), b1 = *reinterpret_cast<const uint4*>(texels + c1 + 4u);
+            p0[0] = a0.x; p0[1] = a0.y; p0[2] = a0.z; p0[3] = a0.w; p0[4] = a1.x; p0[5] = a1.y; p0[6] = a1.z; p0[7] = a1.w;
+            p1[0] = b0.x; p1[1] = b0.y; p1[2] = b0.z; p1[3] = b0.w; p1[4] = b1.x; p1[5] = b1.y; p1[6] = b1.z; p1[7] = b1.w;
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++) {
+                const uint32_t col = min(2u * x0 + i, R.sw - 1u);
+                p0[i] = texels[s0 + col]; p1[i] = texels[s1 + col];
+            }
+        }
+    }
+    const bool srgb = !ALPHA && (R.flags & CHORD_TEXMIPS_SRGB);
+    uint32_t out[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) out[j] = box_texel(srgb, tab, p0[2 * j], p0[2 * j + 1], p1[2 * j], p1[2 * j + 1]);
+
+    const size_t t = (size_t)R.dst + (size_t)y * dw + x0;
+    if (ALPHA) {
+        if (n == 4u && (t & 3u) == 0u) *reinterpret_cast<uint32_t*>(alpha + t) = out[0] | out[1] << 8 | out[2] << 16 | out[3] << 24;
+        else {
+#pragma unroll
+            for (uint32_t x = 0; x < 4u; x++) if (x < n) alpha[t + x] = (uint8_t)out[x];
+        }
+    } else {
+        if (n == 4u && (t & 3u) == 0u) *reinterpret_cast<uint4*>(texels + t) = make_uint4(out[0], out[1], out[2], out[3]);
+        else {
+#pragma unroll
+            for (uint32_t x = 0; x < 4u; x++) if (x < n) texels[t + x] = out[x];
+        }
+    }
+}
+
+// The rest of a chain from a source level of at most 64 x 64: the workgroup holds the source in LDS, makes a level into a second
+// LDS buffer and the store, and goes on from there; the two buffers change roles (a made level has at most 32 x 32 texels).
+template <bool ALPHA>
+__global__ __launch_bounds__(256) void texture_mips_tail_kernel(const DTexTailRec* __restrict__ recs, const float* __restrict__ tables,
+                                                                uint32_t* __restrict__ texels, uint8_t* __restrict__ alpha)
+{
+    __shared__ uint32_t buf[CHORD_TEXMIPS_TAIL * CHORD_TEXMIPS_TAIL + CHORD_TEXMIPS_TAIL * CHORD_TEXMIPS_TAIL / 4u];
+    __shared__ float tab[512];
+    const DTexTailRec R = recs[blockIdx.x];
+    const bool srgb = !ALPHA && (R.flags & CHORD_TEXMIPS_SRGB);                      // (uniform)
+    if (srgb) { tab[threadIdx.x] = tables[threadIdx.x]; tab[threadIdx.x + 256u] = tables[threadIdx.x + 256u]; }
+    uint32_t sw = R.sw, sh = R.sh;
+    size_t off = R.src;
+    for (uint32_t i = threadIdx.x; i < sw * sh; i += 256u) buf[i] = ALPHA ? (uint32_t)alpha[off + i] : texels[off + i];
+    __syncthreads();
+    uint32_t* s = buf;
+    uint32_t* d = buf + CHORD_TEXMIPS_TAIL * CHORD_TEXMIPS_TAIL;
+    off += sw * sh;
+    for (uint32_t l = 0; l < R.levels; l++) {
+        const uint32_t dw = max(1u, sw >> 1), dh = max(1u, sh >> 1);
+        for (uint32_t i = threadIdx.x; i < dw * dh; i += 256u) {
+            const uint32_t y = i / dw, x = i - y * dw;
+            const uint32_t x0 = min(2u * x, sw - 1u), x1 = min(2u * x + 1u, sw - 1u), r0 = min(2u * y, sh - 1u) * sw, r1 = min(2u * y + 1u, sh - 1u) * sw;
+            const uint32_t v = box_texel(srgb, tab, s[r0 + x0], s[r0 + x1], s[r1 + x0], s[r1 + x1]);
+            d[i] = v;
+            if (ALPHA) alpha[off + i] = (uint8_t)v; else texels[off + i] = v;
+        }
+        __syncthreads();
+        uint32_t* const k = s; s = d; d = k;
+        off += dw * dh; sw = dw; sh = dh;
+    }
+}
+
+// Coverage, step 1 and 2: the 256-bin histogram of the alpha of a workgroup's 4096 texels in LDS (a lane adds a run of equal
+// values at once: masks are mostly 0 and 255), then one global add per non-empty bin into the level's row of `work`.
+template <bool ALPHA>
+__global__ __launch_bounds__(256) void texture_coverage_hist_kernel(const DTexCovRec* __restrict__ recs, uint32_t count, uint32_t* __restrict__ work,
+                                                                    const uint32_t* __restrict__ texels, const uint8_t* __restrict__ alpha)
+{
+    __shared__ uint32_t hist[256];
+    const uint32_t r = find_record<DTexCovRec, &DTexCovRec::firstGroup>(recs, count, blockIdx.x);      // (uniform)
+    const DTexCovRec R = recs[r];
+    hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t begin = (blockIdx.x - R.firstGroup) * CHORD_TEXCOV_GROUP, end = min(begin + CHORD_TEXCOV_GROUP, R.texels);
+    uint32_t prev = 0u, run = 0u;
+    for (uint32_t i = begin + threadIdx.x; i < end; i += 256u) {
+        const uint32_t a = ALPHA ? (uint32_t)alpha[(size_t)R.base + i] : texels[(size_t)R.base + i] >> 24;
+        if (a == prev) run++;
+        else { if (run) atomicAdd(&hist[prev], run); prev = a; run = 1u; }
+    }
+    if (run) atomicAdd(&hist[prev], run);
+    __syncthreads();
+    const uint32_t h = hist[threadIdx.x];
+    if (h) atomicAdd(&work[(size_t)r * 256u + threadIdx.x], h);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// Coverage, step 3: one wave per generated level.  cnt(t) = texels with a >= t by a suffix scan of the histogram (a lane holds
+// four bins); t* = the largest t in 1..255 with cnt(t) N0 >= P0 N, or 1 (cnt does not grow with t, so the t that satisfy it are
+// 1 .. t*: t* is how many there are); tlo = the smallest t with cnt(t) = cnt(t*); t' = clamp(cutoff, tlo, t*) goes to
+// work[count * 256 + level].
+__global__ __launch_bounds__(64) void texture_coverage_pick_kernel(const DTexCovRec* __restrict__ recs, uint32_t count, uint32_t* __restrict__ work)
+{
+    __shared__ uint32_t cnt[256];
+    const uint32_t r = blockIdx.x, lane = threadIdx.x;
+    const DTexCovRec R = recs[r];
+    if (R.level0 == r) return;                              // (level 0 as supplied: counted, never rescaled)
+    const uint4 b = *reinterpret_cast<const uint4*>(work + (size_t)r * 256u + 4u * lane);
+    const uint4 z = *reinterpret_cast<const uint4*>(work + (size_t)R.level0 * 256u + 4u * lane);
+    const uint32_t sum = b.x + b.y + b.z + b.w;
+    uint32_t incl = sum;                                    // bins of this lane and of the lanes above
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t v = __shfl_down(incl, d);
+        if (lane + d < 64u) incl += v;
+    }
+    const uint32_t c3 = incl - sum + b.w, c2 = c3 + b.z, c1 = c2 + b.y, c0 = c1 + b.x;
+    cnt[4u * lane] = c0; cnt[4u * lane + 1u] = c1; cnt[4u * lane + 2u] = c2; cnt[4u * lane + 3u] = c3;
+    const uint32_t t0 = 4u * lane;
+    const unsigned long long P0 = wave_sum((t0 >= R.cutoff ? z.x : 0u) + (t0 + 1u >= R.cutoff ? z.y : 0u) + (t0 + 2u >= R.cutoff ? z.z : 0u) + (t0 + 3u >= R.cutoff ? z.w : 0u));
+    const unsigned long long N0 = recs[R.level0].texels, N = R.texels;
+    __syncthreads();
+    uint32_t k = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) k += (t0 + j >= 1u && (unsigned long long)cnt[t0 + j] * N0 >= P0 * N) ? 1u : 0u;
+    const uint32_t tStar = max(1u, wave_sum(k));
+    const uint32_t cStar = cnt[tStar];
+    uint32_t m = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) m += (t0 + j >= 1u && cnt[t0 + j] > cStar) ? 1u : 0u;
+    const uint32_t tLo = 1u + wave_sum(m);
+    if (lane == 0u) work[(size_t)count * 256u + r] = min(max(R.cutoff, tLo), tStar);
+}
+
+// Coverage, step 4: a' = min(255, a * cutoff / t') over the generated levels, through a 256-entry table in LDS.
+template <bool ALPHA>
+__global__ __launch_bounds__(256) void texture_coverage_rescale_kernel(const DTexCovRec* __restrict__ recs, uint32_t count, const uint32_t* __restrict__ work,
+                                                                       uint32_t* __restrict__ texels, uint8_t* __restrict__ alpha)
+{
+    __shared__ uint32_t lut[256];
+    const uint32_t r = find_record<DTexCovRec, &DTexCovRec::firstScaleGroup>(recs, count, blockIdx.x);  // (uniform)
+    const DTexCovRec R = recs[r];
+    const uint32_t tp = work[(size_t)count * 256u + r];
+    if (tp == R.cutoff) return;                             // a' = a
+    lut[threadIdx.x] = min(255u, threadIdx.x * R.cutoff / tp);
+    __syncthreads();
+    const uint32_t begin = (blockIdx.x - R.firstScaleGroup) * CHORD_TEXCOV_GROUP, end = min(begin + CHORD_TEXCOV_GROUP, R.texels);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += 256u) {
+        const size_t t = (size_t)R.base + i;
+        if (ALPHA) alpha[t] = (uint8_t)lut[alpha[t]];
+        else { const uint32_t w = texels[t]; texels[t] = (w & 0x00FFFFFFu) | lut[w >> 24] << 24; }
+    }
+}
+
 } // namespace
 
 void launch_texture_decode(ChordCtx* c, const DTexLevelRec* recs, uint32_t count, uint32_t totalBlocks, const void* staging,
@@ -132,6 +383,35 @@ void launch_texture_decode(ChordCtx* c, const DTexLevelRec* recs, uint32_t count
     const dim3 grid((totalBlocks + 255u) / 256u), block(256);
     if (alphaOnly) CHORD_LAUNCH(c, texture_decode_kernel<true>, grid, block, 0, c->stream, recs, count, totalBlocks, (const uint2*)staging, texels, alpha);
     else CHORD_LAUNCH(c, texture_decode_kernel<false>, grid, block, 0, c->stream, recs, count, totalBlocks, (const uint2*)staging, texels, alpha);
+}
+
+void launch_texture_mips_step(ChordCtx* c, const DTexMipRec* recs, uint32_t count, uint32_t totalUnits, const float* tables,
+                              uint32_t* texels, uint8_t* alpha, bool alphaOnly)
+{
+    if (!count || !totalUnits) return;
+    const dim3 grid((totalUnits + 255u) / 256u), block(256);
+    if (alphaOnly) CHORD_LAUNCH(c, texture_mips_step_kernel<true>, grid, block, 0, c->stream, recs, count, totalUnits, tables, texels, alpha);
+    else CHORD_LAUNCH(c, texture_mips_step_kernel<false>, grid, block, 0, c->stream, recs, count, totalUnits, tables, texels, alpha);
+}
+
+void launch_texture_mips_tail(ChordCtx* c, const DTexTailRec* recs, uint32_t count, const float* tables, uint32_t* texels,
+                              uint8_t* alpha, bool alphaOnly)
+{
+    if (!count) return;
+    const dim3 grid(count), block(256);
+    if (alphaOnly) CHORD_LAUNCH(c, texture_mips_tail_kernel<true>, grid, block, 0, c->stream, recs, tables, texels, alpha);
+    else CHORD_LAUNCH(c, texture_mips_tail_kernel<false>, grid, block, 0, c->stream, recs, tables, texels, alpha);
+}
+
+void launch_texture_coverage(ChordCtx* c, const DTexCovRec* recs, uint32_t count, uint32_t groups, uint32_t scaleGroups,
+                             uint32_t* work, uint32_t* texels, uint8_t* alpha, bool alphaOnly)
+{
+    if (!count || !groups || !scaleGroups) return;
+    if (alphaOnly) CHORD_LAUNCH(c, texture_coverage_hist_kernel<true>, dim3(groups), dim3(256), 0, c->stream, recs, count, work, texels, alpha);
+    else CHORD_LAUNCH(c, texture_coverage_hist_kernel<false>, dim3(groups), dim3(256), 0, c->stream, recs, count, work, texels, alpha);
+    CHORD_LAUNCH(c, texture_coverage_pick_kernel, dim3(count), dim3(64), 0, c->stream, recs, count, work);
+    if (alphaOnly) CHORD_LAUNCH(c, texture_coverage_rescale_kernel<true>, dim3(scaleGroups), dim3(256), 0, c->stream, recs, count, work, texels, alpha);
+    else CHORD_LAUNCH(c, texture_coverage_rescale_kernel<false>, dim3(scaleGroups), dim3(256), 0, c->stream, recs, count, work, texels, alpha);
 }
 
 } // namespace chord

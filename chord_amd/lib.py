@@ -71,6 +71,14 @@ class DepthTarget(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class TextureMips(C.Structure):
+    """ChordTextureMips: mip generation at upload, per texture id (chordvis_set_texture_mips)."""
+    _fields_ = [("levels", C.c_uint32), ("flags", C.c_uint32), ("alphaCutoff8", C.c_uint32), ("pad", C.c_uint32)]
+
+
+TEXMIPS_SRGB, TEXMIPS_COVERAGE, TEXMIPS_FULL = 1, 2, 0xFFFFFFFF
+
+
 class HZB(C.Structure):
     _fields_ = [("desc", R.HZBDesc), ("minTexels", C.c_void_p), ("maxTexels", C.c_void_p), ("validRange", C.c_void_p)]
 
@@ -216,6 +224,8 @@ def _load():
         "chordvis_upload_material_textures": (i32, [vp, P(R.SceneDesc)]),
         "chordvis_texture_chain_bytes": (i32, [u32, u32, u32, u32, P(u64)]),
         "chordvis_readback_material_texture": (i32, [vp, u32, u32, vp]),
+        "chordvis_set_texture_mips": (i32, [vp, P(TextureMips), u32]),
+        "chordvis_texture_mips": (i32, [vp, u32, P(TextureMips)]),
         "chordvis_resolve_material": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets), P(MaterialTargets)]),
         "chordvis_set_material_anisotropy": (i32, [vp, u32]),
         "chordvis_material_anisotropy": (u32, [vp]),

@@ -84,6 +84,23 @@ class VisibilityRenderer:
     def material_anisotropy(self):
         return int(L.lib.chordvis_material_anisotropy(self._ctx))
 
+    def set_texture_mips(self, settings):
+        """Mip chains made on the GPU by LATER upload_scene / upload_material_textures calls: entry i, a
+        lib.TextureMips or a (levels, flags, alphaCutoff8) tuple, belongs to texture id i; None or an empty list: none (the default).
+        levels: lib.TEXMIPS_FULL or a count, 0 = as supplied; flags: lib.TEXMIPS_SRGB | lib.TEXMIPS_COVERAGE.  Per context; kept
+        across uploads."""
+        settings = list(settings or ())
+        arr = (L.TextureMips * max(1, len(settings)))()
+        for i, m in enumerate(settings):
+            arr[i] = m if isinstance(m, L.TextureMips) else L.TextureMips(*m)
+        self._check(L.lib.chordvis_set_texture_mips(self._ctx, arr if settings else None, len(settings)), "set_texture_mips")
+
+    def texture_mips(self, texture):
+        """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""
+        m = L.TextureMips()
+        self._check(L.lib.chordvis_texture_mips(self._ctx, int(texture), C.byref(m)), "texture_mips")
+        return (m.levels, m.flags, m.alphaCutoff8, m.pad)
+
     def update_objects(self, objects):
         objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
         self._check(L.lib.chordvis_update_objects(self._ctx, objects.ctypes.data, len(objects)), "update_objects")

@@ -582,6 +582,35 @@ int chordvis_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t heigh
  * row-major; RGBA8 textures too); synchronises.  CHORDVIS_E_INVALID when no material textures are uploaded, when no material of the
  * scene names the texture, or when the level is not below its mipCount. */
 int chordvis_readback_material_texture(ChordCtx* ctx, uint32_t textureId, uint32_t level, uint8_t* hostRgba8);
+/* Mip chains built on the GPU at upload (opt-in per texture).  Entry i belongs to texture id i of the
+ * descriptors given to LATER chordvis_upload_scene / chordvis_upload_material_textures calls; textures at or beyond `count` have
+ * none.  The entries are copied and held per context, across both uploads (as the anisotropy setting is); both uploads read them.
+ *   levels        0: the texture stays as supplied.  Otherwise it ends up with L = min(levels, full) levels, full =
+ *                 bit_length(max(width, height)) (down to 1 x 1; at most 15).  The host supplies the first mipCount levels in the
+ *                 layout of ChordTexture; where L > mipCount, levels mipCount .. L-1 are made on the device from the last supplied
+ *                 one (a block-compressed one is decoded first; made levels live in the RGBA8 / alpha stores only), and every
+ *                 level count downstream is L: the samplers see a longer chain, chordvis_readback_material_texture reaches the
+ *                 made levels, the 4 G texel caps of the uploads count them (CHORDVIS_E_CAPACITY, nothing kept).  Where
+ *                 L <= mipCount nothing changes for the texture.
+ *   flags         level l+1 is a 2 x 2 box of level l (texel (x, y) from columns min(2x, w-1), min(2x+1, w-1), rows likewise: an
+ *                 odd size drops its last column / row), (sum of four codes + 2) >> 2 per channel.  CHORD_TEXMIPS_SRGB: r, g, b
+ *                 are averaged in linear light instead (decoded through the table of chordvis_material_constants, the nearest
+ *                 code of the float32 mean); chordvis_upload_scene stores alpha only and ignores it.  CHORD_TEXMIPS_COVERAGE: the
+ *                 alpha of every MADE level is rescaled, a' = min(255, a * alphaCutoff8 / t'), with t' chosen per level so that
+ *                 the share of texels with a' >= alphaCutoff8 is, as nearly as the level's alpha values allow and not below, the
+ *                 share of level 0's texels with a >= alphaCutoff8.  Supplied levels are never changed.
+ *   alphaCutoff8  the cutoff as an 8-bit code, 1..255; read only with CHORD_TEXMIPS_COVERAGE.
+ * CHORDVIS_E_INVALID, the setting unchanged, chordvis_last_error naming the allowed values: a flag bit other than the two, a
+ * non-zero pad, or CHORD_TEXMIPS_COVERAGE with alphaCutoff8 outside 1..255.  NULL or count 0: no texture has a setting (the
+ * default: both uploads launch and store exactly what they do without this call).  On a ChordGroup, set the ranks' contexts
+ * before the group's scene upload. */
+#define CHORD_TEXMIPS_SRGB      1u          /* r, g, b averaged in linear light; alpha is always averaged as a code */
+#define CHORD_TEXMIPS_COVERAGE  2u          /* rescale the alpha of generated levels to keep level 0's coverage at alphaCutoff8 */
+#define CHORD_TEXMIPS_FULL      0xFFFFFFFFu /* levels: down to 1 x 1 */
+typedef struct ChordTextureMips { uint32_t levels, flags, alphaCutoff8, pad; } ChordTextureMips;
+int chordvis_set_texture_mips(ChordCtx* ctx, const ChordTextureMips* perTexture, uint32_t count);
+/* What is set for one texture id; all zero at or beyond the count of the last accepted call. */
+int chordvis_texture_mips(const ChordCtx* ctx, uint32_t textureId, ChordTextureMips* out);
 /* Caller-owned device images as in ChordResolveTargets.  Empty pixels, pixels whose id is not below the list's count and pixels
  * whose material's materialType is not kLightingType_GLTF_MetallicRoughnessPBR (1; base.h:423, lighting.hlsl:369) hold 0.
  * Float32, source order, one rounding per operation; the texture sampler is the pinned one of DESIGN.md 2 item 9 (isotropic level
