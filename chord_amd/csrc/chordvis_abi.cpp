@@ -218,6 +218,14 @@ struct TexMipJob {
     }
 };
 
+// what chordvis_upload_material_textures keeps
+void drop_material_textures(ChordCtx* c)
+{
+    dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks);
+    c->matTexelCount = 0; c->matBlockUnits = 0;
+    c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
+}
+
 void record(ChordCtx* c, int tag) { chord::stamp(c, tag); }
 
 void begin_frame_stamps(ChordCtx* c)
@@ -578,11 +586,11 @@ int chordvis_destroy(ChordCtx* c)
         c->dPrims = nullptr; c->dGroups = nullptr; c->dMeshlets = nullptr; c->dGroupIndices = nullptr; c->dMeshletData = nullptr;
         c->dPositions = nullptr; c->dObjStatic = nullptr; c->dGroupRefs = nullptr; c->dMaterials = nullptr; c->dTexAlpha = nullptr;
         c->dTexcoords = nullptr; c->dBvhNodes = nullptr; c->dMeshletLod = nullptr; c->dNormals = nullptr; c->dTangents = nullptr;
-        c->dMatRecords = nullptr; c->dMatTexels = nullptr;
+        c->dMatRecords = nullptr; c->dMatTexels = nullptr; c->dMatBlocks = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -968,8 +976,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
     if (!tng.empty()) { UP(c->dTangents, tng) } else dfree(c->dTangents);
 #undef UP
     c->instTriangles = instTriangles;
-    dfree(c->dMatRecords); dfree(c->dMatTexels);                           // (chordvis_upload_material_textures is per scene upload)
-    c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
+    drop_material_textures(c);                                             // (chordvis_upload_material_textures is per scene upload)
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }       // (it aliased the old scene buffers)
     if ((rc = chord::alloc_scene_work_buffers(c))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dObjectsOwned, s->objects, sizeof(ChordObject) * s->objectCount, hipMemcpyHostToDevice));
@@ -994,8 +1001,7 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: the descriptor's materialCount differs from the uploaded scene's");
     (void)hipSetDevice(c->device);
     CHORD_HIP(c, hipStreamSynchronize(c->stream));                         // (a resolve in flight may read the records being replaced)
-    dfree(c->dMatRecords); dfree(c->dMatTexels);
-    c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
+    drop_material_textures(c);
 
     const uint32_t nTex = s->textures ? s->textureCount : 0u;
     std::vector<uint8_t> named(nTex, 0);
@@ -1012,10 +1018,13 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     }
     // RGBA8 chains are copied to their place in dMatTexels as they are (little-endian: R is the low byte of the word);
     // block-compressed ones are expanded there by one kernel launch
+    // ... unless the context's store is CHORD_TEXSTORE_BLOCKS and every level is supplied: such a chain is copied as it is into
+    // dMatBlocks (8-byte units, 16-byte aligned), and the sampler decodes what it taps
     size_t texelCount = 0;
+    uint64_t blockUnits = 0;
     TexDecodeJob decode;
     TexMipJob mips;                                                        // chordvis_set_texture_mips: the levels made here
-    std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu), texLevels(nTex, 0u);
+    std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu), texLevels(nTex, 0u), texKept(nTex, 0u);   // texKept: the format of a chain kept as blocks
     for (uint32_t t = 0; t < nTex; t++) {
         texLevels[t] = s->textures[t].mipCount;
         if (!named[t]) continue;
@@ -1026,6 +1035,15 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
         ChordTextureMips ms;
         const uint32_t L = tex_levels(c, t, tx, ms);                       // (>= mipCount; the levels beyond it are made on the device)
+        if (c->matTextureStore == CHORD_TEXSTORE_BLOCKS && tex_block_bytes(tx.format) && L == tx.mipCount) {
+            uint64_t bytes = 0;
+            (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &bytes);
+            const uint64_t units = ((bytes + 15ull) & ~15ull) / 8u;
+            if (blockUnits + units >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 2^32 8-byte units of textures kept as blocks");
+            texBase[t] = (uint32_t)blockUnits; texKept[t] = tx.format;
+            blockUnits += units;
+            continue;
+        }
         const size_t count = tex_chain_texels(tx.width, tx.height, L);
         if (texelCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
         texBase[t] = (uint32_t)texelCount; texLevels[t] = L;
@@ -1066,6 +1084,8 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             if (tex[k] >= nTex) continue;                                  // mips = 0: the slot's fallback
             const ChordTexture& tx = s->textures[tex[k]];
             S.mips = texLevels[tex[k]];
+            S.format = texKept[tex[k]];
+            const uint32_t unitsPerBlock = tex_block_bytes(S.format) / 8u;  // (0: a level is w * h texels)
             uint32_t off = texBase[tex[k]];
             for (uint32_t l = 0; l < S.mips; l++) {
                 const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l);
@@ -1073,7 +1093,7 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
                 L.base = off; L.dims = (w - 1u) | (h - 1u) << 16;
                 wrap_consts(w, S.wrapS, L.magicS, L.biasS);
                 wrap_consts(h, S.wrapT, L.magicT, L.biasT);
-                off += w * h;
+                off += unitsPerBlock ? ((w + 3u) / 4u) * ((h + 3u) / 4u) * unitsPerBlock : w * h;
             }
             if (k == (int)CHORD_MATSLOT_NORMAL) anyNormal = true;
         }
@@ -1082,20 +1102,53 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     if ((rc = dalloc(c, &c->dMatRecords, recs.size()))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dMatRecords, recs.data(), recs.size() * sizeof(recs[0]), hipMemcpyHostToDevice));
     if (texelCount) {
-        if ((rc = dalloc(c, &c->dMatTexels, texelCount))) { dfree(c->dMatRecords); return rc; }
+        if ((rc = dalloc(c, &c->dMatTexels, texelCount))) { drop_material_textures(c); return rc; }
         for (uint32_t t = 0; t < nTex; t++) {
             const ChordTexture& tx = s->textures[t];
             if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8) continue;
             const size_t count = tex_chain_texels(tx.width, tx.height, tx.mipCount);
             hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8, count * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dfree(c->dMatRecords); dfree(c->dMatTexels); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
+            if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
         }
-        if ((rc = decode.run(c, "upload_material_textures: texture decode", c->dMatTexels, nullptr, false))) { dfree(c->dMatRecords); dfree(c->dMatTexels); return rc; }
-        if ((rc = mips.run(c, "upload_material_textures: texture mips", c->dMatTexels, nullptr, false))) { dfree(c->dMatRecords); dfree(c->dMatTexels); return rc; }
+        if ((rc = decode.run(c, "upload_material_textures: texture decode", c->dMatTexels, nullptr, false))) { drop_material_textures(c); return rc; }
+        if ((rc = mips.run(c, "upload_material_textures: texture mips", c->dMatTexels, nullptr, false))) { drop_material_textures(c); return rc; }
+    }
+    if (blockUnits) {
+        if ((rc = dalloc(c, &c->dMatBlocks, blockUnits))) { drop_material_textures(c); return rc; }
+        for (uint32_t t = 0; t < nTex; t++) {
+            if (!texKept[t]) continue;
+            const ChordTexture& tx = s->textures[t];
+            uint64_t bytes = 0;
+            (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &bytes);
+            hipError_t e = hipMemcpy(c->dMatBlocks + texBase[t], tx.rgba8, bytes, hipMemcpyHostToDevice);
+            if (e == hipSuccess && (bytes & 15ull)) e = hipMemset((uint8_t*)(c->dMatBlocks + texBase[t]) + bytes, 0, 16u - (bytes & 15ull));   // (the chain's padding)
+            if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
+        }
     }
     c->matTex.resize(nTex);
-    for (uint32_t t = 0; t < nTex; t++) c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, texLevels[t]};
+    for (uint32_t t = 0; t < nTex; t++)
+        c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, texLevels[t], texKept[t]};
+    c->matTexelCount = texelCount; c->matBlockUnits = blockUnits;
     c->matTexturesLoaded = true; c->matAnyNormalTexture = anyNormal;
+    return CHORDVIS_OK;
+}
+
+int chordvis_set_material_texture_store(ChordCtx* c, uint32_t mode)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (mode != CHORD_TEXSTORE_EXPANDED && mode != CHORD_TEXSTORE_BLOCKS)
+        return fail(c, CHORDVIS_E_INVALID, "set_material_texture_store: the store is 0 (CHORD_TEXSTORE_EXPANDED) or 1 (CHORD_TEXSTORE_BLOCKS)");
+    c->matTextureStore = mode;
+    return CHORDVIS_OK;
+}
+uint32_t chordvis_material_texture_store(const ChordCtx* c) { return c ? c->matTextureStore : 0u; }
+
+int chordvis_material_texture_memory(ChordCtx* c, uint64_t* texelBytes, uint64_t* blockBytes)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "material_texture_memory: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (texelBytes) *texelBytes = c->matTexelCount * 4u;
+    if (blockBytes) *blockBytes = c->matBlockUnits * 8u;
     return CHORDVIS_OK;
 }
 
@@ -1122,11 +1175,34 @@ int chordvis_readback_material_texture(ChordCtx* c, uint32_t textureId, uint32_t
         return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: no material of the scene names this texture");
     const ChordCtx::MatTexInfo& t = c->matTex[textureId];
     if (level >= t.mipCount) return fail(c, CHORDVIS_E_INVALID, "readback_material_texture: the level is not below the texture's mipCount");
-    size_t off = t.base;
-    for (uint32_t l = 0; l < level; l++) off += (size_t)std::max(1u, t.width >> l) * std::max(1u, t.height >> l);
-    const size_t count = (size_t)std::max(1u, t.width >> level) * std::max(1u, t.height >> level);
+    const uint32_t w = std::max(1u, t.width >> level), h = std::max(1u, t.height >> level);
+    const size_t count = (size_t)w * h;
     (void)hipSetDevice(c->device);
     CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    if (t.format) {
+        // kept as blocks: the upload decoder expands the one level into a temporary buffer (one record, one launch)
+        const uint32_t unitsPerBlock = tex_block_bytes(t.format) / 8u, bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
+        uint32_t src = t.base;
+        for (uint32_t l = 0; l < level; l++) src += ((std::max(1u, t.width >> l) + 3u) / 4u) * ((std::max(1u, t.height >> l) + 3u) / 4u) * unitsPerBlock;
+        const chord::DTexLevelRec recs[2] = {{0u, src, 0u, w, h, bw, t.format, 0u}, {bw * bh, 0u, 0u, 0u, 0u, 1u, 0u, 0u}};
+        uint32_t* dOut = nullptr;
+        chord::DTexLevelRec* dRecs = nullptr;
+        hipError_t e = hipMalloc((void**)&dOut, count * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&dRecs, sizeof(recs));
+        if (e == hipSuccess) e = hipMemcpy(dRecs, recs, sizeof(recs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            chord::launch_texture_decode(c, dRecs, 1u, bw * bh, c->dMatBlocks, dOut, nullptr, false);
+            e = hipGetLastError();
+            const hipError_t es = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = es;
+        }
+        if (e == hipSuccess) e = hipMemcpy(hostRgba8, dOut, count * 4, hipMemcpyDeviceToHost);
+        if (dOut) (void)hipFree(dOut);
+        if (dRecs) (void)hipFree(dRecs);
+        return e == hipSuccess ? CHORDVIS_OK : fail(c, CHORDVIS_E_HIP, "readback_material_texture: texture decode", e);
+    }
+    size_t off = t.base;
+    for (uint32_t l = 0; l < level; l++) off += (size_t)std::max(1u, t.width >> l) * std::max(1u, t.height >> l);
     CHORD_HIP(c, hipMemcpy(hostRgba8, c->dMatTexels + off, count * 4, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }

@@ -95,7 +95,10 @@ struct DMaterial {             // 48 + 15 x 24 B
 };
 // What chordvis_resolve_material samples (kept by chordvis_upload_material_textures; the raster never sees it): per material the four
 // texture slots of loadGLTFMetallicRoughnessPBRMaterial (material.hlsli:66-153) with texture and sampler resolved, and the factors.
-// A level is a DMatLevel whose `base` counts TEXELS (one uint32 RGBA8 each, R in the low byte) of dMatTexels.
+// A level is a DMatLevel whose `base` counts TEXELS (one uint32 RGBA8 each, R in the low byte) of dMatTexels -- or, in a slot whose
+// `format` is a CHORD_TEXFMT_BC* value (a chain kept as blocks under CHORD_TEXSTORE_BLOCKS), 8-BYTE UNITS of dMatBlocks: the level's
+// blocks row-major, ((dims & 0xFFFF) + 4) >> 2 of them per row, one unit each (BC1_RGB, BC4) or two (BC3, BC5: a 16-byte-aligned
+// pair).  dims and the wrap constants count texels in both kinds.
 #define CHORD_MATSLOT_BASECOLOR 0u
 #define CHORD_MATSLOT_EMISSIVE 1u
 #define CHORD_MATSLOT_NORMAL 2u
@@ -108,7 +111,8 @@ struct DMatSlot {              // 32 + 15 x 24 B
     uint32_t mips;             // 0: the material names no texture here (id >= textureCount)
     uint32_t filter;           // CHORD_MATSLOT_* bits of the sampler's magFilter / minFilter
     uint32_t wrapS, wrapT;
-    uint32_t pad[4];
+    uint32_t format;           // 0: the levels are texels of dMatTexels; CHORD_TEXFMT_BC1_RGB .. BC5: blocks of dMatBlocks
+    uint32_t pad[3];
     DMatLevel levels[CHORD_MAX_TEX_LEVELS];
 };
 struct DMatRecord {            // 64 + 4 x 392 B
@@ -402,8 +406,12 @@ struct ChordCtx {
     // chordvis_upload_material_textures (read by chordvis_resolve_material alone; dropped by the next chordvis_upload_scene)
     chord::DMatRecord* dMatRecords = nullptr; // per material
     uint32_t* dMatTexels = nullptr;           // RGBA8 texels of every level of every texture a material slot names, back to back
+    unsigned long long* dMatBlocks = nullptr; // the chains kept as blocks (CHORD_TEXSTORE_BLOCKS), 8-byte units, each chain 16-byte aligned; null: none
+    uint64_t matTexelCount = 0, matBlockUnits = 0;   // texels of dMatTexels / units of dMatBlocks of the current upload
+    uint32_t matTextureStore = CHORD_TEXSTORE_EXPANDED;   // chordvis_set_material_texture_store; kept across uploads, read by chordvis_upload_material_textures
     bool matTexturesLoaded = false;
-    struct MatTexInfo { uint32_t base, width, height, mipCount; };   // base: first texel in dMatTexels, 0xFFFFFFFF: no material names it
+    // base: first texel in dMatTexels (format 0) or first unit in dMatBlocks (format CHORD_TEXFMT_BC*: kept as blocks), 0xFFFFFFFF: no material names it
+    struct MatTexInfo { uint32_t base, width, height, mipCount, format; };
     std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads

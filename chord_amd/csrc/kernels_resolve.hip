@@ -26,11 +26,18 @@
 //                               sampled by sample_slot_aniso: up to N taps along the longer derivative, each
 //                               the whole per-level pipeline, averaged in index order.  A lane loops to its own tap count; the slot's
 //                               level records are read once, before the loop.  <2> is not touched: it is what N = 1 launches.
+//     <4>, <5>                  the twins of <2> and <3> that chordvis_resolve_material launches while the uploaded store holds a
+//                               chain kept as blocks (chordvis_set_material_texture_store, CHORD_TEXSTORE_BLOCKS).  A slot's format
+//                               is part of its wave-uniform record: a texel slot runs sample_level as <2> / <3> do, a block slot
+//                               sample_level_blocks -- the same wrap arithmetic, then per tap the 8 or 16 bytes of the block that
+//                               holds the texel and bc_decode.h's decode of that one texel into the RGBA8 word the upload decoder
+//                               would have stored; decode_texel and the filter arithmetic behind it are shared.
 
 // The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
 // does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
 
 #include "device_layer.h"
+#include "bc_decode.h"
 #include "device_math.h"
 #include "material_tables.h"
 #include "texel_wrap.h"
@@ -135,6 +142,11 @@ template <int kLevel> struct KernelArgs : ResolveArgs {};
 template <> struct KernelArgs<1> : ResolveArgs { SurfaceArgs e; };
 template <> struct KernelArgs<2> : ResolveArgs { SurfaceArgs e; MaterialArgs m; };
 template <> struct KernelArgs<3> : KernelArgs<2> { uint32_t kmax; };   // log2 of the context's maximum anisotropy (1 .. 4)
+template <> struct KernelArgs<4> : KernelArgs<2> { const uint2* blocks; };   // dMatBlocks: the chains kept as blocks, 8-byte units
+template <> struct KernelArgs<5> : KernelArgs<3> { const uint2* blocks; };
+// the texel stores a slot's levels may live in; blocks == null at compile time (kBlocks false): texels alone, today's code
+template <bool kBlocks> struct TexelStores { const uint32_t* __restrict__ texels; };
+template <> struct TexelStores<true> { const uint32_t* __restrict__ texels; const uint2* __restrict__ blocks; uint32_t format; };
 
 // ---- the pinned sampler ------------------------------------------------------------------------------
 __device__ const uint32_t kSrgbBits[256] = {CHORD_SRGB_TABLE_BITS};
@@ -178,6 +190,72 @@ __device__ __forceinline__ float4 sample_level(const uint32_t* __restrict__ texe
     return make_float4(bil(a00.x, a10.x, a01.x, a11.x), bil(a00.y, a10.y, a01.y, a11.y), bil(a00.z, a10.z, a01.z, a11.z), bil(a00.w, a10.w, a01.w, a11.w));
 }
 
+// Texel (ix, iy), already wrapped, of a level kept as blocks: the unit(s) of block (ix >> 2, iy >> 2), row-major, and DESIGN.md 2 item
+// 9(h)'s decode of the one texel -- the RGBA8 word texture_decode_kernel would have stored.  format is wave-uniform.
+__device__ __forceinline__ uint32_t block_texel(const uint2* __restrict__ level, uint32_t blocksPerRow, uint32_t format, int32_t ix, int32_t iy)
+{
+    const uint32_t b = (uint32_t)(iy >> 2) * blocksPerRow + (uint32_t)(ix >> 2), i = (uint32_t)(iy & 3) * 4u + (uint32_t)(ix & 3);
+    uint2 q0, q1;                                                                       // the block's first unit, and its last (the same one in BC1_RGB and BC4)
+    if (format == CHORD_TEXFMT_BC1_RGB || format == CHORD_TEXFMT_BC4) q0 = q1 = level[b];
+    else {
+        const uint4 q = *reinterpret_cast<const uint4*>(level + 2u * b);                // (16-byte aligned: chains are, and every level before is whole pairs)
+        q0 = make_uint2(q.x, q.y); q1 = make_uint2(q.z, q.w);
+    }
+    uint32_t w = 0xFF000000u;
+    if (format != CHORD_TEXFMT_BC1_RGB) {                                               // BC3: alpha; BC4, BC5: r
+        const uint32_t v = bc_channel_texel(q0, i);
+        w = format == CHORD_TEXFMT_BC3 ? v << 24 : w | v;
+    }
+    if (format == CHORD_TEXFMT_BC5) w |= bc_channel_texel(q1, i) << 8;                  // g
+    else if (format != CHORD_TEXFMT_BC4) w |= bc_colour_texel(q1, format == CHORD_TEXFMT_BC3, i);
+    return w;
+}
+
+// sample_level over a level kept as blocks: the same statements, block_texel in place of the texel load
+template <bool kSrgb>
+__device__ __forceinline__ float4 sample_level_blocks(const uint2* __restrict__ blocks, uint32_t format, const DMatLevel& L, uint32_t wrapS, uint32_t wrapT,
+                                                      bool linear, float u, float v, const float* srgb)
+{
+    const int32_t W = (int32_t)(L.dims & 0xFFFFu) + 1, H = (int32_t)(L.dims >> 16) + 1;
+    const float fW = (float)W, fH = (float)H;
+    const uint2* base = blocks + L.base;
+    const uint32_t bpr = ((L.dims & 0xFFFFu) + 4u) >> 2;
+    if (!linear) {
+        const int32_t ix = wrap_index(texel_floor(u * fW), W, wrapS, L.magicS, L.biasS), iy = wrap_index(texel_floor(v * fH), H, wrapT, L.magicT, L.biasT);
+        return decode_texel<kSrgb>(block_texel(base, bpr, format, ix, iy), srgb);
+    }
+    const float x = u * fW - 0.5f, y = v * fH - 0.5f;
+    const int32_t x0 = texel_floor(x), y0 = texel_floor(y);
+    float fx = x - (float)x0, fy = y - (float)y0;
+    if (!(fabsf(x) < 1.0e9f)) fx = 0.0f;
+    if (!(fabsf(y) < 1.0e9f)) fy = 0.0f;
+    int32_t ix0, ix1, iy0, iy1;
+    wrap_pair(x0, W, wrapS, L.magicS, L.biasS, ix0, ix1);
+    wrap_pair(y0, H, wrapT, L.magicT, L.biasT, iy0, iy1);
+    // four independent fetches: taking the footprints that lie in one block (9 of 16) through a branch of their own that loads and
+    // prepares the block once was measured 10 to 35 % slower -- lanes of a wave rarely agree, so it runs both paths
+    const uint32_t w00 = block_texel(base, bpr, format, ix0, iy0), w10 = block_texel(base, bpr, format, ix1, iy0);
+    const uint32_t w01 = block_texel(base, bpr, format, ix0, iy1), w11 = block_texel(base, bpr, format, ix1, iy1);
+    const float4 a00 = decode_texel<kSrgb>(w00, srgb), a10 = decode_texel<kSrgb>(w10, srgb);
+    const float4 a01 = decode_texel<kSrgb>(w01, srgb), a11 = decode_texel<kSrgb>(w11, srgb);
+    auto bil = [&](float c00, float c10, float c01, float c11) {
+        const float top = c00 + (c10 - c00) * fx, bot = c01 + (c11 - c01) * fx;
+        return top + (bot - top) * fy;
+    };
+    return make_float4(bil(a00.x, a10.x, a01.x, a11.x), bil(a00.y, a10.y, a01.y, a11.y), bil(a00.z, a10.z, a01.z, a11.z), bil(a00.w, a10.w, a01.w, a11.w));
+}
+
+// one level of a slot wherever it lives
+template <bool kSrgb, bool kBlocks>
+__device__ __forceinline__ float4 sample_level(const TexelStores<kBlocks>& T, const DMatLevel& L, uint32_t wrapS, uint32_t wrapT, bool linear,
+                                               float u, float v, const float* srgb)
+{
+    if constexpr (kBlocks) {
+        if (T.format) return sample_level_blocks<kSrgb>(T.blocks, T.format, L, wrapS, wrapT, linear, u, v, srgb);
+    }
+    return sample_level<kSrgb>(T.texels, L, wrapS, wrapT, linear, u, v, srgb);
+}
+
 // level of detail in 1/256 steps from the bit pattern of the squared footprint: the exponent and the top 8 mantissa bits are the
 // piecewise-linear log2 of rho2 in Q8, halved for the square.  A footprint that is not finite or not above 0 gives 0.
 __device__ __forceinline__ int32_t footprint_lodq(float4 g, float fW, float fH)
@@ -190,8 +268,8 @@ __device__ __forceinline__ int32_t footprint_lodq(float4 g, float fW, float fH)
 }
 
 // S: a slot with mips > 0, read wave-uniformly; u, v, g (du/dx, dv/dx, du/dy, dv/dy) per lane
-template <bool kSrgb>
-__device__ __forceinline__ float4 sample_slot(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g, const float* srgb)
+template <bool kSrgb, bool kBlocks>
+__device__ __forceinline__ float4 sample_slot(const TexelStores<kBlocks>& texels, const DMatSlot& S, float u, float v, float4 g, const float* srgb)
 {
     const uint32_t d0 = S.levels[0].dims;
     const int32_t lodq = footprint_lodq(g, (float)((d0 & 0xFFFFu) + 1u), (float)((d0 >> 16) + 1u));
@@ -204,10 +282,10 @@ __device__ __forceinline__ float4 sample_slot(const uint32_t* __restrict__ texel
         else if (filter & CHORD_MATSLOT_MIP_LINEAR) { l0 = min((uint32_t)lodq >> 8, last); l1 = min(l0 + 1u, last); }
     }
     const DMatLevel L0 = S.levels[l0];
-    float4 c = sample_level<kSrgb>(texels, L0, S.wrapS, S.wrapT, linear, u, v, srgb);
+    float4 c = sample_level<kSrgb, kBlocks>(texels, L0, S.wrapS, S.wrapT, linear, u, v, srgb);
     if (l1 != l0) {                                       // (c0 + (c0 - c0) * f is c0: the second level is skipped when it is the first)
         const DMatLevel L1 = S.levels[l1];
-        const float4 c1 = sample_level<kSrgb>(texels, L1, S.wrapS, S.wrapT, linear, u, v, srgb);
+        const float4 c1 = sample_level<kSrgb, kBlocks>(texels, L1, S.wrapS, S.wrapT, linear, u, v, srgb);
         const float f = (float)(lodq & 255) * (1.0f / 256.0f);
         c = make_float4(c.x + (c1.x - c.x) * f, c.y + (c1.y - c.y) * f, c.z + (c1.z - c.z) * f, c.w + (c1.w - c.w) * f);
     }
@@ -220,8 +298,8 @@ __device__ __forceinline__ float4 sample_slot(const uint32_t* __restrict__ texel
 // (i >= 1), c_0 + d * (1 / n): equal taps give c_0 exactly, which a running sum of the taps does not (3c is not c's neighbour).
 // Powers of two make t_i, 1 / n and the level shift exact.  k = 0 (isotropic, magnified, not finite): sample_slot's path, no offset
 // formed, c_0 returned as it is.
-template <bool kSrgb>
-__device__ __forceinline__ float4 sample_slot_aniso(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g, uint32_t kmax,
+template <bool kSrgb, bool kBlocks>
+__device__ __forceinline__ float4 sample_slot_aniso(const TexelStores<kBlocks>& texels, const DMatSlot& S, float u, float v, float4 g, uint32_t kmax,
                                                     const float* srgb)
 {
     const uint32_t d0 = S.levels[0].dims;
@@ -259,9 +337,9 @@ __device__ __forceinline__ float4 sample_slot_aniso(const uint32_t* __restrict__
     for (int32_t i = 0; i < n; i++) {
         float ui = u, vi = v;
         if (k) { const float t = (float)(2 * i + 1 - n) * inv2n; ui = u + du * t; vi = v + dv * t; }
-        float4 c = sample_level<kSrgb>(texels, L0, wrapS, wrapT, linear, ui, vi, srgb);
+        float4 c = sample_level<kSrgb, kBlocks>(texels, L0, wrapS, wrapT, linear, ui, vi, srgb);
         if (l1 != l0) {
-            const float4 c1 = sample_level<kSrgb>(texels, L1, wrapS, wrapT, linear, ui, vi, srgb);
+            const float4 c1 = sample_level<kSrgb, kBlocks>(texels, L1, wrapS, wrapT, linear, ui, vi, srgb);
             c = make_float4(c.x + (c1.x - c.x) * f, c.y + (c1.y - c.y) * f, c.z + (c1.z - c.z) * f, c.w + (c1.w - c.w) * f);
         }
         if (i == 0) c0 = c;
@@ -271,13 +349,17 @@ __device__ __forceinline__ float4 sample_slot_aniso(const uint32_t* __restrict__
     return c0;
 }
 
-// a slot of the material loop: <2> samples it with sample_slot, <3> with sample_slot_aniso
+// a slot of the material loop: <2> and <4> sample it with sample_slot, <3> and <5> with sample_slot_aniso; <4> and <5> look at its format
 template <int kLevel, bool kSrgb>
 __device__ __forceinline__ float4 sample_material_slot(const uint32_t* __restrict__ texels, const DMatSlot& S, float u, float v, float4 g,
                                                        const KernelArgs<kLevel>& a, const float* srgb)
 {
-    if constexpr (kLevel >= 3) return sample_slot_aniso<kSrgb>(texels, S, u, v, g, a.kmax, srgb);
-    else return sample_slot<kSrgb>(texels, S, u, v, g, srgb);
+    constexpr bool kBlocks = kLevel >= 4;
+    TexelStores<kBlocks> T;
+    T.texels = texels;
+    if constexpr (kBlocks) { T.blocks = a.blocks; T.format = S.format; }
+    if constexpr (kLevel == 3 || kLevel == 5) return sample_slot_aniso<kSrgb, kBlocks>(T, S, u, v, g, a.kmax, srgb);
+    else return sample_slot<kSrgb, kBlocks>(T, S, u, v, g, srgb);
 }
 
 template <int kLevel>
@@ -627,11 +709,21 @@ void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const C
     // pixelNormal reads the pixel's vertex normal, and its tangent and bitangent when some material has a normal texture
     a.m.needSurface = m.pixelNormal ? (SURFACE_NORMAL | (c->matAnyNormalTexture ? SURFACE_TANGENT | SURFACE_BITANGENT : 0u)) : 0u;
     const uint32_t waves = a.blocksX * ((c->height + 3u) / 4u);
+    const dim3 grid((waves + 3u) / 4u), block(256);
+    const uint2* blocks = reinterpret_cast<const uint2*>(c->dMatBlocks);
     if (c->matAnisotropy > 1u) {                                         // chordvis_set_material_anisotropy: 2, 4, 8 or 16
         a.kmax = (uint32_t)__builtin_ctz(c->matAnisotropy);
-        CHORD_LAUNCH(c, resolve_attributes_kernel<3>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, a);
+        if (c->matBlockUnits) {                                          // a chain kept as blocks (CHORD_TEXSTORE_BLOCKS): the twin that reads both stores
+            KernelArgs<5> b;
+            static_cast<KernelArgs<3>&>(b) = a; b.blocks = blocks;
+            CHORD_LAUNCH(c, resolve_attributes_kernel<5>, grid, block, 0, c->stream, b);
+        } else CHORD_LAUNCH(c, resolve_attributes_kernel<3>, grid, block, 0, c->stream, a);
+    } else if (c->matBlockUnits) {
+        KernelArgs<4> b;
+        static_cast<KernelArgs<2>&>(b) = a; b.blocks = blocks;
+        CHORD_LAUNCH(c, resolve_attributes_kernel<4>, grid, block, 0, c->stream, b);
     } else {
-        CHORD_LAUNCH(c, resolve_attributes_kernel<2>, dim3((waves + 3u) / 4u), dim3(256), 0, c->stream, static_cast<const KernelArgs<2>&>(a));
+        CHORD_LAUNCH(c, resolve_attributes_kernel<2>, grid, block, 0, c->stream, static_cast<const KernelArgs<2>&>(a));
     }
 }
 

@@ -1,57 +1,35 @@
 // Block-compressed textures (CHORD_TEXFMT_BC1_RGB / BC3 / BC4 / BC5: what the reference's material import stores,
 // asset_gltf_material.cpp:80-110, written by stb_dxt through asset_texture_helper.cpp's mipmapCompressBC1/3/4/5) expanded at upload
 // into the texel stores the library already has: RGBA8 words of dMatTexels (chordvis_upload_material_textures) or the alpha bytes of
-// dTexAlpha (chordvis_upload_scene).  The decode is the pinned one of DESIGN.md 2 item 9(h): integers only, floor divisions.
+// dTexAlpha (chordvis_upload_scene).  The decode is the pinned one of DESIGN.md 2 item 9(h), defined in bc_decode.h.
 //
 // One launch per upload.  The grid is flat over the blocks of every level of every compressed texture of the upload; a lane owns
 // one block: it reads the block once (8 or 16 bytes; consecutive lanes read consecutive blocks) and writes its four texel rows, so
 // that the lanes of a wave write consecutive 16-byte pieces (RGBA8) or 4-byte pieces (alpha) of one texel row per store
 // instruction.  Texels of an edge block outside the level are never written.
 #include "device_layer.h"
+#include "bc_decode.h"
 
 namespace chord {
 
 namespace {
 
-// value k of an alpha / single-channel block with the endpoints a0, a1
-__device__ __forceinline__ uint32_t channel_value(uint32_t a0, uint32_t a1, uint32_t k)
-{
-    if (k < 2u) return k ? a1 : a0;
-    if (a0 > a1) return ((8u - k) * a0 + (k - 1u) * a1) / 7u;
-    if (k < 6u) return ((6u - k) * a0 + (k - 1u) * a1) / 5u;
-    return k == 6u ? 0u : 255u;
-}
-
 // the 16 values of a channel block, shifted to bit `shift` of out[i] (OR-ed in)
 __device__ __forceinline__ void channel_block(uint2 q, uint32_t shift, uint32_t out[16])
 {
     const uint32_t a0 = q.x & 0xFFu, a1 = (q.x >> 8) & 0xFFu;
-    const unsigned long long bits = ((unsigned long long)q.y << 16) | (q.x >> 16);     // the 48 index bits, least significant first
+    const unsigned long long bits = bc_channel_bits(q);
 #pragma unroll
-    for (uint32_t i = 0; i < 16u; i++) out[i] |= channel_value(a0, a1, (uint32_t)(bits >> (3u * i)) & 7u) << shift;
+    for (uint32_t i = 0; i < 16u; i++) out[i] |= bc_channel_value(a0, a1, (uint32_t)(bits >> (3u * i)) & 7u) << shift;
 }
 
-// the 16 colours of a colour block as R | G << 8 | B << 16 (OR-ed in).  fourColour: BC3 (always), BC1 when c0 > c1
+// the 16 colours of a colour block as R | G << 8 | B << 16 (OR-ed in).  alwaysFour: BC3
 __device__ __forceinline__ void colour_block(uint2 q, bool alwaysFour, uint32_t out[16])
 {
-    const uint32_t c0 = q.x & 0xFFFFu, c1 = q.x >> 16;
-    const uint32_t r0 = c0 >> 11, g0 = (c0 >> 5) & 63u, b0 = c0 & 31u, r1 = c1 >> 11, g1 = (c1 >> 5) & 63u, b1 = c1 & 31u;
-    const uint32_t R0 = (r0 << 3) | (r0 >> 2), G0 = (g0 << 2) | (g0 >> 4), B0 = (b0 << 3) | (b0 >> 2);
-    const uint32_t R1 = (r1 << 3) | (r1 >> 2), G1 = (g1 << 2) | (g1 >> 4), B1 = (b1 << 3) | (b1 >> 2);
-    const uint32_t p0 = R0 | G0 << 8 | B0 << 16, p1 = R1 | G1 << 8 | B1 << 16;
-    uint32_t p2, p3;
-    if (alwaysFour || c0 > c1) {
-        p2 = (2u * R0 + R1) / 3u | ((2u * G0 + G1) / 3u) << 8 | ((2u * B0 + B1) / 3u) << 16;
-        p3 = (R0 + 2u * R1) / 3u | ((G0 + 2u * G1) / 3u) << 8 | ((B0 + 2u * B1) / 3u) << 16;
-    } else {
-        p2 = (R0 + R1) / 2u | ((G0 + G1) / 2u) << 8 | ((B0 + B1) / 2u) << 16;
-        p3 = 0u;
-    }
+    uint32_t p0, p1, p2, p3;
+    bc_colour_palette(q.x, alwaysFour, p0, p1, p2, p3);
 #pragma unroll
-    for (uint32_t i = 0; i < 16u; i++) {
-        const uint32_t k = (q.y >> (2u * i)) & 3u;
-        out[i] |= (k & 2u) ? ((k & 1u) ? p3 : p2) : ((k & 1u) ? p1 : p0);
-    }
+    for (uint32_t i = 0; i < 16u; i++) out[i] |= bc_palette_pick((q.y >> (2u * i)) & 3u, p0, p1, p2, p3);
 }
 
 template <bool ALPHA>

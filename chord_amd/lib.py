@@ -77,6 +77,7 @@ class TextureMips(C.Structure):
 
 
 TEXMIPS_SRGB, TEXMIPS_COVERAGE, TEXMIPS_FULL = 1, 2, 0xFFFFFFFF
+TEXSTORE_EXPANDED, TEXSTORE_BLOCKS = 0, 1          # chordvis_set_material_texture_store
 
 
 class HZB(C.Structure):
@@ -229,6 +230,9 @@ def _load():
         "chordvis_resolve_material": (i32, [vp, CountAndCmd, P(ResolveDesc), P(ResolveTargets), P(SurfaceTargets), P(MaterialTargets)]),
         "chordvis_set_material_anisotropy": (i32, [vp, u32]),
         "chordvis_material_anisotropy": (u32, [vp]),
+        "chordvis_set_material_texture_store": (i32, [vp, u32]),
+        "chordvis_material_texture_store": (u32, [vp]),
+        "chordvis_material_texture_memory": (i32, [vp, P(u64), P(u64)]),
         "chordvis_material_constants": (i32, [vp, vp]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),

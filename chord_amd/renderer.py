@@ -84,6 +84,22 @@ class VisibilityRenderer:
     def material_anisotropy(self):
         return int(L.lib.chordvis_material_anisotropy(self._ctx))
 
+    def set_material_texture_store(self, mode):
+        """How LATER upload_material_textures calls store block-compressed textures: lib.TEXSTORE_EXPANDED (default: RGBA8 texels, 4
+        bytes each) or lib.TEXSTORE_BLOCKS (a BC chain whose every level is supplied keeps its blocks; the material resolve decodes
+        what it taps, to the same images).  Per context; kept across upload_scene and upload_material_textures; a store already
+        uploaded stays as it is."""
+        self._check(L.lib.chordvis_set_material_texture_store(self._ctx, int(mode)), "set_material_texture_store")
+
+    def material_texture_store(self):
+        return int(L.lib.chordvis_material_texture_store(self._ctx))
+
+    def material_texture_memory(self):
+        """(texelBytes, blockBytes) of the uploaded material textures: the RGBA8 store and the chains kept as blocks."""
+        t, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(L.lib.chordvis_material_texture_memory(self._ctx, C.byref(t), C.byref(b)), "material_texture_memory")
+        return t.value, b.value
+
     def set_texture_mips(self, settings):
         """Mip chains made on the GPU by LATER upload_scene / upload_material_textures calls: entry i, a
         lib.TextureMips or a (levels, flags, alphaCutoff8) tuple, belongs to texture id i; None or an empty list: none (the default).

@@ -654,6 +654,35 @@ int chordvis_resolve_material(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, 
  *           path and bits. */
 int chordvis_set_material_anisotropy(ChordCtx* ctx, uint32_t maxAnisotropy);
 uint32_t chordvis_material_anisotropy(const ChordCtx* ctx);   /* the last accepted value (1 after chordvis_create) */
+/* Opt-in: how LATER chordvis_upload_material_textures calls store block-compressed textures on the device.
+ *   CHORD_TEXSTORE_EXPANDED (the default)  every texture is expanded to RGBA8 at upload, 4 bytes per texel: what the library does
+ *                                          without this call, the same launches, kernels and bits.
+ *   CHORD_TEXSTORE_BLOCKS                  a texture a material slot names whose format is CHORD_TEXFMT_BC1_RGB / BC3 / BC4 / BC5 and
+ *                                          whose every level is supplied (chordvis_set_texture_mips gives it no made level: levels ==
+ *                                          0 or L <= mipCount) keeps its blocks: its chain is copied as it is into a block store
+ *                                          (8-byte units, every chain 16-byte aligned, the levels in ChordTexture's order), takes no
+ *                                          texel of the RGBA8 store, and needs no staging buffer and no decode launch.
+ *                                          chordvis_resolve_material then decodes the texels of each footprint from their blocks (the
+ *                                          pinned decode of DESIGN.md 2 item 9(h)) and produces exactly the images of mode EXPANDED;
+ *                                          it takes kernels of its own for that only while the uploaded store holds such a chain.
+ *                                          Everything else -- RGBA8 textures, block-compressed textures that get made levels (expanded
+ *                                          whole first) -- is stored as in mode EXPANDED, and both kinds may sit in one upload.
+ * Any other value: CHORDVIS_E_INVALID, the setting unchanged, chordvis_last_error names the allowed values.  Per context; kept across
+ * chordvis_upload_scene and chordvis_upload_material_textures; read by chordvis_upload_material_textures alone: a store that is
+ * already uploaded stays as it is, and chordvis_upload_scene (the alpha its masked buckets test) never keeps blocks, so frames are
+ * the same words in both modes.  On a ChordGroup, set the ranks' contexts before the group's material upload.
+ * Caps: the 4 G texel cap of chordvis_upload_material_textures counts expanded texels only; the block store has its own, 2^32
+ * units (32 GiB), beyond which the upload returns CHORDVIS_E_CAPACITY and keeps nothing.
+ * chordvis_readback_material_texture keeps its contract for a texture kept as blocks: the asked level is expanded into a temporary
+ * device buffer by the upload decoder (one launch) and copied out. */
+#define CHORD_TEXSTORE_EXPANDED 0u
+#define CHORD_TEXSTORE_BLOCKS   1u
+int chordvis_set_material_texture_store(ChordCtx* ctx, uint32_t mode);
+uint32_t chordvis_material_texture_store(const ChordCtx* ctx);   /* the last accepted value (0 after chordvis_create) */
+/* Device memory of the uploaded material textures: texelBytes = 4 x the texels of the RGBA8 store, blockBytes = the sum over the
+ * chains kept as blocks of chordvis_texture_chain_bytes rounded up to 16.  Either pointer may be NULL.  CHORDVIS_E_INVALID when no
+ * material textures are uploaded. */
+int chordvis_material_texture_memory(ChordCtx* ctx, uint64_t* texelBytes, uint64_t* blockBytes);
 /* The two constant tables of the material resolve as the library holds them (host call, no context): the sRGB8 -> linear decode
  * (256 floats) and sRGB_2_AP1 (9 floats, row-major).  Either may be NULL. */
 int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9]);
