@@ -218,6 +218,87 @@ struct TexMipJob {
     }
 };
 
+// ---- block compression at upload (chordvis_set_texture_compress; kernels_texture.hip) ----
+#define CHORD_TEXCOMPRESS_NAMES "0 (none), 1 (BC1_RGB), 2 (BC3), 3 (BC4), 4 (BC5)"
+
+// The encoder's four tables (device_layer.h CHORD_TEXENC_*), derived: the optimal single-colour pairs by the exhaustive scan of
+// DESIGN.md 2 item 9(j), the midpoints as the float nearest to (e(q) + e(q + 1)) / 510 rounded to six decimals
+void tex_encode_tables(uint32_t out[CHORD_TEXENC_TABLE_WORDS])
+{
+    std::memset(out, 0, CHORD_TEXENC_TABLE_WORDS * 4u);
+    for (int bits = 5; bits <= 6; bits++) {
+        const int size = 1 << bits;
+        auto e = [bits](int c) { return bits == 5 ? (c * 33) >> 2 : (c * 65) >> 4; };
+        const uint32_t pairs = bits == 5 ? CHORD_TEXENC_OMATCH5 : CHORD_TEXENC_OMATCH6, mids = bits == 5 ? CHORD_TEXENC_MID5 : CHORD_TEXENC_MID6;
+        for (int target = 0; target < 256; target++) {
+            int bestMn = 0, bestMx = 0, bestErr = 256 * 100;
+            for (int mn = 0; mn < size; mn++)
+                for (int mx = 0; mx < size; mx++) {
+                    const int err = std::abs((2 * e(mx) + e(mn)) / 3 - target) * 100 + std::abs(e(mx) - e(mn)) * 3;
+                    if (err < bestErr) { bestMn = mn; bestMx = mx; bestErr = err; }
+                }
+            out[pairs + (target >> 1)] |= (uint32_t)(bestMx | bestMn << 8) << (16 * (target & 1));
+        }
+        for (int q = 0; q < size; q++) {
+            float m = 1.0f;
+            if (q + 1 < size) {
+                // six decimals of k / 510, rounded to nearest (2 * 10^6 k = 510 (2 m + 1) has no solution: never a tie), then the
+                // nearest float: the decimal's nearest double first, which sits far from every float's rounding boundary
+                const long long k = e(q) + e(q + 1), micro = (k * 2000000ll + 510ll) / 1020ll;
+                m = (float)((double)micro / 1000000.0);
+            }
+            std::memcpy(&out[mids + q], &m, 4);
+        }
+    }
+}
+
+// The levels one upload encodes: their texels are in a staging buffer when the job runs (copied, decoded or made there), one record
+// per level goes to a small device table, ONE kernel launch encodes them all into dMatBlocks; the table is freed after the
+// synchronise (the staging buffer is the caller's).
+struct TexEncodeJob {
+    std::vector<chord::DTexEncRec> recs;
+    uint32_t blocks = 0;
+
+    // src: level 0's first texel in the staging buffer; dst: the chain's first unit in dMatBlocks; levels from .. L-1 are encoded
+    void add(uint32_t src, uint32_t dst, uint32_t width, uint32_t height, uint32_t from, uint32_t L, uint32_t format)
+    {
+        const uint32_t unitsPerBlock = tex_block_bytes(format) / 8u;
+        for (uint32_t l = 0; l < L; l++) {
+            const uint32_t w = std::max(1u, width >> l), h = std::max(1u, height >> l), bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
+            if (l >= from) {
+                recs.push_back(chord::DTexEncRec{blocks, src, dst, w, h, bw, format, 0u});
+                blocks += bw * bh;
+            }
+            src += w * h; dst += bw * bh * unitsPerBlock;
+        }
+    }
+
+    int run(ChordCtx* c, const char* who, const uint32_t* staging, void* blockStore)
+    {
+        if (recs.empty()) return CHORDVIS_OK;
+        if (!c->dTexEncTables) {
+            uint32_t tables[CHORD_TEXENC_TABLE_WORDS];
+            tex_encode_tables(tables);
+            hipError_t e = hipMalloc((void**)&c->dTexEncTables, sizeof(tables));
+            if (e == hipSuccess) e = hipMemcpy(c->dTexEncTables, tables, sizeof(tables), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { dfree(c->dTexEncTables); return fail(c, CHORDVIS_E_HIP, who, e); }
+        }
+        const uint32_t count = (uint32_t)recs.size();
+        recs.push_back(chord::DTexEncRec{blocks, 0u, 0u, 1u, 1u, 1u, 0u, 0u});        // closes the table
+        chord::DTexEncRec* dRecs = nullptr;
+        hipError_t e = hipMalloc((void**)&dRecs, recs.size() * sizeof(recs[0]));
+        if (e == hipSuccess) e = hipMemcpy(dRecs, recs.data(), recs.size() * sizeof(recs[0]), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            chord::launch_texture_encode(c, dRecs, count, blocks, c->dTexEncTables, staging, blockStore);
+            e = hipGetLastError();
+            const hipError_t es = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = es;
+        }
+        if (dRecs) (void)hipFree(dRecs);
+        return e == hipSuccess ? CHORDVIS_OK : fail(c, CHORDVIS_E_HIP, who, e);
+    }
+};
+
 // what chordvis_upload_material_textures keeps
 void drop_material_textures(ChordCtx* c)
 {
@@ -590,7 +671,7 @@ int chordvis_destroy(ChordCtx* c)
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -1025,6 +1106,13 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     TexDecodeJob decode;
     TexMipJob mips;                                                        // chordvis_set_texture_mips: the levels made here
     std::vector<uint32_t> texBase(nTex, 0xFFFFFFFFu), texLevels(nTex, 0u), texKept(nTex, 0u);   // texKept: the format of a chain kept as blocks
+    // chordvis_set_texture_compress: the chains encoded here.  Their texels live in a staging buffer of their own (texStage: level
+    // 0's first texel in it) from the copy through the decode and the mip generation to the encode, and are freed with it
+    size_t stageCount = 0;
+    TexDecodeJob stageDecode;
+    TexMipJob stageMips;
+    TexEncodeJob encode;
+    std::vector<uint32_t> texStage(nTex, 0xFFFFFFFFu);
     for (uint32_t t = 0; t < nTex; t++) {
         texLevels[t] = s->textures[t].mipCount;
         if (!named[t]) continue;
@@ -1035,6 +1123,9 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
         ChordTextureMips ms;
         const uint32_t L = tex_levels(c, t, tx, ms);                       // (>= mipCount; the levels beyond it are made on the device)
+        const uint32_t target = (c->matTextureStore == CHORD_TEXSTORE_BLOCKS && t < c->texCompress.size()) ? c->texCompress[t] : 0u;
+        if (target && tex_block_bytes(tx.format) && tx.format != target)
+            return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a block-compressed texture's format differs from its chordvis_set_texture_compress target (supplied levels are never re-encoded)");
         if (c->matTextureStore == CHORD_TEXSTORE_BLOCKS && tex_block_bytes(tx.format) && L == tx.mipCount) {
             uint64_t bytes = 0;
             (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &bytes);
@@ -1042,6 +1133,22 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             if (blockUnits + units >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 2^32 8-byte units of textures kept as blocks");
             texBase[t] = (uint32_t)blockUnits; texKept[t] = tx.format;
             blockUnits += units;
+            continue;
+        }
+        if (target) {
+            // an RGBA8 source: every level is encoded; a source in the target format with made levels: those alone
+            uint64_t bytes = 0;
+            (void)chordvis_texture_chain_bytes(target, tx.width, tx.height, L, &bytes);
+            const uint64_t units = ((bytes + 15ull) & ~15ull) / 8u;
+            if (blockUnits + units >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 2^32 8-byte units of textures kept as blocks");
+            const size_t count = tex_chain_texels(tx.width, tx.height, L);
+            if (stageCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels staged for compression in one upload");
+            texBase[t] = (uint32_t)blockUnits; texKept[t] = target; texLevels[t] = L; texStage[t] = (uint32_t)stageCount;
+            if (tx.format != CHORD_TEXFMT_RGBA8) stageDecode.add(tx, (uint32_t)stageCount);
+            stageMips.add((uint32_t)stageCount, tx.width, tx.height, tx.mipCount, L, ms,
+                          (ms.flags & CHORD_TEXMIPS_COVERAGE) && (tx.format == CHORD_TEXFMT_RGBA8 || tx.format == CHORD_TEXFMT_BC3));
+            encode.add((uint32_t)stageCount, (uint32_t)blockUnits, tx.width, tx.height, tx.format == CHORD_TEXFMT_RGBA8 ? 0u : tx.mipCount, L, target);
+            stageCount += count; blockUnits += units;
             continue;
         }
         const size_t count = tex_chain_texels(tx.width, tx.height, L);
@@ -1105,7 +1212,7 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         if ((rc = dalloc(c, &c->dMatTexels, texelCount))) { drop_material_textures(c); return rc; }
         for (uint32_t t = 0; t < nTex; t++) {
             const ChordTexture& tx = s->textures[t];
-            if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8) continue;
+            if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8 || texKept[t]) continue;     // (texKept: encoded below, from the staging buffer)
             const size_t count = tex_chain_texels(tx.width, tx.height, tx.mipCount);
             hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8, count * 4, hipMemcpyHostToDevice);
             if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
@@ -1118,12 +1225,30 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t t = 0; t < nTex; t++) {
             if (!texKept[t]) continue;
             const ChordTexture& tx = s->textures[t];
-            uint64_t bytes = 0;
-            (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &bytes);
-            hipError_t e = hipMemcpy(c->dMatBlocks + texBase[t], tx.rgba8, bytes, hipMemcpyHostToDevice);
+            uint64_t bytes = 0, supplied = 0;                              // of the stored chain / of the levels that arrive as blocks
+            (void)chordvis_texture_chain_bytes(texKept[t], tx.width, tx.height, texLevels[t], &bytes);
+            if (tx.format != CHORD_TEXFMT_RGBA8) (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &supplied);
+            hipError_t e = supplied ? hipMemcpy(c->dMatBlocks + texBase[t], tx.rgba8, supplied, hipMemcpyHostToDevice) : hipSuccess;
             if (e == hipSuccess && (bytes & 15ull)) e = hipMemset((uint8_t*)(c->dMatBlocks + texBase[t]) + bytes, 0, 16u - (bytes & 15ull));   // (the chain's padding)
             if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
         }
+    }
+    if (stageCount) {
+        // the chains to encode: supplied texels copied, supplied blocks decoded, the other levels made -- the kernels of the texel
+        // store on a buffer of their own --, then one launch encodes them all
+        uint32_t* dStage = nullptr;
+        hipError_t e = hipMalloc((void**)&dStage, stageCount * 4u);
+        for (uint32_t t = 0; t < nTex && e == hipSuccess; t++) {
+            const ChordTexture& tx = s->textures[t];
+            if (texStage[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8) continue;
+            e = hipMemcpy(dStage + texStage[t], tx.rgba8, tex_chain_texels(tx.width, tx.height, tx.mipCount) * 4u, hipMemcpyHostToDevice);
+        }
+        rc = e == hipSuccess ? CHORDVIS_OK : fail(c, CHORDVIS_E_HIP, "upload_material_textures: staging for compression", e);
+        if (!rc) rc = stageDecode.run(c, "upload_material_textures: texture decode", dStage, nullptr, false);
+        if (!rc) rc = stageMips.run(c, "upload_material_textures: texture mips", dStage, nullptr, false);
+        if (!rc) rc = encode.run(c, "upload_material_textures: texture encode", dStage, c->dMatBlocks);
+        if (dStage) (void)hipFree(dStage);
+        if (rc) { drop_material_textures(c); return rc; }
     }
     c->matTex.resize(nTex);
     for (uint32_t t = 0; t < nTex; t++)
@@ -1164,6 +1289,22 @@ int chordvis_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t heigh
     if (mipCount > 32u) total += (unsigned __int128)(mipCount - 32u) * (bb ? bb : 4u);     // (1 x 1 from level 32 on)
     if (total > 0xFFFFFFFFFFFFFFFFull) return CHORDVIS_E_INVALID;
     *bytes = (uint64_t)total;
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_material_blocks(ChordCtx* c, uint32_t textureId, uint8_t* host, uint64_t bytes)
+{
+    if (!c || !host) return fail(c, CHORDVIS_E_INVALID, "readback_material_blocks: null argument");
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "readback_material_blocks: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (textureId >= c->matTex.size() || c->matTex[textureId].base == 0xFFFFFFFFu || !c->matTex[textureId].format)
+        return fail(c, CHORDVIS_E_INVALID, "readback_material_blocks: the texture is not kept as blocks (no material names it, or it is stored as texels)");
+    const ChordCtx::MatTexInfo& t = c->matTex[textureId];
+    uint64_t chain = 0;
+    (void)chordvis_texture_chain_bytes(t.format, t.width, t.height, t.mipCount, &chain);
+    if (bytes != chain) return fail(c, CHORDVIS_E_INVALID, "readback_material_blocks: bytes differs from chordvis_texture_chain_bytes of the stored chain");
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    CHORD_HIP(c, hipMemcpy(host, c->dMatBlocks + t.base, chain, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }
 
@@ -1974,6 +2115,24 @@ int chordvis_texture_mips(const ChordCtx* c, uint32_t textureId, ChordTextureMip
 {
     if (!c || !out) return CHORDVIS_E_INVALID;
     *out = textureId < c->texMips.size() ? c->texMips[textureId] : ChordTextureMips{0u, 0u, 0u, 0u};
+    return CHORDVIS_OK;
+}
+
+int chordvis_set_texture_compress(ChordCtx* c, const uint32_t* perTextureFormat, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!perTextureFormat || !count) { c->texCompress.clear(); return CHORDVIS_OK; }
+    for (uint32_t t = 0; t < count; t++)
+        if (perTextureFormat[t] && !tex_block_bytes(perTextureFormat[t]))
+            return fail(c, CHORDVIS_E_INVALID, "set_texture_compress: an entry is not allowed; allowed: " CHORD_TEXCOMPRESS_NAMES);
+    c->texCompress.assign(perTextureFormat, perTextureFormat + count);
+    return CHORDVIS_OK;
+}
+
+int chordvis_texture_compress(const ChordCtx* c, uint32_t textureId, uint32_t* format)
+{
+    if (!c || !format) return CHORDVIS_E_INVALID;
+    *format = textureId < c->texCompress.size() ? c->texCompress[textureId] : 0u;
     return CHORDVIS_OK;
 }
 

@@ -177,6 +177,28 @@ static_assert(sizeof(DTexMipRec) == 32 && sizeof(DTexTailRec) == 32 && sizeof(DT
 #define CHORD_TEXMIPS_TAIL 64u          // a source level of at most this size in both directions: the tail kernel takes the rest
 #define CHORD_TEXCOV_GROUP 4096u        // texels per workgroup of the coverage kernels
 
+// Block compression at upload (chordvis_set_texture_compress; kernels_texture.hip; bc_encode.h).
+// One level of one texture for texture_encode_kernel: the records of an upload form a flat grid over their output blocks, in the
+// order of the blocks; a closing record holds the total in firstBlock.
+struct DTexEncRec {            // 32 B
+    uint32_t firstBlock;       // blocks of all records before this one
+    uint32_t src;              // first texel of the level in the staging texels (RGBA8 words)
+    uint32_t dst;              // first block of the level in dMatBlocks, in units of 8 bytes
+    uint32_t width, height;    // of the level, in texels
+    uint32_t blocksPerRow;     // ceil(width / 4)
+    uint32_t format;           // CHORD_TEXFMT_BC*: what to encode to
+    uint32_t pad;
+};
+static_assert(sizeof(DTexEncRec) == 32, "DTexEncRec");
+// The encoder's four tables as words of one device buffer (ChordCtx::dTexEncTables; derived on the host at first use, copied to LDS by
+// every workgroup): the optimal single-colour pairs as max | min << 8, two targets per word (target t: bits 16 (t & 1) .. of word
+// t >> 1), for 5 and for 6 bits; then the midpoints of the 5-bit and of the 6-bit codes as float bits.
+#define CHORD_TEXENC_OMATCH5 0u
+#define CHORD_TEXENC_OMATCH6 128u
+#define CHORD_TEXENC_MID5 256u
+#define CHORD_TEXENC_MID6 288u
+#define CHORD_TEXENC_TABLE_WORDS 352u
+
 // extension of a masked triangle's 48-byte record, in the TWO slots behind it.  Everything a row unit of the tile kernel needs to
 // sample the triangle's alpha is in here -- the chosen level's first byte and size, the wraps, the material's factor and cut-off --
 // so a unit's set-up is one round trip (this record), not three dependent ones (extension -> material -> level offsets).
@@ -415,6 +437,8 @@ struct ChordCtx {
     std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
+    std::vector<uint32_t> texCompress;        // chordvis_set_texture_compress: per texture id, 0 or a CHORD_TEXFMT_BC* target; kept across uploads, read by chordvis_upload_material_textures under CHORD_TEXSTORE_BLOCKS
+    uint32_t* dTexEncTables = nullptr;        // CHORD_TEXENC_TABLE_WORDS words, made by the first upload that encodes
     std::vector<ChordTextureMips> texMips;    // chordvis_set_texture_mips: per texture id; kept across uploads, read by both
     chord::DGroupRef* dGroupRefs = nullptr;   // per flattened (object, group) instance (static: the object -> primitive binding is the scene's)
     chord::DBVHNode* dBvhNodes = nullptr;   // every primitive's tree (or null: the scene came without)
@@ -643,6 +667,10 @@ void launch_texture_mips_tail(ChordCtx* c, const DTexTailRec* recs, uint32_t cou
 // (zeroed by the caller), a wave per level picks its threshold into work[count * 256 + level], a pass rescales.  Three launches.
 void launch_texture_coverage(ChordCtx* c, const DTexCovRec* recs, uint32_t count, uint32_t groups, uint32_t scaleGroups,
                              uint32_t* work, uint32_t* texels, uint8_t* alpha, bool alphaOnly);
+// Encodes the levels of `count` records (recs[count] closes the table) from RGBA8 words of `texels` into blocks of `blocks` (8-byte
+// units); tables: CHORD_TEXENC_TABLE_WORDS words.  One launch on the context's stream.
+void launch_texture_encode(ChordCtx* c, const DTexEncRec* recs, uint32_t count, uint32_t totalBlocks, const uint32_t* tables,
+                           const uint32_t* texels, void* blocks);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -9,6 +9,7 @@
 // instruction.  Texels of an edge block outside the level are never written.
 #include "device_layer.h"
 #include "bc_decode.h"
+#include "bc_encode.h"
 
 namespace chord {
 
@@ -352,7 +353,66 @@ __global__ __launch_bounds__(256) void texture_coverage_rescale_kernel(const DTe
     }
 }
 
+// ---- block compression (chordvis_set_texture_compress; the encoder is bc_encode.h's) ----
+// One launch per upload, behind the mip generation.  The grid is flat over the output blocks of every level of every texture to
+// encode; a lane owns one block: it reads the block's four texel rows (16 bytes at once where the row piece is whole and aligned;
+// single words elsewhere and where the fill wraps: texel (x, y) of block (bx, by) is the level's ((4 bx + x) mod w, (4 by + y) mod
+// h)), keeps the 16 words in registers, and stores the block with one 8- or 16-byte store, consecutive lanes consecutive blocks.
+// The format is a field of the record, not a template argument: a workgroup's first record is uniform, but a lane steps on into
+// the records behind it (a chain's small levels hold a handful of blocks each), so one launch mixes formats within a wave.
+__global__ __launch_bounds__(256) void texture_encode_kernel(const DTexEncRec* __restrict__ recs, uint32_t count, uint32_t totalBlocks,
+                                                             const uint32_t* __restrict__ tables, const uint32_t* __restrict__ texels,
+                                                             uint2* __restrict__ blocks)
+{
+    __shared__ uint32_t tab[CHORD_TEXENC_TABLE_WORDS];
+    tab[threadIdx.x] = tables[threadIdx.x];
+    if (threadIdx.x + 256u < CHORD_TEXENC_TABLE_WORDS) tab[threadIdx.x + 256u] = tables[threadIdx.x + 256u];
+    __syncthreads();
+    const uint32_t first = blockIdx.x * 256u;
+    uint32_t lo = find_record<DTexEncRec, &DTexEncRec::firstBlock>(recs, count, first);
+    const uint32_t b = first + threadIdx.x;
+    if (b >= totalBlocks) return;
+    while (recs[lo + 1u].firstBlock <= b) lo++;             // (ends: the closing record's firstBlock is above every block)
+    const DTexEncRec R = recs[lo];
+
+    const uint32_t lb = b - R.firstBlock, by = lb / R.blocksPerRow, bx = lb - by * R.blocksPerRow;
+    const uint32_t x0 = bx * 4u;
+    uint32_t px[16];
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; r++) {
+        uint32_t y = by * 4u + r;
+        if (y >= R.height) y %= R.height;
+        const size_t t = (size_t)R.src + (size_t)y * R.width;
+        if (x0 + 4u <= R.width && ((t + x0) & 3u) == 0u) {
+            const uint4 q = *reinterpret_cast<const uint4*>(texels + t + x0);
+            px[4 * r] = q.x; px[4 * r + 1] = q.y; px[4 * r + 2] = q.z; px[4 * r + 3] = q.w;
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++) {
+                uint32_t x = x0 + i;
+                if (x >= R.width) x %= R.width;
+                px[4 * r + i] = texels[t + x];
+            }
+        }
+    }
+    if (R.format == CHORD_TEXFMT_BC1_RGB) blocks[(size_t)R.dst + lb] = bc_encode_colour(px, false, tab);
+    else if (R.format == CHORD_TEXFMT_BC4) blocks[(size_t)R.dst + lb] = bc_encode_channel(px, 0u);
+    else {
+        uint2 q0, q1;
+        if (R.format == CHORD_TEXFMT_BC3) { q0 = bc_encode_channel(px, 24u); q1 = bc_encode_colour(px, true, tab); }
+        else { q0 = bc_encode_channel(px, 0u); q1 = bc_encode_channel(px, 8u); }
+        *reinterpret_cast<uint4*>(blocks + (size_t)R.dst + 2u * lb) = make_uint4(q0.x, q0.y, q1.x, q1.y);     // (a chain starts 16-byte aligned and 16-byte blocks keep it so)
+    }
+}
+
 } // namespace
+
+void launch_texture_encode(ChordCtx* c, const DTexEncRec* recs, uint32_t count, uint32_t totalBlocks, const uint32_t* tables,
+                           const uint32_t* texels, void* blocks)
+{
+    if (!count || !totalBlocks) return;
+    CHORD_LAUNCH(c, texture_encode_kernel, dim3((totalBlocks + 255u) / 256u), dim3(256), 0, c->stream, recs, count, totalBlocks, tables, texels, (uint2*)blocks);
+}
 
 void launch_texture_decode(ChordCtx* c, const DTexLevelRec* recs, uint32_t count, uint32_t totalBlocks, const void* staging,
                            uint32_t* texels, uint8_t* alpha, bool alphaOnly)

@@ -233,6 +233,9 @@ def _load():
         "chordvis_set_material_texture_store": (i32, [vp, u32]),
         "chordvis_material_texture_store": (u32, [vp]),
         "chordvis_material_texture_memory": (i32, [vp, P(u64), P(u64)]),
+        "chordvis_set_texture_compress": (i32, [vp, P(u32), u32]),
+        "chordvis_texture_compress": (i32, [vp, u32, P(u32)]),
+        "chordvis_readback_material_blocks": (i32, [vp, u32, vp, u64]),
         "chordvis_material_constants": (i32, [vp, vp]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),

@@ -70,6 +70,23 @@ class VisibilityRenderer:
         self._check(L.lib.chordvis_readback_material_texture(self._ctx, int(texture), int(level), out.ctypes.data), "readback_material_texture")
         return out
 
+    def readback_material_blocks(self, texture, format=None, levels=None):
+        """uint8 array: the whole chain of a texture kept as blocks, in the layout of ChordTexture (after upload_material_textures
+        under lib.TEXSTORE_BLOCKS): the bytes supplied, or what set_texture_compress made the GPU encode.  format / levels: of
+        the stored chain (default: what the current compress and mips settings give the scene's texture).  A lib.ChordvisError
+        for a texture stored as texels."""
+        t = self.scene.texture_images[texture]
+        if format is None:
+            format = self.texture_compress(texture) or getattr(t, "format", 0)
+        if levels is None:
+            full = max(t.shape[0], t.shape[1]).bit_length()
+            levels, mips = self.texture_mips(texture)[0], getattr(t, "mips", full)      # (an image: Scene supplies its full chain)
+            levels = mips if not levels else max(mips, min(levels, full))
+        n = L.texture_chain_bytes(format, t.shape[1], t.shape[0], levels) if format else 0
+        out = np.zeros(max(1, n), dtype=np.uint8)
+        self._check(L.lib.chordvis_readback_material_blocks(self._ctx, int(texture), out.ctypes.data, n), "readback_material_blocks")
+        return out
+
     def read_alpha_plane(self, count, offset=0):
         """`count` bytes of the alpha plane the masked buckets sample, from byte `offset` (chordvis_debug_read 7)."""
         out = np.zeros(int(count), dtype=np.uint8)
@@ -110,6 +127,22 @@ class VisibilityRenderer:
         for i, m in enumerate(settings):
             arr[i] = m if isinstance(m, L.TextureMips) else L.TextureMips(*m)
         self._check(L.lib.chordvis_set_texture_mips(self._ctx, arr if settings else None, len(settings)), "set_texture_mips")
+
+    def set_texture_compress(self, formats):
+        """Block compression on the GPU by LATER upload_material_textures calls under lib.TEXSTORE_BLOCKS:
+        entry i is the target of texture id i, 0 (none) or records.TEXFMT_BC1_RGB / BC3 / BC4 / BC5; None or an empty list: none
+        (the default).  An RGBA8 texture with a target is encoded whole, made levels included, and keeps no texel; a block
+        texture in its target format keeps its supplied levels verbatim and gets its made levels encoded.  Per context; kept
+        across uploads; ignored in mode EXPANDED and by upload_scene."""
+        formats = [int(f) for f in (formats or ())]
+        arr = (C.c_uint32 * max(1, len(formats)))(*formats)
+        self._check(L.lib.chordvis_set_texture_compress(self._ctx, arr if formats else None, len(formats)), "set_texture_compress")
+
+    def texture_compress(self, texture):
+        """The target format set for a texture id; 0 where nothing is set."""
+        f = C.c_uint32(0)
+        self._check(L.lib.chordvis_texture_compress(self._ctx, int(texture), C.byref(f)), "texture_compress")
+        return f.value
 
     def texture_mips(self, texture):
         """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""

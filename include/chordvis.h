@@ -666,7 +666,8 @@ uint32_t chordvis_material_anisotropy(const ChordCtx* ctx);   /* the last accept
  *                                          pinned decode of DESIGN.md 2 item 9(h)) and produces exactly the images of mode EXPANDED;
  *                                          it takes kernels of its own for that only while the uploaded store holds such a chain.
  *                                          Everything else -- RGBA8 textures, block-compressed textures that get made levels (expanded
- *                                          whole first) -- is stored as in mode EXPANDED, and both kinds may sit in one upload.
+ *                                          whole first) -- is stored as in mode EXPANDED, and both kinds may sit in one upload;
+ *                                          chordvis_set_texture_compress (below) turns such textures into blocks too.
  * Any other value: CHORDVIS_E_INVALID, the setting unchanged, chordvis_last_error names the allowed values.  Per context; kept across
  * chordvis_upload_scene and chordvis_upload_material_textures; read by chordvis_upload_material_textures alone: a store that is
  * already uploaded stays as it is, and chordvis_upload_scene (the alpha its masked buckets test) never keeps blocks, so frames are
@@ -683,6 +684,41 @@ uint32_t chordvis_material_texture_store(const ChordCtx* ctx);   /* the last acc
  * chains kept as blocks of chordvis_texture_chain_bytes rounded up to 16.  Either pointer may be NULL.  CHORDVIS_E_INVALID when no
  * material textures are uploaded. */
 int chordvis_material_texture_memory(ChordCtx* ctx, uint64_t* texelBytes, uint64_t* blockBytes);
+/* Opt-in: block compression on the GPU at upload, so that a host that has RGBA8 texels only (a decoded PNG, level 0 and
+ * chordvis_set_texture_mips for the rest) gets the block store of CHORD_TEXSTORE_BLOCKS too.  Entry i is the target format of
+ * texture id i of the descriptors given to LATER chordvis_upload_material_textures calls: 0 (none: the default) or
+ * CHORD_TEXFMT_BC1_RGB / BC3 / BC4 / BC5; textures at or beyond `count` have none.  The array is copied and held per context, across
+ * both uploads (as the mips setting is).  NULL or count 0: no texture has a target.  Any other value: CHORDVIS_E_INVALID, the
+ * setting unchanged, chordvis_last_error names the allowed values.
+ * Read by chordvis_upload_material_textures alone, and only under CHORD_TEXSTORE_BLOCKS: in mode EXPANDED and in
+ * chordvis_upload_scene it is ignored, and with no target every launch and every stored byte is what it is without this call.
+ * Under CHORD_TEXSTORE_BLOCKS, a texture a material slot names that has a target:
+ *   RGBA8 source          its supplied levels are copied to a staging buffer on the device, the levels chordvis_set_texture_mips
+ *                         asks for are made there, then ONE launch on the context's stream encodes all L levels of every such
+ *                         texture into the block store, in the layout of ChordTexture (level l: ceil(w / 4) x ceil(h / 4) blocks,
+ *                         levels back to back, the chain 16-byte aligned); the staging buffer is freed after the synchronise.  None
+ *                         of its texels stay resident: chordvis_material_texture_memory counts it in blockBytes only, and the 4 G
+ *                         texel cap counts only what stays resident (the staging buffer has a 4 G texel cap of its own).  While the call
+ *                         runs the staging buffer holds 4 bytes per texel of every texture being encoded, beside the block
+ *                         store: that is the call's peak, not what it leaves.
+ *   source in the target  format, with made levels (L > mipCount): the supplied levels keep their bytes verbatim -- they are never
+ *                         re-encoded --, the made levels are encoded from the texels the mip generation made of the decoded chain.
+ *                         (With every level supplied the chain is kept as it is, as without this call.)
+ *   source in another     block format: CHORDVIS_E_INVALID, nothing kept.
+ * Downstream nothing changes: chordvis_resolve_material samples the chain from its blocks, chordvis_readback_material_texture
+ * expands a level through the upload decoder, the block store's 2^32-unit cap applies.
+ * The encoder is pinned: the reference importer's (stb_dxt at HIGHQUAL), byte for byte, floats uncontracted.
+ * Texel (x, y) of the block at block column bx, row by is the level's texel ((4 bx + x) mod w, (4 by + y) mod h): for sizes that are
+ * multiples of 4 and for sizes below 4 the blocks are the reference importer's; for other sizes the reference drops the partial
+ * blocks, this library keeps them, with that fill. */
+int chordvis_set_texture_compress(ChordCtx* ctx, const uint32_t* perTextureFormat, uint32_t count);
+/* What is set for one texture id; 0 at or beyond the count of the last accepted call. */
+int chordvis_texture_compress(const ChordCtx* ctx, uint32_t textureId, uint32_t* format);
+/* The whole chain of a texture kept as blocks, in the layout of ChordTexture (`bytes` = chordvis_texture_chain_bytes of its format,
+ * size and level count), so that a host can cache it and supply it compressed next time; synchronises.  A chain that arrived
+ * compressed comes back as the bytes supplied.  CHORDVIS_E_INVALID when no material textures are uploaded, when the texture is not
+ * kept as blocks (no material names it, or it is stored as texels), or when `bytes` differs from the chain's size. */
+int chordvis_readback_material_blocks(ChordCtx* ctx, uint32_t textureId, uint8_t* host, uint64_t bytes);
 /* The two constant tables of the material resolve as the library holds them (host call, no context): the sRGB8 -> linear decode
  * (256 floats) and sRGB_2_AP1 (9 floats, row-major).  Either may be NULL. */
 int chordvis_material_constants(float srgbToLinear[256], float srgbToAp1[9]);
