@@ -41,6 +41,7 @@
 #include "device_layer.h"
 #include "device_math.h"
 #include "texel_wrap.h"
+#include "span_bounds.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2477,6 +2478,13 @@ struct UnitParams {           // one batch entry, as the row loop wants it
 static_assert(TB == 512, "tile_order_part rounds a pass's slice length to batches of 512");
 #define UNIT_CAP 4096           // units per round of a batch
 
+// steps k0 .. k1 of a row loop that contain every covered step (span_bounds.h), with the device's reciprocal
+__device__ __forceinline__ void row_span(float e0, float e1, float e2, float t0, float t1, float t2, int32_t n, int32_t& k0, int32_t& k1)
+{
+    const float e[3] = {e0, e1, e2}, t[3] = {t0, t1, t2};
+    span_bounds(e, t, n, [](float x) { return __builtin_amdgcn_rcpf(x); }, k0, k1);
+}
+
 template <typename E_t>
 __device__ __forceinline__ void scan_row(unsigned long long* __restrict__ tileRow, const UnitParams& u, int32_t ox, int32_t py,
                                          int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
@@ -2495,21 +2503,11 @@ __device__ __forceinline__ void scan_row(unsigned long long* __restrict__ tileRo
     E_t E2 = s * (dx2 * (cy - (E_t)u.Y[0]) - dy2 * (cx - (E_t)u.X[0])) + bias2;
     const E_t st0 = a0 * (E_t)256, st1 = a1 * (E_t)256, st2 = a2 * (E_t)256;
     // Span of the row in steps k from lx0: E_i + k * st_i >= 0 for all i.  The crossings are estimated in fp32
-    // (v_rcp_f32; error far below the +-1 step of slack taken on both sides) and only bound the
-    // loop; coverage itself is decided by the exact edge values inside it, so the loop has no data-dependent
+    // (v_rcp_f32; span_bounds.h has the error bound and the 2^-6 px it is cleared by) and only bound
+    // the loop; coverage itself is decided by the exact edge values inside it, so the loop has no data-dependent
     // branch: a pixel outside merges the value 0, which ds_max ignores.
-    float klo = 0.0f, khi = (float)(lx1 - lx0);
-    {
-        const float e[3] = {(float)E0, (float)E1, (float)E2}, t[3] = {(float)st0, (float)st1, (float)st2};
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float q = fminf(fmaxf(-e[i] * __builtin_amdgcn_rcpf(t[i]), -4.0f), 4096.0f);   // NaN (0 * inf) -> -4
-            if (t[i] > 0.0f) klo = fmaxf(klo, floorf(q) - 1.0f);
-            else if (t[i] < 0.0f) khi = fminf(khi, floorf(q) + 1.0f);
-            else if (e[i] < 0.0f) khi = -1.0f;                                                  // constant and outside
-        }
-    }
-    const int32_t k0 = (int32_t)klo, k1 = (int32_t)khi;
+    int32_t k0, k1;
+    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
     E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
     unsigned long long* px = tileRow + lx0 + k0;
     const unsigned long long payload = noPixels ? 0ull : (unsigned long long)u.payload;
@@ -2593,18 +2591,8 @@ __device__ __forceinline__ int32_t scan_span(unsigned long long* __restrict__ ti
                                           int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ = false)
 {
     // Span of the row in steps k from lx0 (see scan_row): fp32 estimates only BOUND the loop, coverage is exact inside.
-    float klo = 0.0f, khi = (float)(lx1 - lx0);
-    {
-        const float e[3] = {(float)E0, (float)E1, (float)E2}, t[3] = {(float)st0, (float)st1, (float)st2};
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float q = fminf(fmaxf(-e[i] * __builtin_amdgcn_rcpf(t[i]), -4.0f), 4096.0f);   // NaN (0 * inf) -> -4
-            if (t[i] > 0.0f) klo = fmaxf(klo, floorf(q) - 1.0f);
-            else if (t[i] < 0.0f) khi = fminf(khi, floorf(q) + 1.0f);
-            else if (e[i] < 0.0f) khi = -1.0f;                                                  // constant and outside
-        }
-    }
-    const int32_t k0 = (int32_t)klo, k1 = (int32_t)khi;
+    int32_t k0, k1;
+    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
     E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
     unsigned long long* px = tileRow + lx0 + k0;
     const unsigned long long payload = noPixels ? 0ull : (unsigned long long)payloadIn;
@@ -2627,23 +2615,13 @@ __device__ __forceinline__ int32_t scan_span_i32(unsigned long long* __restrict_
                                               float d0, float e1, float e2, float invA, uint32_t payloadIn,
                                               int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
 {
-    float klo = 0.0f, khi = (float)(lx1 - lx0);
-    {
-        const float e[3] = {(float)E0, (float)E1, (float)E2}, t[3] = {(float)st0, (float)st1, (float)st2};
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float q = fminf(fmaxf(-e[i] * __builtin_amdgcn_rcpf(t[i]), -4.0f), 4096.0f);
-            if (t[i] > 0.0f) klo = fmaxf(klo, floorf(q) - 1.0f);
-            else if (t[i] < 0.0f) khi = fminf(khi, floorf(q) + 1.0f);
-            else if (e[i] < 0.0f) khi = -1.0f;
-        }
-    }
-    const int32_t k0 = (int32_t)klo, k1 = (int32_t)khi;
-    E0 += __mul24(k0, st0); E1 += __mul24(k0, st1); E2 += __mul24(k0, st2);     // |st| <= 2^22, 0 <= k0 < 2^12: 24-bit operands
-    // (Round 3: trimming the ~3 slack pixels of the fp32 bounds with exact edge tests before the loop -- 1.5 of a row's 5.6
-    // two-pixel trips -- and predicating the merges instead of merging 0 were both measured: tile kernel 107 -> 109 / 108 us
-    // on config 3, 197 -> 200 / 197 on config 4.  The LDS atomic pipe is ~55 % busy in pass 0 but it is not what the kernel
-    // waits for; profiles/r03_tile_kernel_experiments.txt.)
+    int32_t k0, k1;
+    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
+    E0 += __mul24(k0, st0); E1 += __mul24(k0, st1); E2 += __mul24(k0, st2);     // |st| <= 2^22, 0 <= k0 <= 2^12: 24-bit operands
+    // (Round 3: trimming the ~3 slack pixels that the bounds then had (floor(q) -+ 1) with exact edge tests before the loop --
+    // 1.5 of a row's 5.6 two-pixel trips -- and predicating the merges instead of merging 0 were both measured: tile kernel
+    // 107 -> 109 / 108 us on config 3, 197 -> 200 / 197 on config 4; profiles/r03_tile_kernel_experiments.txt.  The bounds of
+    // span_bounds.h take most of that slack for no instruction; profiles/r10_span_bounds.txt.)
     int32_t U1 = E1 - bias1, U2 = E2 - bias2;                    // the unbiased values the canonical depth uses
     unsigned long long* px = tileRow + lx0 + k0;
     const unsigned long long payload = noPixels ? 0ull : (unsigned long long)payloadIn;
@@ -2713,8 +2691,8 @@ __device__ __forceinline__ uint32_t entry_store(EntrySoA& en, uint32_t t, const 
 // A pixel row of a masked triangle: exact int64 edges, canonical depth, and per covered pixel the perspective-correct
 // texture coordinates, one alpha fetch and the clip() of mesh_raster.hlsl:198-204.
 // E_t: int32_t for triangles whose vertices are at most 64 px apart (|E| < 2^31, as in scan_span_i32; (float)E is then the
-// canonical (float)(double)E), int64_t for the rest.  The span of the row is bounded first (fp32 estimates, one pixel of slack:
-// scan_span), so the loop runs over the covered pixels, not over the bbox row.
+// canonical (float)(double)E), int64_t for the rest.  The span of the row is bounded first (row_span, the same bounds as
+// scan_span's), so the loop runs over the covered pixels, not over the bbox row; a step outside the triangle skips the taps.
 // (A unit of a masked triangle is a GROUP of up to MASKED_ROWS pixel rows, not one: what a unit pays before its first pixel --
 // the triangle's extension record, its material, the texture level, the edge constants: three dependent memory round trips --
 // is then paid once per small triangle instead of once per row.)
@@ -2743,18 +2721,8 @@ __device__ __forceinline__ void masked_rows(const RasterParams& p, unsigned long
     for (int32_t r = 0; r < nrows; r++, R0 += sy0, R1 += sy1, R2 += sy2) {
     E_t E0 = R0, E1 = R1, E2 = R2;
     unsigned long long* __restrict__ tileRow = tileRow0 + r * TPITCH;
-    float klo = 0.0f, khi = (float)(lx1 - lx0);
-    {
-        const float e[3] = {(float)E0, (float)E1, (float)E2}, t[3] = {(float)st0, (float)st1, (float)st2};
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float q = fminf(fmaxf(-e[i] * __builtin_amdgcn_rcpf(t[i]), -4.0f), 4096.0f);   // NaN (0 * inf) -> -4
-            if (t[i] > 0.0f) klo = fmaxf(klo, floorf(q) - 1.0f);
-            else if (t[i] < 0.0f) khi = fminf(khi, floorf(q) + 1.0f);
-            else if (e[i] < 0.0f) khi = -1.0f;
-        }
-    }
-    const int32_t k0 = (int32_t)klo, k1 = (int32_t)khi;
+    int32_t k0, k1;
+    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
     E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
     // the packed word of the pixel with these (biased) edge values, 0 when it is outside or its alpha fails the cut-off.  No branch:
     // a pixel outside the triangle evaluates its texture coordinates anyway (whatever they are, texel_floor / wrap_index give an
