@@ -68,18 +68,20 @@ struct TexDecodeJob {
     uint64_t stagingBytes = 0;
     uint32_t blocks = 0;
 
-    // dst: where level 0 goes (a texel index of dMatTexels / a byte index of dTexAlpha); the levels follow as an RGBA8 chain's do
-    void add(const ChordTexture& tx, uint32_t dst)
+    // dst: where level `first` goes (a texel index of dMatTexels / a byte index of dTexAlpha); the levels follow as an RGBA8 chain's
+    // do.  Levels below `first` (chordvis_set_texture_first_level) are neither staged nor decoded
+    void add(const ChordTexture& tx, uint32_t dst, uint32_t first = 0u)
     {
         const uint32_t bb = tex_block_bytes(tx.format);
         const uint64_t offset = (stagingBytes + 15ull) & ~15ull;
-        uint64_t bytes = 0;
+        uint64_t bytes = 0, skipped = 0;
         for (uint32_t l = 0; l < tx.mipCount; l++) {
             const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l), bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
+            if (l < first) { skipped += (uint64_t)bw * bh * bb; continue; }
             recs.push_back(chord::DTexLevelRec{blocks, (uint32_t)((offset + bytes) / 8u), dst, w, h, bw, tx.format, 0u});
             blocks += bw * bh; bytes += (uint64_t)bw * bh * bb; dst += w * h;
         }
-        copies.push_back(Copy{tx.rgba8, offset, bytes});
+        copies.push_back(Copy{tx.rgba8 + skipped, offset, bytes});
         stagingBytes = offset + bytes;
     }
 
@@ -259,17 +261,19 @@ struct TexEncodeJob {
     std::vector<chord::DTexEncRec> recs;
     uint32_t blocks = 0;
 
-    // src: level 0's first texel in the staging buffer; dst: the chain's first unit in dMatBlocks; levels from .. L-1 are encoded
-    void add(uint32_t src, uint32_t dst, uint32_t width, uint32_t height, uint32_t from, uint32_t L, uint32_t format)
+    // src: level 0's first texel in the staging buffer; dst: the stored chain's first unit in dMatBlocks, where level `first` goes
+    // (chordvis_set_texture_first_level: the levels before it take no unit); levels max(from, first) .. L-1 are encoded
+    void add(uint32_t src, uint32_t dst, uint32_t width, uint32_t height, uint32_t from, uint32_t L, uint32_t format, uint32_t first = 0u)
     {
         const uint32_t unitsPerBlock = tex_block_bytes(format) / 8u;
         for (uint32_t l = 0; l < L; l++) {
             const uint32_t w = std::max(1u, width >> l), h = std::max(1u, height >> l), bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
-            if (l >= from) {
+            if (l >= from && l >= first) {
                 recs.push_back(chord::DTexEncRec{blocks, src, dst, w, h, bw, format, 0u});
                 blocks += bw * bh;
             }
-            src += w * h; dst += bw * bh * unitsPerBlock;
+            src += w * h;
+            if (l >= first) dst += bw * bh * unitsPerBlock;
         }
     }
 
@@ -302,7 +306,7 @@ struct TexEncodeJob {
 // what chordvis_upload_material_textures keeps
 void drop_material_textures(ChordCtx* c)
 {
-    dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks);
+    dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback);
     c->matTexelCount = 0; c->matBlockUnits = 0;
     c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
 }
@@ -671,7 +675,7 @@ int chordvis_destroy(ChordCtx* c)
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dTexEncTables);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -1113,6 +1117,11 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
     TexMipJob stageMips;
     TexEncodeJob encode;
     std::vector<uint32_t> texStage(nTex, 0xFFFFFFFFu);
+    // chordvis_set_texture_first_level: the levels before texFirst[t] are not stored.  A texel chain that has levels to make is
+    // finished in the staging buffer too, and its kept levels copied from there (trims)
+    std::vector<uint32_t> texFirst(nTex, 0u);
+    struct TrimCopy { uint32_t src, dst; size_t count; };
+    std::vector<TrimCopy> trims;
     for (uint32_t t = 0; t < nTex; t++) {
         texLevels[t] = s->textures[t].mipCount;
         if (!named[t]) continue;
@@ -1123,37 +1132,57 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a texture a material names has no data, or is larger than 16384 / 15 levels");
         ChordTextureMips ms;
         const uint32_t L = tex_levels(c, t, tx, ms);                       // (>= mipCount; the levels beyond it are made on the device)
+        const uint32_t f = std::min(t < c->texFirstLevel.size() ? c->texFirstLevel[t] : 0u, L - 1u);
+        const uint32_t fw = std::max(1u, tx.width >> f), fh = std::max(1u, tx.height >> f);   // the stored texture: fw x fh, L - f levels
+        texFirst[t] = f;
         const uint32_t target = (c->matTextureStore == CHORD_TEXSTORE_BLOCKS && t < c->texCompress.size()) ? c->texCompress[t] : 0u;
         if (target && tex_block_bytes(tx.format) && tx.format != target)
             return fail(c, CHORDVIS_E_INVALID, "upload_material_textures: a block-compressed texture's format differs from its chordvis_set_texture_compress target (supplied levels are never re-encoded)");
         if (c->matTextureStore == CHORD_TEXSTORE_BLOCKS && tex_block_bytes(tx.format) && L == tx.mipCount) {
             uint64_t bytes = 0;
-            (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &bytes);
+            (void)chordvis_texture_chain_bytes(tx.format, fw, fh, L - f, &bytes);
             const uint64_t units = ((bytes + 15ull) & ~15ull) / 8u;
             if (blockUnits + units >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 2^32 8-byte units of textures kept as blocks");
-            texBase[t] = (uint32_t)blockUnits; texKept[t] = tx.format;
+            texBase[t] = (uint32_t)blockUnits; texKept[t] = tx.format; texLevels[t] = L - f;
             blockUnits += units;
             continue;
         }
         if (target) {
             // an RGBA8 source: every level is encoded; a source in the target format with made levels: those alone
             uint64_t bytes = 0;
-            (void)chordvis_texture_chain_bytes(target, tx.width, tx.height, L, &bytes);
+            (void)chordvis_texture_chain_bytes(target, fw, fh, L - f, &bytes);
             const uint64_t units = ((bytes + 15ull) & ~15ull) / 8u;
             if (blockUnits + units >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 2^32 8-byte units of textures kept as blocks");
             const size_t count = tex_chain_texels(tx.width, tx.height, L);
             if (stageCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels staged for compression in one upload");
-            texBase[t] = (uint32_t)blockUnits; texKept[t] = target; texLevels[t] = L; texStage[t] = (uint32_t)stageCount;
+            texBase[t] = (uint32_t)blockUnits; texKept[t] = target; texLevels[t] = L - f; texStage[t] = (uint32_t)stageCount;
             if (tx.format != CHORD_TEXFMT_RGBA8) stageDecode.add(tx, (uint32_t)stageCount);
             stageMips.add((uint32_t)stageCount, tx.width, tx.height, tx.mipCount, L, ms,
                           (ms.flags & CHORD_TEXMIPS_COVERAGE) && (tx.format == CHORD_TEXFMT_RGBA8 || tx.format == CHORD_TEXFMT_BC3));
-            encode.add((uint32_t)stageCount, (uint32_t)blockUnits, tx.width, tx.height, tx.format == CHORD_TEXFMT_RGBA8 ? 0u : tx.mipCount, L, target);
+            encode.add((uint32_t)stageCount, (uint32_t)blockUnits, tx.width, tx.height, tx.format == CHORD_TEXFMT_RGBA8 ? 0u : tx.mipCount, L, target, f);
             stageCount += count; blockUnits += units;
             continue;
         }
-        const size_t count = tex_chain_texels(tx.width, tx.height, L);
+        const size_t count = tex_chain_texels(fw, fh, L - f);
         if (texelCount + count >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels");
-        texBase[t] = (uint32_t)texelCount; texLevels[t] = L;
+        texBase[t] = (uint32_t)texelCount; texLevels[t] = L - f;
+        if (f && L > tx.mipCount) {
+            // trimmed, with levels to make: the whole chain is finished in the staging buffer, as it would be in the store
+            const size_t whole = tex_chain_texels(tx.width, tx.height, L);
+            if (stageCount + whole >= 0xFFFFFFFFull) return fail(c, CHORDVIS_E_CAPACITY, "upload_material_textures: more than 4 G texels staged in one upload");
+            texStage[t] = (uint32_t)stageCount;
+            if (tx.format != CHORD_TEXFMT_RGBA8) stageDecode.add(tx, (uint32_t)stageCount);
+            stageMips.add((uint32_t)stageCount, tx.width, tx.height, tx.mipCount, L, ms,
+                          (ms.flags & CHORD_TEXMIPS_COVERAGE) && (tx.format == CHORD_TEXFMT_RGBA8 || tx.format == CHORD_TEXFMT_BC3));
+            trims.push_back(TrimCopy{(uint32_t)(stageCount + tex_chain_texels(tx.width, tx.height, f)), (uint32_t)texelCount, count});
+            stageCount += whole; texelCount += count;
+            continue;
+        }
+        if (f) {                                                           // trimmed, every level supplied: the kept ones alone arrive
+            if (tx.format != CHORD_TEXFMT_RGBA8) decode.add(tx, (uint32_t)texelCount, f);
+            texelCount += count;
+            continue;
+        }
         if (tx.format != CHORD_TEXFMT_RGBA8) decode.add(tx, (uint32_t)texelCount);
         // (BC1_RGB, BC4, BC5: alpha 255 at every level, which the rescale would leave as it is)
         mips.add((uint32_t)texelCount, tx.width, tx.height, tx.mipCount, L, ms,
@@ -1192,10 +1221,12 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
             const ChordTexture& tx = s->textures[tex[k]];
             S.mips = texLevels[tex[k]];
             S.format = texKept[tex[k]];
+            S.texture = tex[k];
+            const uint32_t first = texFirst[tex[k]];
             const uint32_t unitsPerBlock = tex_block_bytes(S.format) / 8u;  // (0: a level is w * h texels)
             uint32_t off = texBase[tex[k]];
             for (uint32_t l = 0; l < S.mips; l++) {
-                const uint32_t w = std::max(1u, tx.width >> l), h = std::max(1u, tx.height >> l);
+                const uint32_t w = std::max(1u, tx.width >> (first + l)), h = std::max(1u, tx.height >> (first + l));
                 chord::DMatLevel& L = S.levels[l];
                 L.base = off; L.dims = (w - 1u) | (h - 1u) << 16;
                 wrap_consts(w, S.wrapS, L.magicS, L.biasS);
@@ -1213,8 +1244,10 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t t = 0; t < nTex; t++) {
             const ChordTexture& tx = s->textures[t];
             if (texBase[t] == 0xFFFFFFFFu || tx.format != CHORD_TEXFMT_RGBA8 || texKept[t]) continue;     // (texKept: encoded below, from the staging buffer)
-            const size_t count = tex_chain_texels(tx.width, tx.height, tx.mipCount);
-            hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8, count * 4, hipMemcpyHostToDevice);
+            if (texStage[t] != 0xFFFFFFFFu) continue;                      // (trimmed, with made levels: copied below, from the staging buffer)
+            const size_t skip = tex_chain_texels(tx.width, tx.height, texFirst[t]);   // (0 without chordvis_set_texture_first_level)
+            const size_t count = tex_chain_texels(tx.width, tx.height, tx.mipCount) - skip;
+            hipError_t e = hipMemcpy(c->dMatTexels + texBase[t], tx.rgba8 + skip * 4, count * 4, hipMemcpyHostToDevice);
             if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
         }
         if ((rc = decode.run(c, "upload_material_textures: texture decode", c->dMatTexels, nullptr, false))) { drop_material_textures(c); return rc; }
@@ -1225,10 +1258,15 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t t = 0; t < nTex; t++) {
             if (!texKept[t]) continue;
             const ChordTexture& tx = s->textures[t];
-            uint64_t bytes = 0, supplied = 0;                              // of the stored chain / of the levels that arrive as blocks
-            (void)chordvis_texture_chain_bytes(texKept[t], tx.width, tx.height, texLevels[t], &bytes);
-            if (tx.format != CHORD_TEXFMT_RGBA8) (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &supplied);
-            hipError_t e = supplied ? hipMemcpy(c->dMatBlocks + texBase[t], tx.rgba8, supplied, hipMemcpyHostToDevice) : hipSuccess;
+            uint64_t bytes = 0, supplied = 0, skip = 0;                    // of the stored chain / of the levels that arrive as blocks / of those not stored
+            const uint32_t f = texFirst[t];
+            (void)chordvis_texture_chain_bytes(texKept[t], std::max(1u, tx.width >> f), std::max(1u, tx.height >> f), texLevels[t], &bytes);
+            if (tx.format != CHORD_TEXFMT_RGBA8) {
+                (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, tx.mipCount, &supplied);
+                if (f) (void)chordvis_texture_chain_bytes(tx.format, tx.width, tx.height, std::min(f, tx.mipCount), &skip);
+                supplied -= skip;
+            }
+            hipError_t e = supplied ? hipMemcpy(c->dMatBlocks + texBase[t], tx.rgba8 + skip, supplied, hipMemcpyHostToDevice) : hipSuccess;
             if (e == hipSuccess && (bytes & 15ull)) e = hipMemset((uint8_t*)(c->dMatBlocks + texBase[t]) + bytes, 0, 16u - (bytes & 15ull));   // (the chain's padding)
             if (e != hipSuccess) { drop_material_textures(c); return fail(c, CHORDVIS_E_HIP, "upload_material_textures: hipMemcpy", e); }
         }
@@ -1247,12 +1285,17 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         if (!rc) rc = stageDecode.run(c, "upload_material_textures: texture decode", dStage, nullptr, false);
         if (!rc) rc = stageMips.run(c, "upload_material_textures: texture mips", dStage, nullptr, false);
         if (!rc) rc = encode.run(c, "upload_material_textures: texture encode", dStage, c->dMatBlocks);
+        for (size_t i = 0; i < trims.size() && !rc; i++) {
+            e = hipMemcpy(c->dMatTexels + trims[i].dst, dStage + trims[i].src, trims[i].count * 4u, hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) rc = fail(c, CHORDVIS_E_HIP, "upload_material_textures: copy of the kept levels", e);
+        }
         if (dStage) (void)hipFree(dStage);
         if (rc) { drop_material_textures(c); return rc; }
     }
     c->matTex.resize(nTex);
     for (uint32_t t = 0; t < nTex; t++)
-        c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], s->textures[t].width, s->textures[t].height, texLevels[t], texKept[t]};
+        c->matTex[t] = ChordCtx::MatTexInfo{texBase[t], std::max(1u, s->textures[t].width >> texFirst[t]), std::max(1u, s->textures[t].height >> texFirst[t]),
+                                            texLevels[t], texKept[t], texFirst[t]};
     c->matTexelCount = texelCount; c->matBlockUnits = blockUnits;
     c->matTexturesLoaded = true; c->matAnyNormalTexture = anyNormal;
     return CHORDVIS_OK;
@@ -1345,6 +1388,32 @@ int chordvis_readback_material_texture(ChordCtx* c, uint32_t textureId, uint32_t
     size_t off = t.base;
     for (uint32_t l = 0; l < level; l++) off += (size_t)std::max(1u, t.width >> l) * std::max(1u, t.height >> l);
     CHORD_HIP(c, hipMemcpy(hostRgba8, c->dMatTexels + off, count * 4, hipMemcpyDeviceToHost));
+    return CHORDVIS_OK;
+}
+
+int chordvis_set_texture_first_level(ChordCtx* c, const uint32_t* perTextureFirst, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!perTextureFirst || !count) c->texFirstLevel.clear();
+    else c->texFirstLevel.assign(perTextureFirst, perTextureFirst + count);
+    return CHORDVIS_OK;
+}
+
+int chordvis_texture_first_level(const ChordCtx* c, uint32_t textureId, uint32_t* first)
+{
+    if (!c || !first) return CHORDVIS_E_INVALID;
+    *first = textureId < c->texFirstLevel.size() ? c->texFirstLevel[textureId] : 0u;
+    return CHORDVIS_OK;
+}
+
+int chordvis_material_texture_levels(ChordCtx* c, uint32_t textureId, uint32_t* firstLevel, uint32_t* levelCount)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "material_texture_levels: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (textureId >= c->matTex.size() || c->matTex[textureId].base == 0xFFFFFFFFu)
+        return fail(c, CHORDVIS_E_INVALID, "material_texture_levels: no material of the scene names this texture");
+    if (firstLevel) *firstLevel = c->matTex[textureId].first;
+    if (levelCount) *levelCount = c->matTex[textureId].mipCount;
     return CHORDVIS_OK;
 }
 
@@ -2091,6 +2160,55 @@ int chordvis_resolve_material(ChordCtx* c, ChordCountAndCmd drawed, const ChordR
     if ((rc = resolve_source(c, drawed, &vis))) return rc;
     chord::launch_resolve_material(c, vis, drawed.cmds, drawed.count, d, tt, chord::MaterialLaunch{ss, mm});
     CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_material_feedback_reset(ChordCtx* c)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "material_feedback_reset: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    (void)hipSetDevice(c->device);
+    const size_t words = c->matTex.size() * CHORD_FEEDBACK_LEVELS;
+    int rc;
+    if (!c->dMatFeedback && (rc = dalloc(c, &c->dMatFeedback, words))) return rc;
+    CHORD_HIP(c, hipMemsetAsync(c->dMatFeedback, 0, std::max<size_t>(words, 1u) * 4u, c->stream));
+    return CHORDVIS_OK;
+}
+
+// chordvis_resolve_material's preconditions when asked for a material target other than pixelNormal, then the pass's own
+int chordvis_material_feedback(ChordCtx* c, ChordCountAndCmd drawed, const ChordFeedbackDesc* desc)
+{
+    int rc = resolve_checks(c, "material_feedback", drawed, true, false, ChordResolveDesc{});
+    if (rc) return rc;
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "material_feedback: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (!c->dMatFeedback) return fail(c, CHORDVIS_E_INVALID, "material_feedback: no chordvis_material_feedback_reset since the last chordvis_upload_material_textures");
+    if (!desc) return fail(c, CHORDVIS_E_INVALID, "material_feedback: null ChordFeedbackDesc");
+    if (desc->slotMask == 0u || desc->slotMask > 15u)
+        return fail(c, CHORDVIS_E_INVALID, "material_feedback: slotMask is 1..15 (CHORD_FEEDBACK_BASECOLOR 1 | EMISSIVE 2 | NORMAL 4 | METALROUGH 8)");
+    if (desc->stride != 1u && desc->stride != 2u && desc->stride != 4u && desc->stride != 8u)
+        return fail(c, CHORDVIS_E_INVALID, "material_feedback: stride is 1, 2, 4 or 8");
+    if (desc->offset[0] >= desc->stride || desc->offset[1] >= desc->stride)
+        return fail(c, CHORDVIS_E_INVALID, "material_feedback: each offset is 0 .. stride - 1");
+    const unsigned long long* vis = nullptr;
+    if ((rc = resolve_source(c, drawed, &vis))) return rc;
+    chord::launch_material_feedback(c, vis, drawed.cmds, drawed.count, *desc, c->dMatFeedback, (uint32_t)c->matTex.size());
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_material_feedback(ChordCtx* c, uint32_t* hostTaps, uint32_t textureCount)
+{
+    if (!c || !hostTaps) return fail(c, CHORDVIS_E_INVALID, "readback_material_feedback: null argument");
+    if (!c->matTexturesLoaded) return fail(c, CHORDVIS_E_INVALID, "readback_material_feedback: no chordvis_upload_material_textures since the last chordvis_upload_scene");
+    if (!c->dMatFeedback) return fail(c, CHORDVIS_E_INVALID, "readback_material_feedback: no chordvis_material_feedback_reset since the last chordvis_upload_material_textures");
+    if (textureCount != c->matTex.size()) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "readback_material_feedback: textureCount is the uploaded descriptor's, %u", (unsigned)c->matTex.size());
+        return fail(c, CHORDVIS_E_INVALID, buf);
+    }
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    if (textureCount) CHORD_HIP(c, hipMemcpy(hostTaps, c->dMatFeedback, (size_t)textureCount * CHORD_FEEDBACK_LEVELS * 4u, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }
 

@@ -112,7 +112,8 @@ struct DMatSlot {              // 32 + 15 x 24 B
     uint32_t filter;           // CHORD_MATSLOT_* bits of the sampler's magFilter / minFilter
     uint32_t wrapS, wrapT;
     uint32_t format;           // 0: the levels are texels of dMatTexels; CHORD_TEXFMT_BC1_RGB .. BC5: blocks of dMatBlocks
-    uint32_t pad[3];
+    uint32_t texture;          // the descriptor's texture id (mips != 0): the row of the feedback buffer; material_feedback_kernel alone reads it
+    uint32_t pad[2];
     DMatLevel levels[CHORD_MAX_TEX_LEVELS];
 };
 struct DMatRecord {            // 64 + 4 x 392 B
@@ -433,8 +434,11 @@ struct ChordCtx {
     uint32_t matTextureStore = CHORD_TEXSTORE_EXPANDED;   // chordvis_set_material_texture_store; kept across uploads, read by chordvis_upload_material_textures
     bool matTexturesLoaded = false;
     // base: first texel in dMatTexels (format 0) or first unit in dMatBlocks (format CHORD_TEXFMT_BC*: kept as blocks), 0xFFFFFFFF: no material names it
-    struct MatTexInfo { uint32_t base, width, height, mipCount, format; };
+    // width, height, mipCount: of the STORED chain, whose level 0 is level `first` of the finished one (chordvis_set_texture_first_level)
+    struct MatTexInfo { uint32_t base, width, height, mipCount, format, first; };
     std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
+    std::vector<uint32_t> texFirstLevel;      // chordvis_set_texture_first_level: per texture id; kept across uploads, read by chordvis_upload_material_textures alone
+    uint32_t* dMatFeedback = nullptr;         // chordvis_material_feedback: CHORD_FEEDBACK_LEVELS words per texture of matTex; made by the first reset after an upload
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     std::vector<uint32_t> texCompress;        // chordvis_set_texture_compress: per texture id, 0 or a CHORD_TEXFMT_BC* target; kept across uploads, read by chordvis_upload_material_textures under CHORD_TEXSTORE_BLOCKS
@@ -653,6 +657,9 @@ void launch_resolve_material(ChordCtx* c, const unsigned long long* vis, const C
                              const ChordResolveDesc& desc, const ChordResolveTargets& targets, const MaterialLaunch& m);
 void launch_resolve_gbuffer(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                             const ChordResolveDesc& desc, const ChordGBufferTargets& targets);
+// kernels_resolve.hip: adds the finest tap level of every lattice pixel and slot of `desc` to taps[texture * CHORD_FEEDBACK_LEVELS + level].  One launch.
+void launch_material_feedback(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                              const ChordFeedbackDesc& desc, uint32_t* taps, uint32_t textureCount);
 void launch_pack_gbuffer(ChordCtx* c, uint32_t width, uint32_t height, const ChordGBufferSources& sources, const ChordGBufferTargets& targets);
 // kernels_texture.hip: expands the blocks of `count` levels (recs[count] closes the table) from `staging` into RGBA8 words of
 // `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.

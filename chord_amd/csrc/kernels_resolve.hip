@@ -39,6 +39,11 @@
 //                               call that asks for vertexNormal / motionVector alone still launches one of them (the material
 //                               loop is skipped at run time): there is no packed <0> or <1>.
 
+//   material_feedback_kernel    chordvis_material_feedback: the same wave block over a LATTICE of pixels, leader loop, set-up and material
+//                               loop as above, cut down to what the uv gradients need; instead of sampling, the lanes of a (material,
+//                               slot) turn are balloted per finest level and one lane adds the popcount to a workgroup table in LDS,
+//                               flushed to the per-(texture, level) counts with one global atomic per entry.
+//
 // The per-vertex products are the same bits whichever lane forms them (one arithmetic, no reassociation): a pixel's result
 // does not depend on its neighbours.  Every + - * / is float32 in source order (-ffp-contract=off, IEEE divide).
 
@@ -689,6 +694,208 @@ __global__ __launch_bounds__(256) void resolve_attributes_kernel(const KernelArg
 }
 
 
+// ---- material feedback (chordvis_material_feedback) ------------------------------------------------------------
+// Which level of which texture the pinned sampler's finest tap lands on, counted per (texture, level) over a lattice of pixels.
+// The level of sample_slot / sample_slot_aniso without their fetches: the same footprint arithmetic statement by statement, the same
+// integer rule (a twin: the sampling kernels stay as they are).  kmax 0: sample_slot's l0; kmax = log2 N >= 1: sample_slot_aniso's.
+struct FeedbackArgs {
+    const unsigned long long* vis;
+    const ChordDrawCmd* cmds;
+    const uint32_t* cmdCount;
+    const ChordObject* objects;
+    const DObjStatic* objStatic;
+    const DMeshlet* meshlets;
+    const uint32_t* meshletData;
+    const float* positions;
+    const float* texcoords;            // null: (0, 0)
+    const DView* view;
+    const DMatRecord* records;
+    uint32_t* taps;                    // [textureCount][CHORD_FEEDBACK_LEVELS]
+    uint32_t W, H, blocksX, waveBlocks;   // the image; wave blocks (16 x 4 lattice pixels) per lattice row, and in all
+    uint32_t blocksPerGroup;           // the strip of wave blocks a workgroup walks
+    uint32_t objectCount, meshletCount;
+    uint32_t stride, offX, offY, slotMask, kmax, tapWords;
+    uint32_t tableMask;                // entries of the workgroup's table in use - 1: FEEDBACK_TABLE - 1 (chordvis_set_debug 4194304: 1)
+};
+#define FEEDBACK_TABLE 512u            // entries of a workgroup's table of (texture * 16 + level) -> count
+#define FEEDBACK_PROBES 32u            // slots a key looks at before it gives up on the table
+#define FEEDBACK_EMPTY 0xFFFFFFFFu
+
+__device__ __forceinline__ uint32_t feedback_level(const DMatSlot& S, float4 g, uint32_t kmax)
+{
+    const uint32_t d0 = S.levels[0].dims;
+    const float fW = (float)((d0 & 0xFFFFu) + 1u), fH = (float)((d0 >> 16) + 1u);
+    int32_t lodq, lmaj;
+    if (kmax == 0u) lodq = lmaj = footprint_lodq(g, fW, fH);
+    else {
+        const float ax = g.x * fW, ay = g.y * fH, bx = g.z * fW, by = g.w * fH;
+        const float ra = ax * ax + ay * ay, rb = bx * bx + by * by;
+        const float rmaj2 = fmaxf(ra, rb), rmin2 = fminf(ra, rb);
+        int32_t k = 0;
+        lmaj = 0;
+        if (ra < __builtin_inff() && rb < __builtin_inff() && rmaj2 > 0.0f) {
+            lmaj = ((int32_t)(__float_as_uint(rmaj2) >> 15) - (127 << 8)) >> 1;
+            if (lmaj > 0) {
+                int32_t spread = (int32_t)kmax;
+                if (rmin2 > 0.0f) spread = (max(lmaj - (((int32_t)(__float_as_uint(rmin2) >> 15) - (127 << 8)) >> 1), 0) + 255) >> 8;
+                k = min(min((int32_t)kmax, spread), (lmaj + 255) >> 8);
+            }
+        }
+        lodq = max(lmaj - (k << 8), 0);
+    }
+    const uint32_t filter = S.filter, last = S.mips - 1u;
+    uint32_t l0 = 0u;
+    if (lmaj > 0) {
+        if (filter & CHORD_MATSLOT_MIP_NEAREST) l0 = min((uint32_t)(lodq + 128) >> 8, last);
+        else if (filter & CHORD_MATSLOT_MIP_LINEAR) l0 = min((uint32_t)lodq >> 8, last);
+    }
+    return l0;
+}
+
+// count more taps of `key`: the workgroup's table, open addressing from a multiplicative hash; a key that finds neither itself nor
+// a free slot in FEEDBACK_PROBES steps goes to global memory
+__device__ __forceinline__ void feedback_add(uint32_t* sKeys, uint32_t* sVals, uint32_t* __restrict__ taps, uint32_t tableMask, uint32_t key,
+                                             uint32_t count)
+{
+    uint32_t h = ((key * 0x9E3779B1u) >> 23) & tableMask;               // 9 bits
+    const uint32_t probes = min(FEEDBACK_PROBES, tableMask + 1u);
+    for (uint32_t p = 0; p < probes; p++) {
+        const uint32_t was = atomicCAS(&sKeys[h], FEEDBACK_EMPTY, key);
+        if (was == FEEDBACK_EMPTY || was == key) { atomicAdd(&sVals[h], count); return; }
+        h = (h + 1u) & tableMask;
+    }
+    atomicAdd(&taps[key], count);
+}
+
+// A wave per 16 x 4 LATTICE pixels, x = (bx * 16 + (lane & 15)) * stride + offX and y likewise: resolve_attributes_kernel's leader
+// loop, the part of its per-triangle set-up and per-pixel arithmetic the uv gradients need (the same statements), and its
+// wave-uniform material loop with the level rule in place of the sampler.  No texel is fetched, no image stored.  Inside a
+// (material, slot) turn the lanes are balloted per distinct level and one lane adds the popcount to the workgroup's LDS table; a
+// workgroup walks a strip of wave blocks and at its end adds every entry it filled to `taps` with one global atomic.
+__global__ __launch_bounds__(256) void material_feedback_kernel(const FeedbackArgs a)
+{
+    static_assert(FEEDBACK_TABLE == 512u, "feedback_add's hash keeps 9 bits");
+    __shared__ uint32_t sKeys[FEEDBACK_TABLE], sVals[FEEDBACK_TABLE];
+    for (uint32_t i = threadIdx.x; i < FEEDBACK_TABLE; i += 256u) { sKeys[i] = FEEDBACK_EMPTY; sVals[i] = 0u; }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n = *a.cmdCount;
+    const DView& dv = *a.view;
+    const float invW = dv.view.renderDimension[2], invH = dv.view.renderDimension[3];
+    const uint32_t first = blockIdx.x * a.blocksPerGroup, end = min(first + a.blocksPerGroup, a.waveBlocks);
+    for (uint32_t block = first + (threadIdx.x >> 6); block < end; block += 4u) {
+        const uint32_t bx = block % a.blocksX, by = block / a.blocksX;
+        const uint32_t x = (bx * 16u + (lane & 15u)) * a.stride + a.offX, y = (by * 4u + (lane >> 4)) * a.stride + a.offY;
+        const bool inside = x < a.W && y < a.H;
+        const uint32_t low = inside ? (uint32_t)a.vis[(size_t)y * a.W + x] : 0u;
+        const uint32_t slot = ((low >> 8) & CHORD_MAX_INSTANCE_ID) - 1u;   // base.hlsli:443-447
+        const bool covered = low != 0u && slot < n;
+
+        // one leader per distinct (slot, triangle) of the wave
+        int leader = (int)lane;
+        uint64_t pending = __ballot(covered);
+        while (pending) {
+            const int l = __ffsll((unsigned long long)pending) - 1;
+            const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)low, l);
+            const bool mine = covered && low == key;
+            if (mine) leader = l;
+            pending &= ~__ballot(mine);
+        }
+        const bool isLeader = covered && leader == (int)lane;
+
+        bool ok = false;
+        float phs[3][4] = {}, uvv[3][2] = {};
+        uint32_t matId = 0u;
+        if (isLeader) {
+            const ChordDrawCmd cmd = a.cmds[slot];
+            const uint32_t tri = low & 0xFFu;
+            if (cmd.objectId < a.objectCount && cmd.meshletId < a.meshletCount) {
+                const DMeshlet& m = a.meshlets[cmd.meshletId];
+                const uint32_t V = m.vertexTriangleCount & 0xFFu, T = (m.vertexTriangleCount >> 8) & 0xFFu;
+                if (tri < T) {
+                    ok = true;
+                    const Mat4 M = load_mat(a.objects[cmd.objectId].basicData.localToTranslatedWorld);
+                    const Mat4 mvp = mul_mm(load_mat(dv.iv.translatedWorldToClip), M);
+                    const uint32_t triWord = a.meshletData[m.dataOffset + V + tri];
+                    matId = CHORD_MATFLAG_MATERIAL(a.objStatic[cmd.objectId].matFlags);
+#pragma unroll
+                    for (int i = 0; i < 3; i++) {
+                        const uint32_t vi = a.meshletData[m.dataOffset + ((triWord >> (8 * i)) & 0xFFu)] + m.vertexBase;
+                        const float px = a.positions[(size_t)vi * 3], py = a.positions[(size_t)vi * 3 + 1], pz = a.positions[(size_t)vi * 3 + 2];
+                        const f4 h = mul_mv(mvp, px, py, pz, 1.0f);
+                        phs[i][0] = h.x; phs[i][1] = h.y; phs[i][2] = h.z; phs[i][3] = h.w;
+                        if (a.texcoords) { uvv[i][0] = a.texcoords[(size_t)vi * 2]; uvv[i][1] = a.texcoords[(size_t)vi * 2 + 1]; }
+                    }
+                }
+            }
+        }
+
+        const bool hit = covered && lane_read((uint32_t)ok, leader) != 0u;
+        float P[3][4], U[3][2];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) P[i][k] = lane_read(phs[i][k], leader);
+            U[i][0] = lane_read(uvv[i][0], leader); U[i][1] = lane_read(uvv[i][1], leader);
+        }
+        const float su = ((float)x + 0.5f) * invW, sv = ((float)y + 0.5f) * invH;
+        const float pcx = 2.0f * (su - 0.5f), pcy = 2.0f * (0.5f - sv);
+        // calculateTriangleBarycentrics -- base.hlsli:457-495: the derivative half
+        const f3 rcpW = {1.0f / P[0][3], 1.0f / P[1][3], 1.0f / P[2][3]};
+        const float p0x = P[0][0] * rcpW.x, p0y = P[0][1] * rcpW.x;
+        const float p1x = P[1][0] * rcpW.y, p1y = P[1][1] * rcpW.y;
+        const float p2x = P[2][0] * rcpW.z, p2y = P[2][1] * rcpW.z;
+        const f3 p120x = {p1x, p2x, p0x}, p120y = {p1y, p2y, p0y}, p201x = {p2x, p0x, p1x}, p201y = {p2y, p0y, p1y};
+        const f3 cdx = {p201y.x - p120y.x, p201y.y - p120y.y, p201y.z - p120y.z};
+        const f3 cdy = {p120x.x - p201x.x, p120x.y - p201x.y, p120x.z - p201x.z};
+        const f3 C = {cdx.x * (pcx - p120x.x) + cdy.x * (pcy - p120y.x),
+                      cdx.y * (pcx - p120x.y) + cdy.y * (pcy - p120y.y),
+                      cdx.z * (pcx - p120x.z) + cdy.z * (pcy - p120y.z)};
+        const f3 G = {C.x * rcpW.x, C.y * rcpW.y, C.z * rcpW.z};
+        const float Hs = dot3(C, rcpW);
+        const float rcpH = 1.0f / Hs;
+        const f3 gdx = {cdx.x * rcpW.x, cdx.y * rcpW.y, cdx.z * rcpW.z};
+        const f3 gdy = {cdy.x * rcpW.x, cdy.y * rcpW.y, cdy.z * rcpW.z};
+        const float hdx = dot3(cdx, rcpW), hdy = dot3(cdy, rcpW);
+        const float rcpH2 = rcpH * rcpH, sx = 2.0f * invW, sy = -2.0f * invH;
+        const f3 ddx = {((gdx.x * Hs - G.x * hdx) * rcpH2) * sx, ((gdx.y * Hs - G.y * hdx) * rcpH2) * sx, ((gdx.z * Hs - G.z * hdx) * rcpH2) * sx};
+        const f3 ddy = {((gdy.x * Hs - G.x * hdy) * rcpH2) * sy, ((gdy.y * Hs - G.y * hdy) * rcpH2) * sy, ((gdy.z * Hs - G.z * hdy) * rcpH2) * sy};
+        const float4 g = make_float4(interp3(U[0][0], U[1][0], U[2][0], ddx), interp3(U[0][1], U[1][1], U[2][1], ddx),
+                                     interp3(U[0][0], U[1][0], U[2][0], ddy), interp3(U[0][1], U[1][1], U[2][1], ddy));
+        const uint32_t mId = lane_read(matId, leader);
+
+        // one turn per distinct material of the wave; its record is wave-uniform
+        uint64_t left = __ballot(hit);
+        while (left) {
+            const int l = __ffsll((unsigned long long)left) - 1;
+            const uint32_t mat = (uint32_t)__builtin_amdgcn_readlane((int)mId, l);
+            const bool mine = hit && mId == mat;
+            const uint64_t lanes = __ballot(mine);
+            left &= ~lanes;
+            const DMatRecord& M = a.records[mat];
+            if (!M.pbr) continue;
+            for (uint32_t s = 0; s < 4u; s++) {
+                if (!((a.slotMask >> s) & 1u) || !M.slot[s].mips) continue;
+                const DMatSlot& S = M.slot[s];
+                const uint32_t l0 = mine ? feedback_level(S, g, a.kmax) : 0u;
+                const uint32_t row = S.texture * CHORD_FEEDBACK_LEVELS;
+                uint64_t rest = lanes;
+                while (rest) {                                          // one turn per distinct level of the slot's lanes
+                    const int q = __ffsll((unsigned long long)rest) - 1;
+                    const uint32_t level = (uint32_t)__builtin_amdgcn_readlane((int)l0, q);
+                    const uint64_t same = __ballot(mine && l0 == level);
+                    rest &= ~same;
+                    const uint32_t key = row + level;
+                    if ((int)lane == q && key < a.tapWords) feedback_add(sKeys, sVals, a.taps, a.tableMask, key, (uint32_t)__popcll((unsigned long long)same));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < FEEDBACK_TABLE; i += 256u)
+        if (sKeys[i] != FEEDBACK_EMPTY && sVals[i]) atomicAdd(&a.taps[sKeys[i]], sVals[i]);
+}
+
 static ResolveArgs resolve_args(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                                 const ChordResolveDesc& desc, const ChordResolveTargets& t)
 {
@@ -786,6 +993,30 @@ void launch_resolve_gbuffer(ChordCtx* c, const unsigned long long* vis, const Ch
     ml.material.pixelNormal = reinterpret_cast<float*>(g.pixelNormal);
     ml.material.roughMetalAO = reinterpret_cast<float*>(g.aoRoughnessMetallic);
     launch_material_level<true>(c, vis, cmds, cmdCount, desc, t, ml);
+}
+
+void launch_material_feedback(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                              const ChordFeedbackDesc& desc, uint32_t* taps, uint32_t textureCount)
+{
+    FeedbackArgs a;
+    a.vis = vis; a.cmds = cmds; a.cmdCount = cmdCount;
+    a.objects = c->dObjects; a.objStatic = c->dObjStatic; a.meshlets = c->dMeshlets; a.meshletData = c->dMeshletData;
+    a.positions = c->dPositions; a.texcoords = c->dTexcoords; a.view = c->dView; a.records = c->dMatRecords; a.taps = taps;
+    a.W = c->width; a.H = c->height;
+    a.stride = desc.stride; a.offX = desc.offset[0]; a.offY = desc.offset[1]; a.slotMask = desc.slotMask;
+    // lattice pixels per row / column: those x = i * stride + offset below the size (none when the offset is not)
+    const uint32_t latW = a.offX < a.W ? (a.W - a.offX + a.stride - 1u) / a.stride : 0u, latH = a.offY < a.H ? (a.H - a.offY + a.stride - 1u) / a.stride : 0u;
+    a.blocksX = (latW + 15u) / 16u;
+    a.waveBlocks = a.blocksX * ((latH + 3u) / 4u);
+    if (!a.waveBlocks) return;
+    // strips: at most four workgroups per CU, each at least its four waves' one block
+    const uint32_t groups = min((a.waveBlocks + 3u) / 4u, (uint32_t)c->numCUs * 4u);
+    a.blocksPerGroup = (a.waveBlocks + groups - 1u) / groups;
+    a.objectCount = c->objectCount; a.meshletCount = c->meshletCount;
+    a.kmax = c->matAnisotropy > 1u ? (uint32_t)__builtin_ctz(c->matAnisotropy) : 0u;
+    a.tapWords = textureCount * CHORD_FEEDBACK_LEVELS;
+    a.tableMask = (c->debugFlags & 4194304u) ? 1u : FEEDBACK_TABLE - 1u;   // (the debug switch: two entries, so that most adds find the table full)
+    CHORD_LAUNCH(c, material_feedback_kernel, dim3((a.waveBlocks + a.blocksPerGroup - 1u) / a.blocksPerGroup), dim3(256), 0, c->stream, a);
 }
 
 } // namespace chord

@@ -96,6 +96,15 @@ TEXMIPS_SRGB, TEXMIPS_COVERAGE, TEXMIPS_FULL = 1, 2, 0xFFFFFFFF
 TEXSTORE_EXPANDED, TEXSTORE_BLOCKS = 0, 1          # chordvis_set_material_texture_store
 
 
+class FeedbackDesc(C.Structure):
+    """ChordFeedbackDesc: which slots and which lattice of pixels chordvis_material_feedback counts."""
+    _fields_ = [("slotMask", C.c_uint32), ("stride", C.c_uint32), ("offset", C.c_uint32 * 2)]
+
+
+FEEDBACK_LEVELS = 16                               # words per texture of the feedback buffer
+FEEDBACK_BASECOLOR, FEEDBACK_EMISSIVE, FEEDBACK_NORMAL, FEEDBACK_METALROUGH = 1, 2, 4, 8
+
+
 class HZB(C.Structure):
     _fields_ = [("desc", R.HZBDesc), ("minTexels", C.c_void_p), ("maxTexels", C.c_void_p), ("validRange", C.c_void_p)]
 
@@ -254,6 +263,12 @@ def _load():
         "chordvis_set_texture_compress": (i32, [vp, P(u32), u32]),
         "chordvis_texture_compress": (i32, [vp, u32, P(u32)]),
         "chordvis_readback_material_blocks": (i32, [vp, u32, vp, u64]),
+        "chordvis_material_feedback_reset": (i32, [vp]),
+        "chordvis_material_feedback": (i32, [vp, CountAndCmd, P(FeedbackDesc)]),
+        "chordvis_readback_material_feedback": (i32, [vp, vp, u32]),
+        "chordvis_set_texture_first_level": (i32, [vp, P(u32), u32]),
+        "chordvis_texture_first_level": (i32, [vp, u32, P(u32)]),
+        "chordvis_material_texture_levels": (i32, [vp, u32, P(u32), P(u32)]),
         "chordvis_material_constants": (i32, [vp, vp]),
         "chordvis_stream": (vp, [vp]),
         "chordvis_readback_tile_marker": (i32, [vp, P(TileMarker), vp]),

@@ -65,7 +65,8 @@ class VisibilityRenderer:
         """(h, w, 4) uint8: the expanded texels of one level of a texture as chordvis_resolve_material reads them (after
         upload_material_textures; block-compressed textures as the library decoded them)."""
         t = self.scene.texture_images[texture]
-        h, w = max(1, t.shape[0] >> level), max(1, t.shape[1] >> level)
+        level0 = level + self._stored_first_level(texture)     # (set_texture_first_level: `level` counts from the first stored one)
+        h, w = max(1, t.shape[0] >> level0), max(1, t.shape[1] >> level0)
         out = np.zeros((h, w, 4), dtype=np.uint8)
         self._check(L.lib.chordvis_readback_material_texture(self._ctx, int(texture), int(level), out.ctypes.data), "readback_material_texture")
         return out
@@ -73,8 +74,8 @@ class VisibilityRenderer:
     def readback_material_blocks(self, texture, format=None, levels=None):
         """uint8 array: the whole chain of a texture kept as blocks, in the layout of ChordTexture (after upload_material_textures
         under lib.TEXSTORE_BLOCKS): the bytes supplied, or what set_texture_compress made the GPU encode.  format / levels: of
-        the stored chain (default: what the current compress and mips settings give the scene's texture).  A lib.ChordvisError
-        for a texture stored as texels."""
+        the FINISHED chain (default: what the current compress and mips settings give the scene's texture); a chain trimmed by
+        set_texture_first_level comes back from its first stored level on.  A lib.ChordvisError for a texture stored as texels."""
         t = self.scene.texture_images[texture]
         if format is None:
             format = self.texture_compress(texture) or getattr(t, "format", 0)
@@ -82,10 +83,17 @@ class VisibilityRenderer:
             full = max(t.shape[0], t.shape[1]).bit_length()
             levels, mips = self.texture_mips(texture)[0], getattr(t, "mips", full)      # (an image: Scene supplies its full chain)
             levels = mips if not levels else max(mips, min(levels, full))
-        n = L.texture_chain_bytes(format, t.shape[1], t.shape[0], levels) if format else 0
+        first = min(self._stored_first_level(texture), levels - 1)                       # (set_texture_first_level: the stored chain is the smaller texture's)
+        n = L.texture_chain_bytes(format, max(1, t.shape[1] >> first), max(1, t.shape[0] >> first), levels - first) if format else 0
         out = np.zeros(max(1, n), dtype=np.uint8)
         self._check(L.lib.chordvis_readback_material_blocks(self._ctx, int(texture), out.ctypes.data, n), "readback_material_blocks")
         return out
+
+    def _stored_first_level(self, texture):
+        """firstLevel of chordvis_material_texture_levels; 0 where the store holds nothing of the texture"""
+        f = C.c_uint32(0)
+        rc = L.lib.chordvis_material_texture_levels(self._ctx, int(texture), C.byref(f), None)
+        return f.value if rc == L.OK else 0
 
     def read_alpha_plane(self, count, offset=0):
         """`count` bytes of the alpha plane the masked buckets sample, from byte `offset` (chordvis_debug_read 7)."""
@@ -143,6 +151,45 @@ class VisibilityRenderer:
         f = C.c_uint32(0)
         self._check(L.lib.chordvis_texture_compress(self._ctx, int(texture), C.byref(f)), "texture_compress")
         return f.value
+
+    def set_texture_first_level(self, first):
+        """Trimmed chains: entry i is the first level LATER upload_material_textures calls keep of texture id i (clamped to its last
+        level); None or an empty list: every texture keeps level 0 (the default).  The stored texture is then the one whose level 0
+        is that level, and every level index counts from there.  Per context; kept across uploads; ignored by upload_scene."""
+        first = [int(f) for f in (first or ())]
+        arr = (C.c_uint32 * max(1, len(first)))(*first)
+        self._check(L.lib.chordvis_set_texture_first_level(self._ctx, arr if first else None, len(first)), "set_texture_first_level")
+
+    def texture_first_level(self, texture):
+        """The first level set for a texture id; 0 where nothing is set."""
+        f = C.c_uint32(0)
+        self._check(L.lib.chordvis_texture_first_level(self._ctx, int(texture), C.byref(f)), "texture_first_level")
+        return f.value
+
+    def material_texture_levels(self, texture):
+        """(firstLevel, levelCount) of what the uploaded store holds of a texture a material names."""
+        f, n = C.c_uint32(0), C.c_uint32(0)
+        self._check(L.lib.chordvis_material_texture_levels(self._ctx, int(texture), C.byref(f), C.byref(n)), "material_texture_levels")
+        return f.value, n.value
+
+    def reset_material_feedback(self):
+        """Zeroes the context's feedback buffer (allocating it after a material upload), on the context's stream."""
+        self._check(L.lib.chordvis_material_feedback_reset(self._ctx), "material_feedback_reset")
+
+    def material_feedback(self, slot_mask=15, stride=1, offset=(0, 0), drawed_meshlet_cmd=None):
+        """Adds, for every pixel (x % stride, y % stride) == offset that resolve_attributes would write material images for and
+        every texture slot of slot_mask (lib.FEEDBACK_* bits), 1 to the count of the finest level the material sampler would
+        fetch there (chordvis_material_feedback: one launch on the context's stream; counts accumulate until the next reset)."""
+        d = L.FeedbackDesc(int(slot_mask), int(stride), (C.c_uint32 * 2)(int(offset[0]), int(offset[1])))
+        cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
+        self._check(L.lib.chordvis_material_feedback(self._ctx, cmd, C.byref(d)), "material_feedback")
+
+    def read_material_feedback(self, texture_count=None):
+        """(textureCount, lib.FEEDBACK_LEVELS) uint32: the counts per texture id and stored level; synchronises."""
+        n = len(self.scene.texture_images) if texture_count is None else int(texture_count)
+        out = np.zeros((n, L.FEEDBACK_LEVELS), dtype=np.uint32)
+        self._check(L.lib.chordvis_readback_material_feedback(self._ctx, out.ctypes.data if n else np.zeros(1, np.uint32).ctypes.data, n), "readback_material_feedback")
+        return out
 
     def texture_mips(self, texture):
         """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""

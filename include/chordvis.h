@@ -719,6 +719,68 @@ int chordvis_texture_compress(const ChordCtx* ctx, uint32_t textureId, uint32_t*
  * compressed comes back as the bytes supplied.  CHORDVIS_E_INVALID when no material textures are uploaded, when the texture is not
  * kept as blocks (no material names it, or it is stored as texels), or when `bytes` differs from the chain's size. */
 int chordvis_readback_material_blocks(ChordCtx* ctx, uint32_t textureId, uint8_t* host, uint64_t bytes);
+/* Opt-in: sampler feedback.  Which levels of which textures does the frame read?  The level rule is this library's (DESIGN.md 2 item
+ * 9), so a host with a streaming or budgeted texture pool cannot work it out itself; this pass counts it, and
+ * chordvis_set_texture_first_level (below) is the upload option that leaves out the levels nobody read.
+ * The buffer is the context's: CHORD_FEEDBACK_LEVELS uint32 words per texture of the last chordvis_upload_material_textures
+ * descriptor (levels 0..14 exist; word 15 stays 0).
+ *   chordvis_material_feedback_reset   allocates it on first use after a material upload and zeroes it on the context's stream.
+ *   chordvis_material_feedback         ONE launch on the context's stream that accumulates into it: calling it twice doubles the
+ *                                      counts, and several views or lattice offsets may be summed.  Counts are uint32, modulo 2^32:
+ *                                      reset before they can wrap (a call adds at most 4 x width x height / stride^2 in all).
+ *   chordvis_readback_material_feedback synchronises and copies textureCount x CHORD_FEEDBACK_LEVELS words.
+ * Definition.  A pixel of the lattice (x % stride == offset[0] and y % stride == offset[1]) contributes when it is covered, its id is
+ * below the list's count, it has a valid triangle and its material is kLightingType_GLTF_MetallicRoughnessPBR: exactly the pixels
+ * chordvis_resolve_material writes material images for.  For each slot s of slotMask in which its material names a texture, let l0 be
+ * the finer of the two levels the sampler of chordvis_resolve_material would fetch for that pixel and slot under the context's current
+ * chordvis_material_anisotropy (N = 1: from lodq; N > 1: from lodq'; a sampler without a mip filter: 0); the pass adds 1 to
+ * taps[texture of the slot][l0].  A texture several materials or slots name gets the sum; one no material names stays 0.  All
+ * adds are integers: the result does not depend on their order.  Levels count as the stored texture's do (a texture trimmed by
+ * chordvis_set_texture_first_level: from its first stored level).
+ * Preconditions, waits and image are those of chordvis_resolve_material asked for a material target (material textures uploaded, a
+ * frame rendered, no chordvis_update_objects / chordvis_set_view since, the resolved row-major image after the same wait; a rank of a
+ * sharded set-up counts the whole image); neither normals nor tangents are needed.  CHORDVIS_E_INVALID besides, chordvis_last_error
+ * naming the allowed values: no chordvis_material_feedback_reset since the last material upload; desc NULL; slotMask 0 or above 15;
+ * a stride other than 1, 2, 4 or 8; an offset not below the stride; a textureCount that differs from the uploaded count. */
+#define CHORD_FEEDBACK_LEVELS      16u
+#define CHORD_FEEDBACK_BASECOLOR    1u   /* slotMask bits, in the order of ChordMaterialTargets */
+#define CHORD_FEEDBACK_EMISSIVE     2u
+#define CHORD_FEEDBACK_NORMAL       4u
+#define CHORD_FEEDBACK_METALROUGH   8u
+typedef struct ChordFeedbackDesc {
+    uint32_t slotMask;     /* 1..15 */
+    uint32_t stride;       /* 1, 2, 4 or 8 */
+    uint32_t offset[2];    /* each < stride */
+} ChordFeedbackDesc;
+int chordvis_material_feedback_reset(ChordCtx* ctx);
+int chordvis_material_feedback(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordFeedbackDesc* desc);
+int chordvis_readback_material_feedback(ChordCtx* ctx, uint32_t* hostTaps /* textureCount x CHORD_FEEDBACK_LEVELS */, uint32_t textureCount);
+/* Opt-in: trimmed mip chains.  Entry i is the first level texture id i of the descriptors given to LATER
+ * chordvis_upload_material_textures calls keeps; textures at or beyond `count` keep level 0.  The array is copied and held per
+ * context (as the mips and compress settings are); NULL or count 0 clears it.  chordvis_upload_scene's alpha plane ignores it (the
+ * raster's alpha test taps occluded fragments too, which no feedback from visible pixels covers), so frames stay word for word; with
+ * no setting every launch and every stored byte is what it is without this call.
+ * Rule.  Let L be the texture's level count after chordvis_set_texture_mips and f = min(first, L - 1).  The chain is finished exactly as
+ * without the setting (supplied levels as they are, made levels from the last supplied one, COVERAGE measured on level 0); then levels
+ * 0 .. f-1 are not stored.  From the upload on the texture IS the one whose level 0 is the chain's level f: max(1, w >> f) x
+ * max(1, h >> f) with L - f levels, and every level index the library takes or reports counts from there
+ * (chordvis_readback_material_texture, chordvis_readback_material_blocks -- whose `bytes` is the chain size of the smaller texture --,
+ * the feedback rows).  RGBA8 and expanded BC textures keep texels of the kept levels only (and decode only those when no level has to
+ * be made); a BC chain kept as blocks keeps the bytes from level f's offset; chordvis_set_texture_compress encodes only the kept
+ * levels.  chordvis_material_texture_memory and both caps count what stays resident; staging buffers hold the finished chain while
+ * the call runs.
+ * Property (not a promise for all inputs): the images of chordvis_resolve_material equal the untrimmed ones bit for bit when the
+ * texture's width and height are multiples of 2^f, no contributing pixel's l0 is below f, and the sampler's min and mag filters agree on
+ * nearest versus bilinear -- scaling both dimensions by 2^-f scales the squared footprint by exactly 4^-f, which shifts lodq by exactly
+ * 256 f, and the anisotropic k is not bound by its ceil(lmaj) cap while lodq' >= 256 f.  The exception the third condition covers: a
+ * pixel with lodq in (256 f - 128, 256 f] under *_MIPMAP_NEAREST, or exactly 256 f under *_MIPMAP_LINEAR, is minified untrimmed and not
+ * minified trimmed, where it takes the mag filter. */
+int chordvis_set_texture_first_level(ChordCtx* ctx, const uint32_t* perTextureFirst, uint32_t count);
+/* The setting of one texture id; 0 at or beyond the count of the last call. */
+int chordvis_texture_first_level(const ChordCtx* ctx, uint32_t textureId, uint32_t* first);
+/* What the store holds of a texture a material names: firstLevel = f of the upload (add it to a stored level's index for the level of
+ * the finished chain), levelCount = L - f.  CHORDVIS_E_INVALID when no material textures are uploaded or no material names it. */
+int chordvis_material_texture_levels(ChordCtx* ctx, uint32_t textureId, uint32_t* firstLevel, uint32_t* levelCount);
 /* The G-buffer in the reference's packed image formats -- what exportGbuffer (lighting.hlsl:62-73) writes into GBufferTextures
  * (render_textures.h:27-49) and every later pass reads: 28 bytes per pixel for the six images, where the float images of
  * chordvis_resolve_material take 88.  The packing is pinned; float32, source order, unfused; R in the low bits:
@@ -817,7 +879,9 @@ int chordvis_stats(ChordCtx* ctx, ChordStats* out);
  * hzb_tail_kernel between the raster passes instead of letting the phase-1 cull reduce HZB levels 6.. itself, 262144 the
  * pixel-block kernel always runs its hot-tile variant and treats a bin of 64 entries as hot (by default the variant is chosen
  * when the previous frame had a bin of 65536 entries or more), 524288 the library's own sharded frames (chordvis_comm_*, ChordGroup)
- * keep the replicated group cull instead of the sharded one (A / B measurements; every rank of a frame must agree). */
+ * keep the replicated group cull instead of the sharded one (A / B measurements; every rank of a frame must agree), 4194304
+ * chordvis_material_feedback's workgroups use 2 entries of their on-chip count tables instead of 512, so that most adds find
+ * the table full and go to global memory (the same counts, slower). */
 int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 /* measurement / test aid: fills EVERY rank's chunk of the cull exchange buffer on this context for the current view (what the
  * all-gather would deliver), so that one rank of a sharded frame can be timed alone on one device (tools/shard_time.py) */

@@ -7,6 +7,7 @@ targets of chordvis_resolve_surface (vertexNormal, tangent, bitangent), bytes mo
     python tools/resolve_time.py [N] [WARMUP] --materials [--sets a,b] [--compare OTHER_LIB [ROUNDS]] [--compare-sets a,b]
     python tools/resolve_time.py [N] [WARMUP] --materials --sets material --anisotropy 1,8,16 [--taps]
     python tools/resolve_time.py [N] [WARMUP] --materials --sets gbuffer,gbuffer_float --alternate 5
+    python tools/resolve_time.py [N] [WARMUP] --materials --sets material --feedback 1,2,4
 
 --materials: config 3 under the textured materials (scenes.config3_street(materials=True)) and two more sets: `material` (the four
 images of chordvis_resolve_material) and `everything` (all fifteen).  Their bytes column counts the image bytes only (the texels
@@ -22,6 +23,8 @@ again (ROUNDS times, default 3): this library against the other one, and the oth
 chordvis_set_material_anisotropy (its line is named set@value); the other sets are timed once.
 --taps: per value, the sampler taps and the texel fetches the pinned sampler requests per PBR pixel of the frame, counted on the
 host by tests/spec_material_aniso_np.py's tap_plan from the uv gradients the device resolved (no texel is read).
+--feedback S,T,...: after the sets, chordvis_material_feedback at slotMask 15 is timed once per stride (offset 0, 0), the same way
+(its line is named feedback/stride; the buffer is reset before each timed run), and the counts of the first stride are printed.
 """
 import json
 import os
@@ -168,10 +171,28 @@ def main():
                               **({"runs_ms": [round(t, 4) for t in times[name]]} if alternate > 1 else {})))
     info = dict(workload="config3_materials_3840x2160_two_pass" if materials else "config3_masked_attributes_3840x2160_two_pass", pixels=cam.width * cam.height, covered=covered, resolves=n, warmup=warm,
                 device=torch.cuda.get_device_name(0))
-    for ln in lines:
+    for ln in [ln for ln in lines if "bytes" in ln]:
         print("%-20s %8.4f ms  %3d B/px  %6.1f MB  bound %.4f ms @8 TB/s, %.4f ms @6.3 TB/s  -> %.1f %% of 8 TB/s" % (
             ln["targets"], ln["ms"], ln["bytes_per_pixel"], ln["bytes"] / 1e6, ln["bytes_bound_ms_8tbs"], ln["bytes_bound_ms_6p3tbs"],
             100.0 * ln["share_of_8tbs"]) + ("   runs %s" % ln["runs_ms"] if "runs_ms" in ln else ""))
+    if "--feedback" in argv:
+        for stride in [int(x) for x in argv[argv.index("--feedback") + 1].split(",")]:
+            with torch.cuda.stream(stream):
+                r.reset_material_feedback()
+                for _ in range(warm):
+                    r.material_feedback(15, stride)
+                r.reset_material_feedback()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(n):
+                    r.material_feedback(15, stride)
+                e1.record(stream)
+                e1.synchronize()
+            taps = r.read_material_feedback()
+            ms = e0.elapsed_time(e1) / n
+            lines.append(dict(targets="feedback/%d" % stride, ms=round(ms, 4), lattice_pixels=((cam.width + stride - 1) // stride) * ((cam.height + stride - 1) // stride),
+                              taps_per_call=int(taps.sum()) // n, rows=[[int(v) // n for v in row[:12]] for row in taps]))
+            print("%-20s %8.4f ms  %9d lattice pixels  %9d taps per call" % (lines[-1]["targets"], ms, lines[-1]["lattice_pixels"], lines[-1]["taps_per_call"]))
     if "--taps" in argv:
         info["taps"] = {}
         for a, (taps, fetches, pbr) in count_taps(r, scene, [1 if a is None else a for a in aniso]).items():
