@@ -675,7 +675,7 @@ int chordvis_destroy(ChordCtx* c)
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dTexEncTables);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -1062,6 +1062,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
 #undef UP
     c->instTriangles = instTriangles;
     drop_material_textures(c);                                             // (chordvis_upload_material_textures is per scene upload)
+    dfree(c->dGeoFeedback); c->geoFeedbackCmds = nullptr;                  // (chordvis_geometry_feedback's counts are per scene upload too)
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }       // (it aliased the old scene buffers)
     if ((rc = chord::alloc_scene_work_buffers(c))) return rc;
     CHORD_HIP(c, hipMemcpy(c->dObjectsOwned, s->objects, sizeof(ChordObject) * s->objectCount, hipMemcpyHostToDevice));
@@ -2209,6 +2210,109 @@ int chordvis_readback_material_feedback(ChordCtx* c, uint32_t* hostTaps, uint32_
     (void)hipSetDevice(c->device);
     CHORD_HIP(c, hipStreamSynchronize(c->stream));
     if (textureCount) CHORD_HIP(c, hipMemcpy(hostTaps, c->dMatFeedback, (size_t)textureCount * CHORD_FEEDBACK_LEVELS * 4u, hipMemcpyDeviceToHost));
+    return CHORDVIS_OK;
+}
+
+// ---------------------------------------------------------------- geometry feedback (kernels_geometry.hip) --
+
+int chordvis_geometry_feedback_reset(ChordCtx* c)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "geometry_feedback_reset: no scene (call chordvis_upload_scene first)");
+    (void)hipSetDevice(c->device);
+    if (!c->dGeoFeedback) {
+        const uint64_t O = c->objectCount, P = (uint64_t)c->primCount * CHORD_GEOMETRY_LODS, B = ((uint64_t)c->cmdCapacity + 31u) / 32u, G = (B + 255u) / 256u;
+        const uint64_t words = 3u * O + 3u * P + 4u + B + G;
+        if (words >= 0xFFFFFFFFull || c->cmdCapacity > 0xFFFFFF00u) return fail(c, CHORDVIS_E_CAPACITY, "geometry_feedback_reset: more than 2^32 words of counts");
+        chord::GeoLayout& l = c->geoLayout;
+        l.objectPixels = 0u; l.objectSubmitted = (uint32_t)O; l.objectVisible = (uint32_t)(2u * O);
+        l.lodPixels = (uint32_t)(3u * O); l.lodSubmitted = (uint32_t)(3u * O + P); l.lodVisible = (uint32_t)(3u * O + 2u * P);
+        l.totals = (uint32_t)(3u * O + 3u * P);
+        l.seen = l.totals + 4u; l.seenWords = (uint32_t)B;
+        l.groupCounts = l.seen + l.seenWords; l.groups = (uint32_t)G;
+        l.words = (uint32_t)words;
+        int rc;
+        if ((rc = dalloc(c, &c->dGeoFeedback, (size_t)words))) return rc;
+    }
+    CHORD_HIP(c, hipMemsetAsync(c->dGeoFeedback, 0, (size_t)c->geoLayout.words * 4u, c->stream));
+    c->geoFeedbackCmds = nullptr;
+    return CHORDVIS_OK;
+}
+
+// chordvis_resolve_attributes' preconditions, then the pass's own
+int chordvis_geometry_feedback(ChordCtx* c, ChordCountAndCmd drawed, const ChordGeometryFeedbackDesc* desc)
+{
+    int rc = resolve_checks(c, "geometry_feedback", drawed, true, false, ChordResolveDesc{});
+    if (rc) return rc;
+    if (!c->dGeoFeedback) return fail(c, CHORDVIS_E_INVALID, "geometry_feedback: no chordvis_geometry_feedback_reset since the last chordvis_upload_scene");
+    if (!desc) return fail(c, CHORDVIS_E_INVALID, "geometry_feedback: null ChordGeometryFeedbackDesc");
+    if (desc->stride != 1u && desc->stride != 2u && desc->stride != 4u && desc->stride != 8u)
+        return fail(c, CHORDVIS_E_INVALID, "geometry_feedback: stride is 1, 2, 4 or 8");
+    if (desc->offset[0] >= desc->stride || desc->offset[1] >= desc->stride)
+        return fail(c, CHORDVIS_E_INVALID, "geometry_feedback: each offset is 0 .. stride - 1");
+    if (desc->pad) return fail(c, CHORDVIS_E_INVALID, "geometry_feedback: pad is 0");
+    const unsigned long long* vis = nullptr;
+    if ((rc = resolve_source(c, drawed, &vis))) return rc;
+    // the bitmap is the latest call's
+    CHORD_HIP(c, hipMemsetAsync(c->dGeoFeedback + c->geoLayout.seen, 0, (size_t)c->geoLayout.seenWords * 4u, c->stream));
+    chord::launch_geometry_feedback(c, vis, drawed.cmds, drawed.count, *desc);
+    CHORD_HIP(c, hipGetLastError());
+    c->geoFeedbackCmds = drawed.cmds;
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_geometry_feedback(ChordCtx* c, const ChordGeometryFeedback* out, uint32_t objectCount, uint32_t primitiveCount)
+{
+    if (!c || !out) return fail(c, CHORDVIS_E_INVALID, "readback_geometry_feedback: null argument");
+    if (!c->sceneLoaded || !c->dGeoFeedback)
+        return fail(c, CHORDVIS_E_INVALID, "readback_geometry_feedback: no chordvis_geometry_feedback_reset since the last chordvis_upload_scene");
+    if (objectCount != c->objectCount || primitiveCount != c->primCount) {
+        char buf[192];
+        std::snprintf(buf, sizeof(buf), "readback_geometry_feedback: objectCount and primitiveCount are the uploaded scene's, %u and %u",
+                      (unsigned)c->objectCount, (unsigned)c->primCount);
+        return fail(c, CHORDVIS_E_INVALID, buf);
+    }
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    const chord::GeoLayout& l = c->geoLayout;
+    const size_t lodWords = (size_t)primitiveCount * CHORD_GEOMETRY_LODS;
+    const struct { uint32_t* host; uint32_t at; size_t words; } copies[7] = {
+        {out->objectPixels, l.objectPixels, objectCount}, {out->objectSubmitted, l.objectSubmitted, objectCount}, {out->objectVisible, l.objectVisible, objectCount},
+        {out->lodPixels, l.lodPixels, lodWords}, {out->lodSubmitted, l.lodSubmitted, lodWords}, {out->lodVisible, l.lodVisible, lodWords},
+        {out->totals, l.totals, 4u}};
+    for (const auto& cp : copies)
+        if (cp.host && cp.words) CHORD_HIP(c, hipMemcpy(cp.host, c->dGeoFeedback + cp.at, cp.words * 4u, hipMemcpyDeviceToHost));
+    return CHORDVIS_OK;
+}
+
+int chordvis_visible_clusters(ChordCtx* c, ChordCountAndCmd drawed, ChordDrawCmd* deviceOut, uint32_t* deviceCount, uint32_t capacity)
+{
+    if (!c || !c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "visible_clusters: no scene");
+    if (!drawed.count || !drawed.cmds) return fail(c, CHORDVIS_E_INVALID, "visible_clusters: null command list");
+    if (!deviceCount || (!deviceOut && capacity)) return fail(c, CHORDVIS_E_INVALID, "visible_clusters: null output (deviceOut may be null only with capacity 0)");
+    if (!c->dGeoFeedback || !c->geoFeedbackCmds)
+        return fail(c, CHORDVIS_E_INVALID, "visible_clusters: no chordvis_geometry_feedback since the last chordvis_geometry_feedback_reset / chordvis_upload_scene");
+    if (drawed.cmds != c->geoFeedbackCmds)
+        return fail(c, CHORDVIS_E_INVALID, "visible_clusters: the list is not the one the latest chordvis_geometry_feedback was given");
+    (void)hipSetDevice(c->device);
+    chord::launch_visible_clusters(c, drawed.cmds, drawed.count, deviceOut, deviceCount, capacity);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_geometry_feedback_seen(ChordCtx* c, uint32_t* hostWords, uint32_t wordCount)
+{
+    if (!c || !hostWords) return fail(c, CHORDVIS_E_INVALID, "geometry_feedback_seen: null argument");
+    if (!c->sceneLoaded || !c->dGeoFeedback)
+        return fail(c, CHORDVIS_E_INVALID, "geometry_feedback_seen: no chordvis_geometry_feedback_reset since the last chordvis_upload_scene");
+    if (wordCount != c->geoLayout.seenWords) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "geometry_feedback_seen: wordCount is ceil(capacity / 32), %u", (unsigned)c->geoLayout.seenWords);
+        return fail(c, CHORDVIS_E_INVALID, buf);
+    }
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    CHORD_HIP(c, hipMemcpy(hostWords, c->dGeoFeedback + c->geoLayout.seen, (size_t)wordCount * 4u, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }
 

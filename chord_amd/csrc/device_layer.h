@@ -69,6 +69,17 @@ struct DObjStatic {            // per object, derived once per upload, 48 B
 };
 static_assert(sizeof(DObjStatic) == 48, "DObjStatic");
 
+// chordvis_geometry_feedback's buffer, one allocation of uint32 words: where each array starts.  A word's index is also its key in the
+// workgroups' count tables (kernels_geometry.hip)
+struct GeoLayout {
+    uint32_t objectPixels, objectSubmitted, objectVisible;   // objectCount words each
+    uint32_t lodPixels, lodSubmitted, lodVisible;            // primCount x CHORD_GEOMETRY_LODS words each
+    uint32_t totals;                                         // 4 words
+    uint32_t seen, seenWords;                                // the bitmap of the latest call: ceil(cmdCapacity / 32) words
+    uint32_t groupCounts, groups;                            // chordvis_visible_clusters' scratch: a word per 256 bitmap words
+    uint32_t words;                                          // the whole buffer
+};
+
 #define CHORD_MATFLAG_TWO_SIDED 1u
 #define CHORD_MATFLAG_ALPHA(f) (((f) >> 1) & 3u)
 #define CHORD_MATFLAG_MATERIAL(f) ((f) >> 8)
@@ -439,6 +450,10 @@ struct ChordCtx {
     std::vector<MatTexInfo> matTex;           // per texture of the descriptor (chordvis_readback_material_texture)
     std::vector<uint32_t> texFirstLevel;      // chordvis_set_texture_first_level: per texture id; kept across uploads, read by chordvis_upload_material_textures alone
     uint32_t* dMatFeedback = nullptr;         // chordvis_material_feedback: CHORD_FEEDBACK_LEVELS words per texture of matTex; made by the first reset after an upload
+    // chordvis_geometry_feedback: the counts, the seen bitmap and the list compaction's scratch; made by the first reset after a scene upload
+    uint32_t* dGeoFeedback = nullptr;
+    chord::GeoLayout geoLayout = {};
+    const ChordDrawCmd* geoFeedbackCmds = nullptr;   // the list of the latest chordvis_geometry_feedback call; null: none since the last reset
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     std::vector<uint32_t> texCompress;        // chordvis_set_texture_compress: per texture id, 0 or a CHORD_TEXFMT_BC* target; kept across uploads, read by chordvis_upload_material_textures under CHORD_TEXSTORE_BLOCKS
@@ -660,6 +675,12 @@ void launch_resolve_gbuffer(ChordCtx* c, const unsigned long long* vis, const Ch
 // kernels_resolve.hip: adds the finest tap level of every lattice pixel and slot of `desc` to taps[texture * CHORD_FEEDBACK_LEVELS + level].  One launch.
 void launch_material_feedback(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
                               const ChordFeedbackDesc& desc, uint32_t* taps, uint32_t textureCount);
+// kernels_geometry.hip: the pixel pass over the lattice of `desc` and the list pass over the commands, adding into c->dGeoFeedback (whose
+// bitmap the caller has cleared).  Two launches.
+void launch_geometry_feedback(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,
+                              const ChordGeometryFeedbackDesc& desc);
+// the commands whose bit the bitmap holds, in list order, into out[0 .. capacity); *outCount = how many there are.  Two launches.
+void launch_visible_clusters(ChordCtx* c, const ChordDrawCmd* cmds, const uint32_t* cmdCount, ChordDrawCmd* out, uint32_t* outCount, uint32_t capacity);
 void launch_pack_gbuffer(ChordCtx* c, uint32_t width, uint32_t height, const ChordGBufferSources& sources, const ChordGBufferTargets& targets);
 // kernels_texture.hip: expands the blocks of `count` levels (recs[count] closes the table) from `staging` into RGBA8 words of
 // `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.

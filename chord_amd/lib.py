@@ -105,6 +105,21 @@ FEEDBACK_LEVELS = 16                               # words per texture of the fe
 FEEDBACK_BASECOLOR, FEEDBACK_EMISSIVE, FEEDBACK_NORMAL, FEEDBACK_METALROUGH = 1, 2, 4, 8
 
 
+class GeometryFeedbackDesc(C.Structure):
+    """ChordGeometryFeedbackDesc: which lattice of pixels chordvis_geometry_feedback counts."""
+    _fields_ = [("stride", C.c_uint32), ("offset", C.c_uint32 * 2), ("pad", C.c_uint32)]
+
+
+class GeometryFeedback(C.Structure):
+    """ChordGeometryFeedback: host pointers chordvis_readback_geometry_feedback fills (None: not wanted)."""
+    _fields_ = [("objectPixels", C.c_void_p), ("objectSubmitted", C.c_void_p), ("objectVisible", C.c_void_p),
+                ("lodPixels", C.c_void_p), ("lodSubmitted", C.c_void_p), ("lodVisible", C.c_void_p), ("totals", C.c_void_p)]
+
+
+GEOMETRY_LODS = 16                                 # LOD columns per primitive of the geometry feedback
+GEOMETRY_ARRAYS = ("objectPixels", "objectSubmitted", "objectVisible", "lodPixels", "lodSubmitted", "lodVisible", "totals")
+
+
 class HZB(C.Structure):
     _fields_ = [("desc", R.HZBDesc), ("minTexels", C.c_void_p), ("maxTexels", C.c_void_p), ("validRange", C.c_void_p)]
 
@@ -266,6 +281,11 @@ def _load():
         "chordvis_material_feedback_reset": (i32, [vp]),
         "chordvis_material_feedback": (i32, [vp, CountAndCmd, P(FeedbackDesc)]),
         "chordvis_readback_material_feedback": (i32, [vp, vp, u32]),
+        "chordvis_geometry_feedback_reset": (i32, [vp]),
+        "chordvis_geometry_feedback": (i32, [vp, CountAndCmd, P(GeometryFeedbackDesc)]),
+        "chordvis_readback_geometry_feedback": (i32, [vp, P(GeometryFeedback), u32, u32]),
+        "chordvis_visible_clusters": (i32, [vp, CountAndCmd, vp, vp, u32]),
+        "chordvis_geometry_feedback_seen": (i32, [vp, vp, u32]),
         "chordvis_set_texture_first_level": (i32, [vp, P(u32), u32]),
         "chordvis_texture_first_level": (i32, [vp, u32, P(u32)]),
         "chordvis_material_texture_levels": (i32, [vp, u32, P(u32), P(u32)]),

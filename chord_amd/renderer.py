@@ -191,6 +191,53 @@ class VisibilityRenderer:
         self._check(L.lib.chordvis_readback_material_feedback(self._ctx, out.ctypes.data if n else np.zeros(1, np.uint32).ctypes.data, n), "readback_material_feedback")
         return out
 
+    def reset_geometry_feedback(self):
+        """Zeroes the context's geometry feedback buffer (allocating it after a scene upload), on the context's stream."""
+        self._check(L.lib.chordvis_geometry_feedback_reset(self._ctx), "geometry_feedback_reset")
+
+    def geometry_feedback(self, stride=1, offset=(0, 0), drawed_meshlet_cmd=None):
+        """Adds what the pixels (x % stride, y % stride) == offset of the last frame's image saw to the context's counts and makes
+        the seen bitmap that of this call (chordvis_geometry_feedback: one memset and two launches on the context's stream)."""
+        d = L.GeometryFeedbackDesc(int(stride), (C.c_uint32 * 2)(int(offset[0]), int(offset[1])), 0)
+        cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
+        self._check(L.lib.chordvis_geometry_feedback(self._ctx, cmd, C.byref(d)), "geometry_feedback")
+
+    def read_geometry_feedback(self, names=L.GEOMETRY_ARRAYS):
+        """{name: uint32 array} of the counts: (objectCount,) for the object arrays, (primitiveCount, lib.GEOMETRY_LODS) for the lod
+        arrays, (4,) for totals (lattice pixels looked at, contributing, rejected, seen commands); synchronises."""
+        no, npr = len(self.scene.objects), len(self.scene.primitives)
+        shape = lambda n: (4,) if n == "totals" else (no,) if n.startswith("object") else (npr, L.GEOMETRY_LODS)
+        out = {n: np.zeros(shape(n), dtype=np.uint32) for n in names}
+        fb = L.GeometryFeedback(**{n: a.ctypes.data for n, a in out.items()})
+        self._check(L.lib.chordvis_readback_geometry_feedback(self._ctx, C.byref(fb), no, npr), "readback_geometry_feedback")
+        return out
+
+    def read_geometry_feedback_seen(self):
+        """uint32 words of the latest geometry_feedback call's seen bitmap: bit i & 31 of word i >> 5 for command i; synchronises."""
+        out = np.zeros((self.last_frame_cmds().capacity + 31) // 32, dtype=np.uint32)
+        self._check(L.lib.chordvis_geometry_feedback_seen(self._ctx, out.ctypes.data, len(out)), "geometry_feedback_seen")
+        return out
+
+    def visible_clusters(self, capacity=None, drawed_meshlet_cmd=None, out=None):
+        """(records, total): the commands the latest geometry_feedback call saw, in list order (chordvis_visible_clusters into a
+        device tensor of `capacity` records, default the list's capacity), read back; total may exceed capacity.  out: a torch int32
+        tensor of at least 3 * capacity + 1 words on the context's device to use instead (records, then the count word)."""
+        import torch
+        cmd = drawed_meshlet_cmd if drawed_meshlet_cmd is not None else self.last_frame_cmds()
+        capacity = int(cmd.capacity if capacity is None else capacity)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            with torch.cuda.device(dev):
+                out = torch.zeros(3 * capacity + 1, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+        assert out.is_contiguous() and out.numel() >= 3 * capacity + 1
+        base = out.data_ptr()
+        self._check(L.lib.chordvis_visible_clusters(self._ctx, cmd, base if capacity else None, base + 12 * capacity, capacity), "visible_clusters")
+        self.sync()
+        host = out.cpu().numpy()
+        total = int(host[3 * capacity:3 * capacity + 1].view(np.uint32)[0])
+        return host[:3 * min(capacity, total)].copy().view(R.DRAW_CMD), total
+
     def texture_mips(self, texture):
         """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""
         m = L.TextureMips()

@@ -781,6 +781,69 @@ int chordvis_texture_first_level(const ChordCtx* ctx, uint32_t textureId, uint32
 /* What the store holds of a texture a material names: firstLevel = f of the upload (add it to a stored level's index for the level of
  * the finished chain), levelCount = L - f.  CHORDVIS_E_INVALID when no material textures are uploaded or no material names it. */
 int chordvis_material_texture_levels(ChordCtx* ctx, uint32_t textureId, uint32_t* firstLevel, uint32_t* levelCount);
+/* Opt-in: geometry feedback.  What did the frame SEE?  Which objects own a pixel (the occlusion-query answer), which LOD levels of
+ * which primitive the cut selected and which of those reached the image, how many of the submitted clusters ended up visible, and the
+ * visible clusters themselves as a command list.  The slot -> command mapping, a pixel's validity rule and a meshlet's LOD live in
+ * device buffers, so a host cannot work this out; these calls count it on the device.  Integers throughout: the result does not depend
+ * on the order of the adds.  No existing launch, record or image changes; the calls add launches only when made.
+ * Inputs.  The row-major (resolved) visibility image chordvis_visibility_mark reads, and `drawed`, the list its ids index.  Let
+ * n = min(*drawed.count, the context's command capacity -- the `capacity` of chordvis_last_frame_cmds' handle); drawed.cmds must hold
+ * n records.  A pixel of the lattice has x % stride == offset[0] and y % stride == offset[1].  With low = word & 0xFFFFFFFF, a lattice
+ * pixel CONTRIBUTES when low != 0, slot = ((low >> 8) & 0xFFFFFF) - 1 < n, cmd = cmds[slot] has objectId < objectCount and meshletId
+ * < meshletCount, and tri = low & 0xFF is below the meshlet's triangle count: exactly the pixels chordvis_resolve_attributes writes.  A
+ * lattice pixel with low != 0 that does not contribute is REJECTED.  For a command, prim = ChordObject::GLTFPrimitiveDetail of its object
+ * as uploaded (the row of the descriptor's primitive array; chordvis_upload_scene refuses an object whose row is not below
+ * primitiveCount, so prim is always in range and is no part of the validity rule) and lod = min(ChordMeshlet::lod of its meshlet, CHORD_GEOMETRY_LODS - 1)
+ * (the reference's kNaniteMaxLODCount is 12).  A command i < n is SEEN when at least one contributing pixel of THIS call's lattice has
+ * slot == i; it is VALID when its objectId and meshletId are in range.  With stride > 1 "seen" means seen on the lattice: a cluster that
+ * covers only off-lattice pixels is missed.
+ * One chordvis_geometry_feedback call ADDS to the context's buffer (uint32, modulo 2^32: reset before a count can wrap):
+ *   objectPixels[o]      +1 per contributing pixel of object o          lodPixels[prim][lod]      +1 per contributing pixel of its command
+ *   objectSubmitted[o]   +1 per valid command i < n of object o         lodSubmitted[prim][lod]   +1 per valid command i < n
+ *   objectVisible[o]     +1 per seen command of object o                lodVisible[prim][lod]     +1 per seen command
+ *   totals[0..3]         lattice pixels looked at, contributing pixels, rejected pixels, seen commands
+ * so that sum(objectPixels) == sum(lodPixels) == totals[1], sum(objectVisible) == sum(lodVisible) == totals[3], objectVisible[o] <=
+ * objectSubmitted[o], and objectPixels[o] > 0 exactly when objectVisible[o] > 0.
+ * The seen bitmap has ceil(capacity / 32) words, bit i & 31 of word i >> 5 for command i.  It belongs to the LATEST call -- every call
+ * clears it first: slots are per-frame names, so it is not accumulated.
+ *   chordvis_geometry_feedback_reset     allocates the buffer on first use after a scene upload and zeroes it (counts and bitmap) on the
+ *                                        context's stream; the next chordvis_upload_scene and chordvis_destroy free it.
+ *   chordvis_geometry_feedback           one memset and two launches on the context's stream.  Preconditions, the wait for the image and
+ *                                        the treatment of a sharded context are chordvis_resolve_attributes' (a frame rendered; no
+ *                                        chordvis_update_objects / chordvis_set_view since; a rank of a sharded set-up counts the whole
+ *                                        resolved image).  Material textures are not needed.
+ *   chordvis_readback_geometry_feedback  synchronises and copies the arrays whose pointer is not NULL.
+ *   chordvis_visible_clusters            writes the seen commands of the latest chordvis_geometry_feedback call into caller-owned DEVICE
+ *                                        memory, IN LIST ORDER, records verbatim (`slot` keeps the original slot, so visibility ids still
+ *                                        resolve through the full list).  *deviceCount receives the number of seen commands even when
+ *                                        it exceeds `capacity`; nothing is written at or beyond `capacity` (deviceOut may be NULL when
+ *                                        capacity is 0).  The order is part of the contract and does not depend on scheduling.  Two
+ *                                        launches.  CHORDVIS_E_INVALID when no feedback call has run since the last reset or scene
+ *                                        upload, or when drawed.cmds is not the list the latest feedback call was given.  Only the
+ *                                        pointer is compared: the list (records and count word) must be UNCHANGED since that feedback
+ *                                        call.  The bitmap names slots of the list as it was then, so after a chordvis_render_frame or
+ *                                        a cull that refills the list, call chordvis_geometry_feedback again first; otherwise the
+ *                                        bits select whatever commands now sit in those slots.
+ *   chordvis_geometry_feedback_seen      synchronises and copies the bitmap (tests and tools).
+ * CHORDVIS_E_INVALID besides, chordvis_last_error naming the allowed values: no chordvis_geometry_feedback_reset since the scene
+ * upload; desc NULL; a stride other than 1, 2, 4 or 8; an offset not below the stride; pad not 0; read-back counts that differ from the
+ * uploaded scene's; a wordCount that is not ceil(capacity / 32). */
+#define CHORD_GEOMETRY_LODS 16u
+typedef struct ChordGeometryFeedbackDesc {
+    uint32_t stride;       /* 1, 2, 4 or 8 */
+    uint32_t offset[2];    /* each < stride */
+    uint32_t pad;          /* 0 */
+} ChordGeometryFeedbackDesc;
+typedef struct ChordGeometryFeedback {      /* HOST pointers, NULL = not wanted */
+    uint32_t *objectPixels, *objectSubmitted, *objectVisible;   /* objectCount each */
+    uint32_t *lodPixels, *lodSubmitted, *lodVisible;            /* primitiveCount x CHORD_GEOMETRY_LODS each */
+    uint32_t *totals;                                           /* 4 */
+} ChordGeometryFeedback;
+int chordvis_geometry_feedback_reset(ChordCtx* ctx);
+int chordvis_geometry_feedback(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordGeometryFeedbackDesc* desc);
+int chordvis_readback_geometry_feedback(ChordCtx* ctx, const ChordGeometryFeedback* out, uint32_t objectCount, uint32_t primitiveCount);
+int chordvis_visible_clusters(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, ChordDrawCmd* deviceOut, uint32_t* deviceCount, uint32_t capacity);
+int chordvis_geometry_feedback_seen(ChordCtx* ctx, uint32_t* hostWords, uint32_t wordCount);
 /* The G-buffer in the reference's packed image formats -- what exportGbuffer (lighting.hlsl:62-73) writes into GBufferTextures
  * (render_textures.h:27-49) and every later pass reads: 28 bytes per pixel for the six images, where the float images of
  * chordvis_resolve_material take 88.  The packing is pinned; float32, source order, unfused; R in the low bits:
@@ -881,7 +944,8 @@ int chordvis_stats(ChordCtx* ctx, ChordStats* out);
  * when the previous frame had a bin of 65536 entries or more), 524288 the library's own sharded frames (chordvis_comm_*, ChordGroup)
  * keep the replicated group cull instead of the sharded one (A / B measurements; every rank of a frame must agree), 4194304
  * chordvis_material_feedback's workgroups use 2 entries of their on-chip count tables instead of 512, so that most adds find
- * the table full and go to global memory (the same counts, slower). */
+ * the table full and go to global memory (the same counts, slower), 8388608 chordvis_geometry_feedback's workgroups likewise use
+ * 2 entries of their count tables instead of 1024. */
 int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 /* measurement / test aid: fills EVERY rank's chunk of the cull exchange buffer on this context for the current view (what the
  * all-gather would deliver), so that one rank of a sharded frame can be timed alone on one device (tools/shard_time.py) */
