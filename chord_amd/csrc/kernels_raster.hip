@@ -2484,6 +2484,14 @@ __device__ __forceinline__ void row_span(float e0, float e1, float e2, float t0,
     const float e[3] = {e0, e1, e2}, t[3] = {t0, t1, t2};
     span_bounds(e, t, n, [](float x) { return __builtin_amdgcn_rcpf(x); }, k0, k1);
 }
+// the same with the steps' reciprocals ready-made (entry_store: a triangle's three, once) and the int32 steps read for their signs only
+__device__ __forceinline__ void row_span_rcp(float e0, float e1, float e2, int32_t st0, int32_t st1, int32_t st2, float r0, float r1, float r2,
+                                             int32_t n, int32_t& k0, int32_t& k1)
+{
+    const float e[3] = {e0, e1, e2}, r[3] = {r0, r1, r2};
+    const int32_t t[3] = {st0, st1, st2};
+    span_bounds_rcp(e, t, r, n, k0, k1);
+}
 
 template <typename E_t>
 __device__ __forceinline__ void scan_row(unsigned long long* __restrict__ tileRow, const UnitParams& u, int32_t ox, int32_t py,
@@ -2572,7 +2580,28 @@ __device__ __forceinline__ uint32_t block_scan_tb(uint32_t v, uint32_t* waveSums
 #define MASKED_SEG_SHIFT 6
 #endif
 #define MASKED_SEG (1 << MASKED_SEG_SHIFT)
+// -DENTRY_RCP=1 (a measurement variant): the reciprocals of an int32 entry's three steps (the span bounds of every one of its rows
+// multiply by them) are made once, by entry_store, and ride in three more entry words.  Three words x 512 entries are 6 KB that two
+// workgroups per CU do not have beside the tile, so the unit list pays for them: with one segment per row a unit is
+// (entry | row << 9), 15 bits, and the list holds 16-bit words (8 KB, not 16).  Bit-exact and 0.4 % of the flagship frame (two spreads
+// of same-build runs), but one masked instantiation then spills a register: not in the product (profiles/r11_row_units.txt).
+#ifndef ENTRY_RCP
+#define ENTRY_RCP 0
+#endif
+// A row of 64 pixels is ONE segment: where the units of an entry are listed (list_units, a loop of one trip per row of the
+// entry's own thread) the segment count is the constant 1, not arithmetic on the box word with a compare and two selects per trip.
+// -DUNIT_NSEG_CONST=0 (a measurement variant) keeps the arithmetic.
+#ifndef UNIT_NSEG_CONST
+#define UNIT_NSEG_CONST 1
+#endif
+#if ENTRY_RCP
+static_assert(SEG_SHIFT == 6 && MASKED_SEG_SHIFT == 6, "a 16-bit unit has no segment bits: build other segment widths with -DENTRY_RCP=0 (32-bit list, 13 entry words)");
+typedef uint16_t unit_t;
+#define ENTRY_WORDS 16            // word 12: record index of a masked triangle (its extension follows it); 13 - 15: step reciprocals (kind 0)
+#else
+typedef uint32_t unit_t;
 #define ENTRY_WORDS 13            // word 12: record index of a masked triangle (its extension follows it)
+#endif
 // entries per batch of the tile kernel's triangle pipeline (the first TILE_BATCH threads fetch and set up one bin entry each) and units
 // per round of its unit list: 512 / 4096 = 26 + 16 KB of LDS beside the 33-KB tile = two workgroups per CU; 256 / 1536 = 13 + 6 KB =
 // three, if the registers allow it (TILE_MIN_BLOCKS 6: 80 VGPRs) -- a build switch, measured in profiles/r05_tile_kernel_experiments.txt
@@ -2610,13 +2639,17 @@ __device__ __forceinline__ int32_t scan_span(unsigned long long* __restrict__ ti
 }
 
 // int32 specialisation of the conversion (float)(double)E: exact for |E| < 2^31 either way, one instruction instead of two
+// RCP: r0 .. r2 are v_rcp_f32 of (float)st_i, ready-made (entry_store); otherwise they are not read and the bounds compute them
+template <bool RCP>
 __device__ __forceinline__ int32_t scan_span_i32(unsigned long long* __restrict__ tileRow, int32_t E0, int32_t E1, int32_t E2,
                                               int32_t st0, int32_t st1, int32_t st2, int32_t bias1, int32_t bias2,
                                               float d0, float e1, float e2, float invA, uint32_t payloadIn,
-                                              int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
+                                              int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ,
+                                              float r0, float r1, float r2)
 {
     int32_t k0, k1;
-    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
+    if (RCP) row_span_rcp((float)E0, (float)E1, (float)E2, st0, st1, st2, r0, r1, r2, lx1 - lx0, k0, k1);
+    else row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
     E0 += __mul24(k0, st0); E1 += __mul24(k0, st1); E2 += __mul24(k0, st2);     // |st| <= 2^22, 0 <= k0 <= 2^12: 24-bit operands
     // (Round 3: trimming the ~3 slack pixels that the bounds then had (floor(q) -+ 1) with exact edge tests before the loop --
     // 1.5 of a row's 5.6 two-pixel trips -- and predicating the merges instead of merging 0 were both measured: tile kernel
@@ -2629,6 +2662,9 @@ __device__ __forceinline__ int32_t scan_span_i32(unsigned long long* __restrict_
     // two pixels per trip.  The second may lie one past the bound: coverage is decided by the exact edge values, and
     // the word it would touch is at most the row's padding word (lx1 <= 63), a pixel right of the screen or a pixel of
     // the next segment of the same row (which merges the same value) -- never another row.
+    // (Round 11: the two pixels' l1, l2 and z as two-element vectors -- four v_pk_mul_f32 and two v_pk_add_f32 for the twelve scalar
+    // multiplies and adds, -4.4 % of the first pass's VALU instructions -- was timed and left the frame 0.6 % slower: a packed
+    // instruction issues at 2.7 cycles against 1.6 at four waves per SIMD; profiles/r11_row_units.txt.  Not kept, not even as a switch.)
     for (int32_t k = k0; k <= k1; k += 2) {
         const bool insideA = (E0 | E1 | E2) >= 0;
         const bool insideB = ((E0 + st0) | (E1 + st1) | (E2 + st2)) >= 0;
@@ -2670,6 +2706,12 @@ __device__ __forceinline__ uint32_t entry_store(EntrySoA& en, uint32_t t, const 
         en.w[4][t] = (uint32_t)(s * (__mul24(dx1, cy - ts.Y[2]) - __mul24(dy1, cx - ts.X[2])) + bias1);
         en.w[5][t] = (uint32_t)(s * (__mul24(dx2, cy - ts.Y[0]) - __mul24(dy2, cx - ts.X[0])) + bias2);
         box |= (bias1 ? 1u << 26 : 0u) | (bias2 ? 1u << 27 : 0u);
+#if ENTRY_RCP
+        // the reciprocals of the row loop's steps st_i = 256 a_i: the same instruction on the same float as row_span's, once per triangle
+        en.w[13][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a0 * 256)));
+        en.w[14][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a1 * 256)));
+        en.w[15][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a2 * 256)));
+#endif
     } else {
         int32_t mag = 0;
 #pragma unroll
@@ -2779,8 +2821,14 @@ __device__ __forceinline__ int32_t entry_unit(const RasterParams& p, const Entry
         const int32_t E0 = (int32_t)en.w[3][e] + (__mul24(a0, lx0) + __mul24(b0, ly)) * 256;
         const int32_t E1 = (int32_t)en.w[4][e] + (__mul24(a1, lx0) + __mul24(b1, ly)) * 256;
         const int32_t E2 = (int32_t)en.w[5][e] + (__mul24(a2, lx0) + __mul24(b2, ly)) * 256;
-        return scan_span_i32(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
-                             d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH);
+#if ENTRY_RCP
+        return scan_span_i32<true>(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
+                                   d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH,
+                                   __uint_as_float(en.w[13][e]), __uint_as_float(en.w[14][e]), __uint_as_float(en.w[15][e]));
+#else
+        return scan_span_i32<false>(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
+                                    d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH, 0.0f, 0.0f, 0.0f);
+#endif
     } else {
         UnitParams u;
         u.X[0] = (int32_t)en.w[0][e]; u.X[1] = (int32_t)en.w[1][e]; u.X[2] = (int32_t)en.w[2][e];
@@ -3131,8 +3179,9 @@ template <bool SH, bool MASKED, bool DEPTH>
 __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(RasterParams p)
 {
     __shared__ __align__(16) unsigned long long tile[TILE * TPITCH];   // 32.5 KB
-    __shared__ EntrySoA prm;                                     // 26 KB: the batch's entries that need row units
-    __shared__ uint32_t unitList[TILE_UNIT_CAP];                      // 16 KB: (entry | row << 9 | segment << 15) of the units of a round
+    __shared__ EntrySoA prm;                                     // 26 KB (ENTRY_RCP: 32): the batch's entries that need row units
+    __shared__ unit_t unitList[TILE_UNIT_CAP];                        // 16 KB: (entry | row << 9 | segment << 15) of the units of a round (ENTRY_RCP: 8 KB, no segment)
+    static_assert(sizeof(tile) + sizeof(EntrySoA) + sizeof(unitList) + 512 <= 81920, "two workgroups per CU need at most 80 KB of LDS each (512: the small arrays below)");
     __shared__ uint32_t offs[16];                                // (scratch of the tile-out reduction)
     __shared__ uint32_t waveSums[2][TB / 64];
     __shared__ uint32_t chunkTab[64];                            // the overflow chunks this item's entries live in
@@ -3442,14 +3491,14 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
         auto list_units = [&](uint32_t off, uint32_t n, uint32_t r0) {
             if (!n) return;
             const uint32_t box = prm.w[11][tix];
-            const uint32_t nseg = ((((box >> 12) & 63u) - (box & 63u)) >> SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
+            const uint32_t nseg = (UNIT_NSEG_CONST && SEG_SHIFT == 6) ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
             const uint32_t lo2 = max(off, r0), hi2 = min(off + n, r0 + TILE_UNIT_CAP);
             if (lo2 < hi2) {
                 uint32_t j = lo2 - off;
                 uint32_t row = y0l + (nseg == 1u ? j : nseg == 2u ? j >> 1 : nseg == 4u ? j >> 2 : j / 3u);
                 uint32_t seg = nseg == 1u ? 0u : nseg == 2u ? (j & 1u) : nseg == 4u ? (j & 3u) : j % 3u;
                 for (uint32_t u = lo2; u < hi2; u++) {
-                    unitList[u - r0] = tix | (row << 9) | (seg << 15);
+                    unitList[u - r0] = (unit_t)(tix | (row << 9) | (seg << 15));
                     if (++seg == nseg) { seg = 0u; row++; }
                 }
             }
@@ -3471,13 +3520,13 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
         for (uint32_t r0 = 0; r0 < totalM; r0 += TILE_UNIT_CAP) {      // (MASKED only) the alpha-tested triangles' units
             if (rowsM) {
                 const uint32_t box = prm.w[11][tix];
-                const uint32_t nseg = ((((box >> 12) & 63u) - (box & 63u)) >> MASKED_SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
+                const uint32_t nseg = (UNIT_NSEG_CONST && MASKED_SEG_SHIFT == 6) ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> MASKED_SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
                 const uint32_t lo2 = max(offM, r0), hi2 = min(offM + rowsM, r0 + TILE_UNIT_CAP);
                 if (lo2 < hi2) {
                     const uint32_t j = lo2 - offM, g = j / nseg;
                     uint32_t row = y0l + g * MASKED_ROWS, seg = j - g * nseg;
                     for (uint32_t u = lo2; u < hi2; u++) {
-                        unitList[u - r0] = tix | (row << 9) | (seg << 15);
+                        unitList[u - r0] = (unit_t)(tix | (row << 9) | (seg << 15));
                         if (++seg == nseg) { seg = 0u; row += MASKED_ROWS; }
                     }
                 }

@@ -33,6 +33,20 @@
 // way a finite value that no branch reads.
 //
 // -DSPAN_SLACK_LEGACY=1 (a measurement variant, build switch only) returns the earlier bounds floor(q) - 1 / floor(q) + 1.
+//
+// The form of the code.  The three cases of an edge (st > 0, st < 0, st == 0 and outside) are an if / else-if ladder; the lanes
+// of a wave hold different edges with different signs, so a wave runs every arm anyway and pays the exec-mask bookkeeping of three
+// nested ladders on top.  -DSPAN_STRAIGHT=1 (a measurement variant) compiles the same values as selects:
+//     klo = max(klo, st > 0 ? ceil(q - delta) : 0)                       0 is neutral: klo starts at 0 and only grows
+//     khi = st == 0 && E < 0 ? -1 : min(khi, st < 0 ? floor(q + delta) : SPAN_NONE)     SPAN_NONE is above every khi
+// (the constant-and-outside case ASSIGNS -1 as the ladder does; it does not take the minimum: an earlier edge may have left khi at
+// -4, and k1 is the ladder's for every input; tests/span_bounds_equal_main.cpp holds a copy of the ladder and compares).  The tile
+// kernel then issues 75 scalar instructions and 13 branches fewer (static), 14 vector ones and 10 registers more, and its frame
+// is 0.4 % SLOWER on the flagship workload (profiles/r11_row_units.txt): the ladder is the product.
+//
+// Two entrances, one body.  span_bounds() computes the three reciprocals with the reciprocal it is given; span_bounds_rcp() takes
+// them ready-made (the tile kernel stores a triangle's three with its batch entry: they belong to the triangle, not to the row)
+// and wants of the steps only their signs, so it takes them in any arithmetic type -- the int32 steps as they are, unconverted.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -40,7 +54,11 @@
 #ifndef SPAN_SLACK_LEGACY
 #define SPAN_SLACK_LEGACY 0
 #endif
+#ifndef SPAN_STRAIGHT
+#define SPAN_STRAIGHT 0
+#endif
 #define SPAN_DELTA 0.015625f        // 2^-6 px
+#define SPAN_NONE 8192.0f           // no bound: above n (<= 63) and above floor(4096 + delta)
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SPAN_HD __host__ __device__ __forceinline__
@@ -48,25 +66,41 @@
 #define SPAN_HD inline
 #endif
 
-// e[i], t[i]: the edge values at step 0 and the steps per pixel, converted to float; n: the row's last step; rcp: float -> float.
+// e[i]: the edge values at step 0, converted to float; t[i]: the steps per pixel (only their signs are read: float or integer);
+// r[i]: the reciprocals of the steps as floats; n: the row's last step.
 // Steps k0 .. k1 (k1 < k0: none) contain every covered step of 0 .. n.
-template <typename Rcp>
-SPAN_HD void span_bounds(const float (&e)[3], const float (&t)[3], int32_t n, Rcp rcp, int32_t& k0, int32_t& k1)
+template <typename Step>
+SPAN_HD void span_bounds_rcp(const float (&e)[3], const Step (&t)[3], const float (&r)[3], int32_t n, int32_t& k0, int32_t& k1)
 {
     float klo = 0.0f, khi = (float)n;
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #pragma unroll
 #endif
     for (int i = 0; i < 3; i++) {
-        const float q = fminf(fmaxf(-e[i] * rcp(t[i]), -4.0f), 4096.0f);                      // NaN (0 * inf) -> -4
+        const float q = fminf(fmaxf(-e[i] * r[i], -4.0f), 4096.0f);                           // NaN (0 * inf) -> -4
 #if SPAN_SLACK_LEGACY
-        if (t[i] > 0.0f) klo = fmaxf(klo, floorf(q) - 1.0f);
-        else if (t[i] < 0.0f) khi = fminf(khi, floorf(q) + 1.0f);
+        const float lo = floorf(q) - 1.0f, hi = floorf(q) + 1.0f;
 #else
-        if (t[i] > 0.0f) klo = fmaxf(klo, ceilf(q - SPAN_DELTA));
-        else if (t[i] < 0.0f) khi = fminf(khi, floorf(q + SPAN_DELTA));
+        const float lo = ceilf(q - SPAN_DELTA), hi = floorf(q + SPAN_DELTA);
 #endif
+#if SPAN_STRAIGHT
+        const bool pos = t[i] > (Step)0, neg = t[i] < (Step)0;
+        const bool out = !pos && !neg && e[i] < 0.0f;                                          // constant and outside
+        klo = fmaxf(klo, pos ? lo : 0.0f);
+        khi = out ? -1.0f : fminf(khi, neg ? hi : SPAN_NONE);
+#else
+        if (t[i] > (Step)0) klo = fmaxf(klo, lo);
+        else if (t[i] < (Step)0) khi = fminf(khi, hi);
         else if (e[i] < 0.0f) khi = -1.0f;                                                     // constant and outside
+#endif
     }
     k0 = (int32_t)klo; k1 = (int32_t)khi;
+}
+
+// e[i], t[i]: the edge values at step 0 and the steps per pixel, converted to float; n: the row's last step; rcp: float -> float.
+template <typename Rcp>
+SPAN_HD void span_bounds(const float (&e)[3], const float (&t)[3], int32_t n, Rcp rcp, int32_t& k0, int32_t& k1)
+{
+    const float r[3] = {rcp(t[0]), rcp(t[1]), rcp(t[2])};
+    span_bounds_rcp(e, t, r, n, k0, k1);
 }

@@ -16,10 +16,13 @@
 #define REP32(X) REP8(X) REP8(X) REP8(X) REP8(X)
 #define REP256(X) REP32(X) REP32(X) REP32(X) REP32(X) REP32(X) REP32(X) REP32(X) REP32(X)
 
-enum { ADD_U32, AND_B32, LSHL_ADD, MUL_F32, FMA_F32, MAD_U24, MUL_LO_U32, CVT_F32_I32, CNDMASK, RCP_F32, MIN_I32, ADD_F32_ALT, DEP_ADD_U32, DEP_FMA_F32, CMP_CNDMASK, NKINDS };
+enum { ADD_U32, AND_B32, LSHL_ADD, MUL_F32, FMA_F32, MAD_U24, MUL_LO_U32, CVT_F32_I32, CNDMASK, RCP_F32, MIN_I32, ADD_F32_ALT, DEP_ADD_U32, DEP_FMA_F32, CMP_CNDMASK,
+       PK_MUL_F32, PK_ADD_F32, DEP_PK_MUL_F32, DEP_PK_ADD_F32, ADD_F32, DEP_MUL_F32, NKINDS };
 static const char* kNames[NKINDS] = {"v_add_u32", "v_and_b32", "v_lshl_add_u32", "v_mul_f32", "v_fma_f32", "v_mad_u32_u24", "v_mul_lo_u32",
                                      "v_cvt_f32_i32", "v_cndmask_b32 (vcc)", "v_rcp_f32", "v_min_i32", "v_add_f32 / v_add_u32 alternating",
-                                     "v_add_u32, ONE dependent chain", "v_fma_f32, ONE dependent chain", "v_cmp_lt_u32 + v_cndmask_b32 pairs"};
+                                     "v_add_u32, ONE dependent chain", "v_fma_f32, ONE dependent chain", "v_cmp_lt_u32 + v_cndmask_b32 pairs",
+                                     "v_pk_mul_f32", "v_pk_add_f32", "v_pk_mul_f32, ONE dependent chain", "v_pk_add_f32, ONE dependent chain",
+                                     "v_add_f32", "v_mul_f32, ONE dependent chain"};
 
 template <int KIND>
 __global__ __launch_bounds__(1024, 2) void k_issue(uint32_t loops, unsigned long long* out, uint32_t seed)
@@ -28,6 +31,16 @@ __global__ __launch_bounds__(1024, 2) void k_issue(uint32_t loops, unsigned long
 #pragma unroll
     for (int i = 0; i < 8; i++) r[i] = seed + threadIdx.x * 8u + i;
     const uint32_t c = seed | 3u;
+    // (packed fp32: a two-element vector lives in an even-aligned register pair; one v_pk_* instruction does the work of two scalar ones)
+    typedef float float2v __attribute__((ext_vector_type(2)));
+    // (only the packed kinds touch rp: the scalar rows keep the registers, prologue and epilogue they were first recorded with)
+    constexpr bool PACKED = KIND == PK_MUL_F32 || KIND == PK_ADD_F32 || KIND == DEP_PK_MUL_F32 || KIND == DEP_PK_ADD_F32;
+    float2v rp[8] = {};
+    if (PACKED) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) rp[i] = float2v{1.0f + (float)(threadIdx.x * 8u + i) * 0x1p-20f, 1.0f};
+    }
+    const float2v cp = {1.0f + (float)(seed & 255u) * 0x1p-23f, 1.0f};
     __syncthreads();
     const unsigned long long t0 = __builtin_readcyclecounter(), w0 = wall_clock64();
     for (uint32_t l = 0; l < loops; l++) {
@@ -45,6 +58,12 @@ __global__ __launch_bounds__(1024, 2) void k_issue(uint32_t loops, unsigned long
         else if (KIND == DEP_FMA_F32) asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(r[0]) : "v"(c)); \
         else if (KIND == CMP_CNDMASK) { if ((i) & 1) asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(r[i]) : "v"(c)); else asm volatile("v_cmp_lt_u32 vcc, %0, %1" : : "v"(r[i]), "v"(c) : "vcc"); } \
         else if (KIND == RCP_F32) asm volatile("v_rcp_f32 %0, %0" : "+v"(r[i])); \
+        else if (KIND == PK_MUL_F32) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(rp[i]) : "v"(cp)); \
+        else if (KIND == PK_ADD_F32) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(rp[i]) : "v"(cp)); \
+        else if (KIND == DEP_PK_MUL_F32) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(rp[0]) : "v"(cp)); \
+        else if (KIND == DEP_PK_ADD_F32) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(rp[0]) : "v"(cp)); \
+        else if (KIND == ADD_F32) asm volatile("v_add_f32 %0, %0, %1" : "+v"(r[i]) : "v"(c)); \
+        else if (KIND == DEP_MUL_F32) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(r[0]) : "v"(c)); \
         else if (KIND == MIN_I32) asm volatile("v_min_i32 %0, %0, %1" : "+v"(r[i]) : "v"(c)); \
         else if (KIND == ADD_F32_ALT) { if ((i) & 1) asm volatile("v_add_f32 %0, %0, %1" : "+v"(r[i]) : "v"(c)); else asm volatile("v_add_u32 %0, %0, %1" : "+v"(r[i]) : "v"(c)); }
         REP256(ONE)
@@ -53,7 +72,7 @@ __global__ __launch_bounds__(1024, 2) void k_issue(uint32_t loops, unsigned long
     const unsigned long long t1 = __builtin_readcyclecounter(), w1 = wall_clock64();
     uint32_t acc = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) acc ^= r[i];
+    for (int i = 0; i < 8; i++) acc ^= PACKED ? __float_as_uint(rp[i].x) ^ __float_as_uint(rp[i].y) : r[i];
     if ((threadIdx.x & 63u) == 0u) {
         const size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
         out[w * 3 + 0] = t1 - t0; out[w * 3 + 1] = w1 - w0; out[w * 3 + 2] = acc;
@@ -101,5 +120,8 @@ int main()
     run<MAD_U24>(s, dOut, cus, wallHz); run<CVT_F32_I32>(s, dOut, cus, wallHz); run<CNDMASK>(s, dOut, cus, wallHz);
     run<MUL_LO_U32>(s, dOut, cus, wallHz); run<RCP_F32>(s, dOut, cus, wallHz);
     run<DEP_ADD_U32>(s, dOut, cus, wallHz); run<DEP_FMA_F32>(s, dOut, cus, wallHz); run<CMP_CNDMASK>(s, dOut, cus, wallHz);
+    // packed fp32 beside the scalar instructions it replaces two of (the tile kernel's two-pixel depth)
+    run<ADD_F32>(s, dOut, cus, wallHz); run<PK_MUL_F32>(s, dOut, cus, wallHz); run<PK_ADD_F32>(s, dOut, cus, wallHz);
+    run<DEP_MUL_F32>(s, dOut, cus, wallHz); run<DEP_PK_MUL_F32>(s, dOut, cus, wallHz); run<DEP_PK_ADD_F32>(s, dOut, cus, wallHz);
     return 0;
 }
