@@ -613,8 +613,7 @@ __device__ __forceinline__ AlphaLevel alpha_level(const uint8_t* __restrict__ te
 __device__ __forceinline__ float sample_alpha(const AlphaLevel& t, float u, float v)
 {
     if (!t.base) return 1.0f;
-    if (EXP_MASKED & 1) return 1.0f;
-    if (!t.linear || (EXP_MASKED & 2)) {
+    if (!t.linear) {
         const int32_t ix = wrap_index(texel_floor(u * t.fW), t.W, t.wrapS, t.magicS, t.biasS), iy = wrap_index(texel_floor(v * t.fH), t.H, t.wrapT, t.magicT, t.biasT);
         return (float)t.base[iy * t.W + ix] * (1.0f / 255.0f);
     }
@@ -2442,7 +2441,7 @@ __device__ __forceinline__ void tile_raster_narrow(unsigned long long* tile, con
 
 // ---- row units ------------------------------------------------------------------------------
 // Triangles are not equal: a tile may hold thousands of 1-pixel triangles or a few that cover it
-// completely.  Each batch of 256 bin entries is therefore cut into (triangle, pixel row) units; a
+// completely.  Each batch of 512 bin entries is therefore cut into (triangle, pixel row) units; a
 // block-wide prefix sum over the row counts hands every thread one row at a time, so a lane's loop
 // length is one row span (<= 64 pixels) instead of one bbox area (<= 4096).  Tiny triangles (clipped
 // bbox <= TINY_AREA / TINY_AREA_DENSE pixels) are scanned directly by the thread that set them up.
@@ -2452,6 +2451,7 @@ __device__ __forceinline__ void tile_raster_narrow(unsigned long long* tile, con
 //   kind 1  double  |coordinates| < 2^25 sub-pixels: every product and sum below 2^53, so fp64 is exact
 //                   and v_cvt_f32_f64 IS the canonical (float)(double)E
 //   kind 2  int64   anything else (guard-band monsters)
+//   kind 3  a masked (alpha-tested) triangle: int32 or int64 by its extent (masked_rows)
 // The threshold follows the tile: where a bin is long (>= TINY_DENSE_MIN entries: distant instances, a triangle or two per
 // pixel) nearly everything is small and a lane's own loop of up to 48 pixels beats a unit list that is mostly one- and two-row
 // triangles; where it is short the triangles are larger and more varied, and 8 keeps the lanes of a wave alike.  Measured
@@ -2471,7 +2471,6 @@ struct UnitParams {           // one batch entry, as the row loop wants it
     int32_t X[3], Y[3];
     float d0, e1, e2, invA;
     uint32_t payload;
-    uint32_t box;             // x0 | y0 << 8 | x1 << 16 | y1 << 24, tile-local
     int32_t skind;            // s in bit 0 (1 = negative), kind << 1
 };
 #define TB 512                  // threads per tile workgroup = entries per batch
@@ -2483,14 +2482,6 @@ __device__ __forceinline__ void row_span(float e0, float e1, float e2, float t0,
 {
     const float e[3] = {e0, e1, e2}, t[3] = {t0, t1, t2};
     span_bounds(e, t, n, [](float x) { return __builtin_amdgcn_rcpf(x); }, k0, k1);
-}
-// the same with the steps' reciprocals ready-made (entry_store: a triangle's three, once) and the int32 steps read for their signs only
-__device__ __forceinline__ void row_span_rcp(float e0, float e1, float e2, int32_t st0, int32_t st1, int32_t st2, float r0, float r1, float r2,
-                                             int32_t n, int32_t& k0, int32_t& k1)
-{
-    const float e[3] = {e0, e1, e2}, r[3] = {r0, r1, r2};
-    const int32_t t[3] = {st0, st1, st2};
-    span_bounds_rcp(e, t, r, n, k0, k1);
 }
 
 template <typename E_t>
@@ -2559,97 +2550,48 @@ __device__ __forceinline__ uint32_t block_scan_tb(uint32_t v, uint32_t* waveSums
 // then costs two multiply-adds per edge instead of re-deriving deltas, orientation, biases and the 24.8 products
 // (about 50 of the ~135 instructions a unit spent before its first pixel).  All values are exact 32-bit integers:
 // |a|, |b| <= 2^14 and a pixel of the tile is at most 2^15 + 128 sub-pixels from a vertex, so |E| < 2^31.
-// Rows wider than SEG pixels are cut into SEG-pixel segments, one unit each: a wave's row loops are at most SEG trips
-// long whatever mix of triangles the tile holds (62 % of the lanes were active in round 1), and a tile covered by a few
-// huge triangles becomes hundreds of units instead of 64.
 // Wide triangles (kind 1: fp64 edges, kind 2: int64) keep their vertices and derive the edges per unit as before.
+// A unit is one pixel row of one entry, of opaque and of masked (alpha-tested) triangles alike.  The unit word, the listing and the
+// decode keep a segment of SEG pixels of the row (SEG_SHIFT, MASKED_SEG_SHIFT); SEG is the tile's width, so a row is ONE segment and
+// the segment ALWAYS 0: where an entry's units are listed the count is the constant 1, not arithmetic on the box word.
 #ifndef SEG_SHIFT
-#define SEG_SHIFT 6             // 64: one unit per row (16 / 32 were measured 3 % / 1 % slower on config 3: more units, same trips)
+#define SEG_SHIFT 6             // 64: one unit per row
 #endif
 #define SEG (1 << SEG_SHIFT)
-// Units of masked (alpha-tested) triangles: MASKED_ROWS pixel rows x segments of MASKED_SEG pixels, one pixel
-// per trip of the row loop.  Measured on street_4k_masked (profiles/r04_masked_variants.txt; tile kernel per frame): one row x 64
-// px x 1 pixel per trip 418 us; segments of 32 / 16 / 8 px 419 / 421 / 498 (and no different once a unit's set-up is one round
-// trip); two pixels per trip (taps of both in flight) 488: the masked instantiation sits at 128 VGPRs with scratch, more live taps
-// move spills into the loop; 16 rows per unit 1 012.  By removal (-DEXP_MASKED): of the pass's ~250 us the bilinear taps are 80,
-// the remainders of non-power-of-two sizes were 45 (period_mod recovered 30), the two divisions 5.
-#ifndef MASKED_ROWS
-#define MASKED_ROWS 1
-#endif
 #ifndef MASKED_SEG_SHIFT
 #define MASKED_SEG_SHIFT 6
 #endif
 #define MASKED_SEG (1 << MASKED_SEG_SHIFT)
-// -DENTRY_RCP=1 (a measurement variant): the reciprocals of an int32 entry's three steps (the span bounds of every one of its rows
-// multiply by them) are made once, by entry_store, and ride in three more entry words.  Three words x 512 entries are 6 KB that two
-// workgroups per CU do not have beside the tile, so the unit list pays for them: with one segment per row a unit is
-// (entry | row << 9), 15 bits, and the list holds 16-bit words (8 KB, not 16).  Bit-exact and 0.4 % of the flagship frame (two spreads
-// of same-build runs), but one masked instantiation then spills a register: not in the product (profiles/r11_row_units.txt).
-#ifndef ENTRY_RCP
-#define ENTRY_RCP 0
-#endif
-// A row of 64 pixels is ONE segment: where the units of an entry are listed (list_units, a loop of one trip per row of the
-// entry's own thread) the segment count is the constant 1, not arithmetic on the box word with a compare and two selects per trip.
-// -DUNIT_NSEG_CONST=0 (a measurement variant) keeps the arithmetic.
-#ifndef UNIT_NSEG_CONST
-#define UNIT_NSEG_CONST 1
-#endif
-#if ENTRY_RCP
-static_assert(SEG_SHIFT == 6 && MASKED_SEG_SHIFT == 6, "a 16-bit unit has no segment bits: build other segment widths with -DENTRY_RCP=0 (32-bit list, 13 entry words)");
-typedef uint16_t unit_t;
-#define ENTRY_WORDS 16            // word 12: record index of a masked triangle (its extension follows it); 13 - 15: step reciprocals (kind 0)
-#else
-typedef uint32_t unit_t;
+// A batch is TB bin entries, one per thread, and a round of its unit list UNIT_CAP units: 26 + 16 KB of LDS beside the 33-KB tile = two
+// workgroups per CU.
+// Measured and rejected; the code of each is in the history at commit bb3c4eb:
+//  * rows cut into segments of 16 / 32 pixels, one unit each (-DSEG_SHIFT=4 / 5): 3 % / 1 % slower on config 3, more units for the same
+//    trips (round 3); masked segments of 32 / 16 / 8 px: tile kernel 419 / 421 / 498 us against 418 on street_4k_masked
+//    (profiles/r04_masked_variants.txt).
+//  * the segment count worked out from the box word where units are listed (-DUNIT_NSEG_CONST=0): a compare and two selects per trip
+//    of a serial loop, 3 % of the flagship frame (profiles/r11_row_units.txt).
+//  * units of 16 rows of a masked triangle (-DMASKED_ROWS=16), its set-up paid once per group: 1 012 us against 418; two pixels per
+//    trip 488: the masked instantiations sit at 128 VGPRs, more live taps move spills into the loop (profiles/r04_masked_variants.txt).
+//  * an entry's three step reciprocals made once by entry_store, in three more entry words beside a 16-bit unit list (-DENTRY_RCP=1):
+//    bit-exact and 0.4 % of the flagship frame, but one masked instantiation spills a register (profiles/r11_row_units.txt).
+//  * three workgroups per CU, batches of 256 entries and rounds of 1 536 units at 80 VGPRs (-DTILE_BATCH=256 -DTILE_UNIT_CAP=1536
+//    -DTILE_MIN_BLOCKS=6): +5 % on config 3, +26 % on config 4, +71 % masked (profiles/r05_tile_kernel_experiments.txt).
+//  * the masked pass with parts removed, to see what each costs (-DEXP_MASKED, results differ): of its ~250 us the bilinear taps are 80,
+//    the remainders of non-power-of-two sizes were 45 (period_mod recovered 30), the two divisions 5 (profiles/r04_masked_variants.txt).
 #define ENTRY_WORDS 13            // word 12: record index of a masked triangle (its extension follows it)
-#endif
-// entries per batch of the tile kernel's triangle pipeline (the first TILE_BATCH threads fetch and set up one bin entry each) and units
-// per round of its unit list: 512 / 4096 = 26 + 16 KB of LDS beside the 33-KB tile = two workgroups per CU; 256 / 1536 = 13 + 6 KB =
-// three, if the registers allow it (TILE_MIN_BLOCKS 6: 80 VGPRs) -- a build switch, measured in profiles/r05_tile_kernel_experiments.txt
-#ifndef TILE_BATCH
-#define TILE_BATCH TB
-#endif
-#ifndef TILE_UNIT_CAP
-#define TILE_UNIT_CAP UNIT_CAP
-#endif
-struct EntrySoA { uint32_t w[ENTRY_WORDS][TILE_BATCH]; };
+struct EntrySoA { uint32_t w[ENTRY_WORDS][TB]; };
 #define EF_KIND_SHIFT 24          // box word: x0 | y0 << 6 | x1 << 12 | y1 << 18 | kind << 24 | bias1 << 26 | bias2 << 27 | sneg << 28
 
-template <typename E_t>
-__device__ __forceinline__ int32_t scan_span(unsigned long long* __restrict__ tileRow, E_t E0, E_t E1, E_t E2, E_t st0, E_t st1, E_t st2,
-                                          E_t bias1, E_t bias2, float d0, float e1, float e2, float invA, uint32_t payloadIn,
-                                          int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ = false)
-{
-    // Span of the row in steps k from lx0 (see scan_row): fp32 estimates only BOUND the loop, coverage is exact inside.
-    int32_t k0, k1;
-    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
-    E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
-    unsigned long long* px = tileRow + lx0 + k0;
-    const unsigned long long payload = noPixels ? 0ull : (unsigned long long)payloadIn;
-    for (int32_t k = k0; k <= k1; k++) {
-        const bool inside = std::is_floating_point<E_t>::value ? (E0 >= (E_t)0 && E1 >= (E_t)0 && E2 >= (E_t)0)
-                                                              : (((int64_t)E0 | (int64_t)E1 | (int64_t)E2) >= 0);
-        const float l1 = (float)(double)(E1 - bias1) * invA, l2 = (float)(double)(E2 - bias2) * invA;
-        float z = (d0 + l1 * e1) + l2 * e2;
-        if (clampZ) z = fminf(fmaxf(z, 0.0f), 1.0f);
-        const unsigned long long packed = ((unsigned long long)__float_as_uint(z) << 32) | payload;
-        atomicMax(px, inside && !noPixels ? packed : 0ull);      // ds_max_u64
-        E0 += st0; E1 += st1; E2 += st2; px++;
-    }
-    return max(k1 - k0 + 1, 0);
-}
-
-// int32 specialisation of the conversion (float)(double)E: exact for |E| < 2^31 either way, one instruction instead of two
-// RCP: r0 .. r2 are v_rcp_f32 of (float)st_i, ready-made (entry_store); otherwise they are not read and the bounds compute them
-template <bool RCP>
+// One row of an entry with stored edge constants (kind 0), two pixels per trip; returns the loop's steps.  The int32 form of scan_row:
+// the canonical (float)(double)E is (float)E for |E| < 2^31, one instruction instead of two.
+// Span of the row in steps k from lx0 (see scan_row): fp32 estimates only BOUND the loop, coverage is exact inside.
 __device__ __forceinline__ int32_t scan_span_i32(unsigned long long* __restrict__ tileRow, int32_t E0, int32_t E1, int32_t E2,
                                               int32_t st0, int32_t st1, int32_t st2, int32_t bias1, int32_t bias2,
                                               float d0, float e1, float e2, float invA, uint32_t payloadIn,
-                                              int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ,
-                                              float r0, float r1, float r2)
+                                              int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
 {
     int32_t k0, k1;
-    if (RCP) row_span_rcp((float)E0, (float)E1, (float)E2, st0, st1, st2, r0, r1, r2, lx1 - lx0, k0, k1);
-    else row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
+    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
     E0 += __mul24(k0, st0); E1 += __mul24(k0, st1); E2 += __mul24(k0, st2);     // |st| <= 2^22, 0 <= k0 <= 2^12: 24-bit operands
     // (Round 3: trimming the ~3 slack pixels that the bounds then had (floor(q) -+ 1) with exact edge tests before the loop --
     // 1.5 of a row's 5.6 two-pixel trips -- and predicating the merges instead of merging 0 were both measured: tile kernel
@@ -2685,7 +2627,7 @@ __device__ __forceinline__ uint32_t entry_store(EntrySoA& en, uint32_t t, const 
                                                 int32_t ox, int32_t oy, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                                                 bool masked = false, uint32_t recIndex = 0u)
 {
-    const bool maskedNarrow = masked && narrow;                   // (bit 29 of the box word: masked_row may use 32-bit edge functions)
+    const bool maskedNarrow = masked && narrow;                   // (bit 29 of the box word: masked_rows may use 32-bit edge functions)
     narrow = narrow && !masked;                                   // masked triangles keep their vertices (kind 3)
     uint32_t box = (uint32_t)(x0 - ox) | ((uint32_t)(y0 - oy) << 6) | ((uint32_t)(x1 - ox) << 12) | ((uint32_t)(y1 - oy) << 18);
     if (narrow) {
@@ -2706,12 +2648,6 @@ __device__ __forceinline__ uint32_t entry_store(EntrySoA& en, uint32_t t, const 
         en.w[4][t] = (uint32_t)(s * (__mul24(dx1, cy - ts.Y[2]) - __mul24(dy1, cx - ts.X[2])) + bias1);
         en.w[5][t] = (uint32_t)(s * (__mul24(dx2, cy - ts.Y[0]) - __mul24(dy2, cx - ts.X[0])) + bias2);
         box |= (bias1 ? 1u << 26 : 0u) | (bias2 ? 1u << 27 : 0u);
-#if ENTRY_RCP
-        // the reciprocals of the row loop's steps st_i = 256 a_i: the same instruction on the same float as row_span's, once per triangle
-        en.w[13][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a0 * 256)));
-        en.w[14][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a1 * 256)));
-        en.w[15][t] = __float_as_uint(__builtin_amdgcn_rcpf((float)(a2 * 256)));
-#endif
     } else {
         int32_t mag = 0;
 #pragma unroll
@@ -2725,22 +2661,26 @@ __device__ __forceinline__ uint32_t entry_store(EntrySoA& en, uint32_t t, const 
     }
     en.w[6][t] = __float_as_uint(ts.d0); en.w[7][t] = __float_as_uint(ts.e1); en.w[8][t] = __float_as_uint(ts.e2);
     en.w[9][t] = __float_as_uint(ts.invA); en.w[10][t] = ts.payload; en.w[11][t] = box;
-    // units: one per (row, segment); a masked triangle's are groups of MASKED_ROWS rows (masked_rows)
-    if (masked) return ((uint32_t)(y1 - y0) / MASKED_ROWS + 1u) * ((uint32_t)((x1 - x0) >> MASKED_SEG_SHIFT) + 1u);
+    // units: one per (row, segment)
+    if (masked) return ((uint32_t)(y1 - y0) + 1u) * ((uint32_t)((x1 - x0) >> MASKED_SEG_SHIFT) + 1u);
     return (uint32_t)(y1 - y0 + 1) * ((uint32_t)((x1 - x0) >> SEG_SHIFT) + 1u);
 }
 
-// A pixel row of a masked triangle: exact int64 edges, canonical depth, and per covered pixel the perspective-correct
+// The pixel rows of one unit of a masked triangle: exact integer edges, canonical depth, and per covered pixel the perspective-correct
 // texture coordinates, one alpha fetch and the clip() of mesh_raster.hlsl:198-204.
 // E_t: int32_t for triangles whose vertices are at most 64 px apart (|E| < 2^31, as in scan_span_i32; (float)E is then the
-// canonical (float)(double)E), int64_t for the rest.  The span of the row is bounded first (row_span, the same bounds as
-// scan_span's), so the loop runs over the covered pixels, not over the bbox row; a step outside the triangle skips the taps.
-// (A unit of a masked triangle is a GROUP of up to MASKED_ROWS pixel rows, not one: what a unit pays before its first pixel --
-// the triangle's extension record, its material, the texture level, the edge constants: three dependent memory round trips --
-// is then paid once per small triangle instead of once per row.)
+// canonical (float)(double)E), int64_t for the rest.  The span of a row is bounded first (row_span, the same bounds as
+// scan_row's), so the loop runs over the covered pixels, not over the bbox row; a step outside the triangle skips the taps.
+// A unit is ONE row: every caller passes nrows = 1 (units of 16 rows were measured and rejected, see above), and what a unit pays
+// before its first pixel -- the triangle's extension record, its texture level, the edge set-up -- it pays per row.  The row loop and
+// the per-row steps sy0 .. sy2 are dead at one row and their spelling is deliberate: the compiler removes them, but not before they
+// have shaped the code -- with b_i used a second time it writes the top-left rule of the biases as selects, without it as a branch,
+// and the three masked instantiations come out differently (profiles/r12_row_unit_cleanup.txt).  The same holds for the edge set-up
+// that this function repeats from scan_row: moved into one function, all six instantiations change.  Both are instruction-stream
+// changes for a pull request that measures them.
 template <typename E_t>
 __device__ __forceinline__ void masked_rows(const RasterParams& p, unsigned long long* __restrict__ tileRow0, const UnitParams& u, uint32_t recIndex,
-                                         int32_t ox, int32_t py0, int32_t nrows, int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
+                                            int32_t ox, int32_t py0, int32_t nrows, int32_t lx0, int32_t lx1, bool noPixels, const bool clampZ)
 {
     // (60 bytes of the extension, one round trip: nothing here depends on another fetch)
     const TriRecMaskExt ext = *reinterpret_cast<const TriRecMaskExt*>(&p.tris[recIndex + 1u]);
@@ -2761,51 +2701,50 @@ __device__ __forceinline__ void masked_rows(const RasterParams& p, unsigned long
     const E_t st0 = a0 * (E_t)256, st1 = a1 * (E_t)256, st2 = a2 * (E_t)256;
     const E_t sy0 = b0 * (E_t)256, sy1 = b1 * (E_t)256, sy2 = b2 * (E_t)256;           // one row down
     for (int32_t r = 0; r < nrows; r++, R0 += sy0, R1 += sy1, R2 += sy2) {
-    E_t E0 = R0, E1 = R1, E2 = R2;
-    unsigned long long* __restrict__ tileRow = tileRow0 + r * TPITCH;
-    int32_t k0, k1;
-    row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
-    E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
-    // the packed word of the pixel with these (biased) edge values, 0 when it is outside or its alpha fails the cut-off.  No branch:
-    // a pixel outside the triangle evaluates its texture coordinates anyway (whatever they are, texel_floor / wrap_index give an
-    // index inside the level), so that the taps of both pixels of a trip are in flight together -- the loop is bound by the latency
-    // of its dependent byte loads, one round trip per covered pixel before.
-    auto pixel = [&](E_t e0, E_t e1, E_t e2) -> unsigned long long {
-        const bool inside = (e0 | e1 | e2) >= 0;
-        const float l1 = std::is_same<E_t, int32_t>::value ? (float)(e1 - bias1) * u.invA : (float)(double)(e1 - bias1) * u.invA;
-        const float l2 = std::is_same<E_t, int32_t>::value ? (float)(e2 - bias2) * u.invA : (float)(double)(e2 - bias2) * u.invA;
-        const float l0 = (1.0f - l1) - l2;
-        const float den = (l0 * ext.iw[0] + l1 * ext.iw[1]) + l2 * ext.iw[2];
-        float tu = (l0 * ext.uw[0] + l1 * ext.uw[1]) + l2 * ext.uw[2];
-        float tv = (l0 * ext.vw[0] + l1 * ext.vw[1]) + l2 * ext.vw[2];
-        if (EXP_MASKED & 8) {
-            float r = __builtin_amdgcn_rcpf(den);
-            r = __builtin_fmaf(__builtin_fmaf(-den, r, 1.0f), r, r);
-            float q = tu * r; q = __builtin_fmaf(__builtin_fmaf(-den, q, tu), r, q); tu = __builtin_fmaf(__builtin_fmaf(-den, q, tu), r, q);
-            q = tv * r; q = __builtin_fmaf(__builtin_fmaf(-den, q, tv), r, q); tv = __builtin_fmaf(__builtin_fmaf(-den, q, tv), r, q);
-        } else { tu = tu / den; tv = tv / den; }
-        const float alpha = sample_alpha(tex, tu, tv);
-        const bool keep = inside && !(alpha * m.alphaFactor - m.alphaCutOff < 0.0f) && !noPixels;      // clip()
-        float z = (u.d0 + l1 * u.e1) + l2 * u.e2;
-        if (clampZ) z = fminf(fmaxf(z, 0.0f), 1.0f);
-        return keep ? (((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)u.payload) : 0ull;
-    };
-    unsigned long long* px = tileRow + lx0 + k0;
-    for (int32_t k = k0; k <= k1; k++, E0 += st0, E1 += st1, E2 += st2, px++) {
-        if ((E0 | E1 | E2) < 0) continue;
-        atomicMax(px, pixel(E0, E1, E2));                                         // ds_max_u64 (0 changes nothing)
-    }
+        E_t E0 = R0, E1 = R1, E2 = R2;
+        unsigned long long* __restrict__ tileRow = tileRow0 + r * TPITCH;
+        int32_t k0, k1;
+        row_span((float)E0, (float)E1, (float)E2, (float)st0, (float)st1, (float)st2, lx1 - lx0, k0, k1);
+        E0 += (E_t)k0 * st0; E1 += (E_t)k0 * st1; E2 += (E_t)k0 * st2;
+        // the packed word of the pixel with these (biased) edge values, 0 when it is outside or its alpha fails the cut-off.  No branch:
+        // a pixel outside the triangle evaluates its texture coordinates anyway (whatever they are, texel_floor / wrap_index give an
+        // index inside the level), so that the taps of both pixels of a trip are in flight together -- the loop is bound by the latency
+        // of its dependent byte loads, one round trip per covered pixel before.
+        auto pixel = [&](E_t e0, E_t e1, E_t e2) -> unsigned long long {
+            const bool inside = (e0 | e1 | e2) >= 0;
+            const float l1 = std::is_same<E_t, int32_t>::value ? (float)(e1 - bias1) * u.invA : (float)(double)(e1 - bias1) * u.invA;
+            const float l2 = std::is_same<E_t, int32_t>::value ? (float)(e2 - bias2) * u.invA : (float)(double)(e2 - bias2) * u.invA;
+            const float l0 = (1.0f - l1) - l2;
+            const float den = (l0 * ext.iw[0] + l1 * ext.iw[1]) + l2 * ext.iw[2];
+            float tu = (l0 * ext.uw[0] + l1 * ext.uw[1]) + l2 * ext.uw[2];
+            float tv = (l0 * ext.vw[0] + l1 * ext.vw[1]) + l2 * ext.vw[2];
+            tu = tu / den; tv = tv / den;
+            const float alpha = sample_alpha(tex, tu, tv);
+            const bool keep = inside && !(alpha * m.alphaFactor - m.alphaCutOff < 0.0f) && !noPixels;      // clip()
+            float z = (u.d0 + l1 * u.e1) + l2 * u.e2;
+            if (clampZ) z = fminf(fmaxf(z, 0.0f), 1.0f);
+            return keep ? (((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)u.payload) : 0ull;
+        };
+        unsigned long long* px = tileRow + lx0 + k0;
+        for (int32_t k = k0; k <= k1; k++, E0 += st0, E1 += st1, E2 += st2, px++) {
+            if ((E0 | E1 | E2) < 0) continue;
+            atomicMax(px, pixel(E0, E1, E2));                                         // ds_max_u64 (0 changes nothing)
+        }
     }
 }
 
 // one unit = (entry e, its j-th (row, segment))
-template <bool MASKED, bool DEPTH>
-__device__ __forceinline__ int32_t entry_unit(const RasterParams& p, const EntrySoA& en, unsigned long long* tile, uint32_t e, uint32_t row, uint32_t seg,
+template <bool DEPTH>
+__device__ __forceinline__ int32_t entry_unit(const EntrySoA& en, unsigned long long* tile, uint32_t e, uint32_t row, uint32_t seg,
                                            int32_t ox, int32_t oy, bool noPixels)
 {
     const uint32_t box = en.w[11][e];
     const int32_t bx0 = (int32_t)(box & 63u), bx1 = (int32_t)((box >> 12) & 63u);
     const int32_t ly = (int32_t)row;
+    // (seg is always 0 -- SEG is the tile's width -- and the compiler cannot know it: it comes out of LDS.  The arithmetic stays: with
+    // the unit word (entry | row << 9), lx0 = bx0 and lx1 = bx1 the opaque instantiations hold 103 / 104 / 103 VGPRs for 105 / 106 /
+    // 105 and the file is shorter, but street_x64_4k_hzb ran 0.3 % SLOWER than the library of commit bb3c4eb in seven of eight interleaved
+    // pairs, 0.3837 against 0.3824 ms, tile kernel 168.4 against 167.0 us; profiles/r12_row_unit_cleanup.txt)
     const int32_t lx0 = bx0 + (int32_t)(seg << SEG_SHIFT), lx1 = min(bx1, lx0 + SEG - 1);
     unsigned long long* tileRow = tile + ly * TPITCH;
     const float d0 = __uint_as_float(en.w[6][e]), e1 = __uint_as_float(en.w[7][e]), e2 = __uint_as_float(en.w[8][e]);
@@ -2821,19 +2760,13 @@ __device__ __forceinline__ int32_t entry_unit(const RasterParams& p, const Entry
         const int32_t E0 = (int32_t)en.w[3][e] + (__mul24(a0, lx0) + __mul24(b0, ly)) * 256;
         const int32_t E1 = (int32_t)en.w[4][e] + (__mul24(a1, lx0) + __mul24(b1, ly)) * 256;
         const int32_t E2 = (int32_t)en.w[5][e] + (__mul24(a2, lx0) + __mul24(b2, ly)) * 256;
-#if ENTRY_RCP
-        return scan_span_i32<true>(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
-                                   d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH,
-                                   __uint_as_float(en.w[13][e]), __uint_as_float(en.w[14][e]), __uint_as_float(en.w[15][e]));
-#else
-        return scan_span_i32<false>(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
-                                    d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH, 0.0f, 0.0f, 0.0f);
-#endif
+        return scan_span_i32(tileRow, E0, E1, E2, a0 * 256, a1 * 256, a2 * 256, (box >> 26) & 1u ? -1 : 0, (box >> 27) & 1u ? -1 : 0,
+                             d0, e1, e2, invA, payload, lx0, lx1, noPixels, DEPTH);
     } else {
         UnitParams u;
         u.X[0] = (int32_t)en.w[0][e]; u.X[1] = (int32_t)en.w[1][e]; u.X[2] = (int32_t)en.w[2][e];
         u.Y[0] = (int32_t)en.w[3][e]; u.Y[1] = (int32_t)en.w[4][e]; u.Y[2] = (int32_t)en.w[5][e];
-        u.d0 = d0; u.e1 = e1; u.e2 = e2; u.invA = invA; u.payload = payload; u.box = 0;
+        u.d0 = d0; u.e1 = e1; u.e2 = e2; u.invA = invA; u.payload = payload;
         u.skind = (int32_t)((box >> 28) & 1u) | (int32_t)(kind << 1);
         if (kind == 1u)      scan_row<double>(tileRow, u, ox, oy + ly, lx0, lx1, noPixels, DEPTH);
         else if (kind == 2u) scan_row<int64_t>(tileRow, u, ox, oy + ly, lx0, lx1, noPixels, DEPTH);
@@ -2843,7 +2776,7 @@ __device__ __forceinline__ int32_t entry_unit(const RasterParams& p, const Entry
 }
 
 // The units of alpha-tested triangles (kind 3) are listed and scanned apart from the others (the block-wide scan counts both
-// kinds): the texture fetch of masked_row (level offsets, wrap modes, four taps, two divisions per pixel) inlined into the loop
+// kinds): the texture fetch of masked_rows (level offsets, wrap modes, four taps, two divisions per pixel) inlined into the loop
 // above put every masked instantiation of the tile kernel 37-54 VGPRs past its 128 -- 144-224 bytes of scratch per lane that
 // every unit of every triangle paid for, masked or not -- and in a list of their own the masked units fill whole waves instead
 // of a lane here and there.  A batch without masked entries skips the pass.
@@ -2852,17 +2785,17 @@ __device__ __forceinline__ void entry_unit_masked(const RasterParams& p, const E
                                                   int32_t ox, int32_t oy, bool noPixels)
 {
     const uint32_t box = en.w[11][e];
-    const int32_t bx0 = (int32_t)(box & 63u), bx1 = (int32_t)((box >> 12) & 63u), by1 = (int32_t)((box >> 18) & 63u);
-    const int32_t ly = (int32_t)row, nrows = MASKED_ROWS == 1 ? 1 : min(MASKED_ROWS, by1 - ly + 1);   // (row: the first row of the group)
-    const int32_t lx0 = bx0 + (int32_t)(seg << MASKED_SEG_SHIFT), lx1 = min(bx1, lx0 + MASKED_SEG - 1);
+    const int32_t bx0 = (int32_t)(box & 63u), bx1 = (int32_t)((box >> 12) & 63u);
+    const int32_t ly = (int32_t)row;
+    const int32_t lx0 = bx0 + (int32_t)(seg << MASKED_SEG_SHIFT), lx1 = min(bx1, lx0 + MASKED_SEG - 1);   // (seg: always 0, see entry_unit)
     UnitParams u;
     u.X[0] = (int32_t)en.w[0][e]; u.X[1] = (int32_t)en.w[1][e]; u.X[2] = (int32_t)en.w[2][e];
     u.Y[0] = (int32_t)en.w[3][e]; u.Y[1] = (int32_t)en.w[4][e]; u.Y[2] = (int32_t)en.w[5][e];
     u.d0 = __uint_as_float(en.w[6][e]); u.e1 = __uint_as_float(en.w[7][e]); u.e2 = __uint_as_float(en.w[8][e]);
-    u.invA = __uint_as_float(en.w[9][e]); u.payload = en.w[10][e]; u.box = 0;
+    u.invA = __uint_as_float(en.w[9][e]); u.payload = en.w[10][e];
     u.skind = (int32_t)((box >> 28) & 1u) | (3 << 1);
-    if ((box >> 29) & 1u) masked_rows<int32_t>(p, tile + ly * TPITCH, u, en.w[12][e], ox, oy + ly, nrows, lx0, lx1, noPixels, DEPTH);   // vertices at most 64 px apart
-    else                  masked_rows<int64_t>(p, tile + ly * TPITCH, u, en.w[12][e], ox, oy + ly, nrows, lx0, lx1, noPixels, DEPTH);
+    if ((box >> 29) & 1u) masked_rows<int32_t>(p, tile + ly * TPITCH, u, en.w[12][e], ox, oy + ly, 1, lx0, lx1, noPixels, DEPTH);   // vertices at most 64 px apart
+    else                  masked_rows<int64_t>(p, tile + ly * TPITCH, u, en.w[12][e], ox, oy + ly, 1, lx0, lx1, noPixels, DEPTH);
 }
 
 // Tile-out of a finished tile fused with its HZB reduction (single-GPU frames): every word goes to the visibility
@@ -3179,8 +3112,8 @@ template <bool SH, bool MASKED, bool DEPTH>
 __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(RasterParams p)
 {
     __shared__ __align__(16) unsigned long long tile[TILE * TPITCH];   // 32.5 KB
-    __shared__ EntrySoA prm;                                     // 26 KB (ENTRY_RCP: 32): the batch's entries that need row units
-    __shared__ unit_t unitList[TILE_UNIT_CAP];                        // 16 KB: (entry | row << 9 | segment << 15) of the units of a round (ENTRY_RCP: 8 KB, no segment)
+    __shared__ EntrySoA prm;                                     // 26 KB: the batch's entries that need row units
+    __shared__ uint32_t unitList[UNIT_CAP];                      // 16 KB: (entry | row << 9 | segment << 15) of the units of a round
     static_assert(sizeof(tile) + sizeof(EntrySoA) + sizeof(unitList) + 512 <= 81920, "two workgroups per CU need at most 80 KB of LDS each (512: the small arrays below)");
     __shared__ uint32_t offs[16];                                // (scratch of the tile-out reduction)
     __shared__ uint32_t waveSums[2][TB / 64];
@@ -3244,14 +3177,13 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     // (kept order: the tile's counter line is read here, and -- the address needs the tile only -- a whole tile's first bin entries
     // beside it, so that the chain item -> bin entry -> record does not grow by the round trip for the length)
     const uint32_t* bin = p.tileBins + (size_t)tileId * p.binCap;
-    const bool entryThread = TILE_BATCH == TB || tix < TILE_BATCH;   // (a batch is TILE_BATCH bin entries, one per thread of the first waves)
     uint32_t countWord = itemCount.y, wordSpec = 0xFFFFFFFFu;
     if (p.orderKept) {
         // (the bin words are asked for whatever the item is -- a slice's first entries are elsewhere and these are dropped --, and the
         // counter line with a SCALAR load (words 0 and 1: final since the binner ended; the kernel's own atomics touch word 2 only):
         // under `slices == 1`, and with the line in a vector register the allocator used again for the bin words' address, the compiler
         // put the fetch it was meant to travel beside behind the wait for the line -- a round trip in front of every tile)
-        if (entryThread) wordSpec = bin[tix];
+        wordSpec = bin[tix];
         const unsigned long long cnt = scalar_load(reinterpret_cast<const unsigned long long*>(&p.tileCount[(size_t)tileId * TC_STRIDE]));
         countWord = min((uint32_t)cnt, bin_capacity(p)) | ((uint32_t)(cnt >> 32) ? 0x80000000u : 0u);
     }
@@ -3304,7 +3236,7 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     // pool chunks name them through chunkTab, which is filled behind the barrier: they keep the old order.)
     const bool early = n <= p.binCap && !hasBlocks;               // (uniform)
     const uint32_t k0 = lo + tix;
-    const uint32_t word0 = (early && entryThread && k0 < n) ? ((p.orderKept && slices == 1u) ? wordSpec : bin[k0]) : 0xFFFFFFFFu;
+    const uint32_t word0 = (early && k0 < n) ? ((p.orderKept && slices == 1u) ? wordSpec : bin[k0]) : 0xFFFFFFFFu;
 
     // ---- tile in: zero (first pass: this is the clear; un-fused later passes merge by max at tile-out), or the
     //      current words when a later pass must leave the finished tile in LDS for the fused HZB reduction ----
@@ -3349,12 +3281,12 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
     if (early) {
         nameNext = record_name(word0);                                          // (binEntry of an entry of the fixed bin)
         if (nameNext != 0xFFFFFFFFu) FETCH_REC(nameNext, nq0, nq1, nq2);        // record of batch 0
-        if (entryThread && k0 + TILE_BATCH < n) idxNext = record_name(bin[k0 + TILE_BATCH]);   // bin entry of batch 1
+        if (k0 + TB < n) idxNext = record_name(bin[k0 + TB]);                    // bin entry of batch 1
     }
     __syncthreads();
     PHASE(0);
 
-    // ---- scan-convert the bin, 256 entries per batch -------------------------------------------
+    // ---- scan-convert the bin, 512 entries per batch -------------------------------------------
     // Software pipeline over the two dependent fetches of a batch (bin entry -> 48-byte record): the
     // record of batch b+1 and the bin entry of batch b+2 are in flight while batch b is scan-converted.
     // Overflow chunks the item's entries [lo, n) live in: a WINDOW of 64 chunk names in LDS (chunk c at chunkTab[c & 63], names of
@@ -3425,10 +3357,10 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
         return okIdx ? gi : 0xFFFFFFFFu;                       // (only after a reported overflow)
     };
     if (!early) {
-        idxNext = entryThread && k0 < n ? binEntry(k0) : 0xFFFFFFFFu;            // bin entry of batch 0
+        idxNext = k0 < n ? binEntry(k0) : 0xFFFFFFFFu;                           // bin entry of batch 0
         nameNext = idxNext;
         if (nameNext != 0xFFFFFFFFu) FETCH_REC(nameNext, nq0, nq1, nq2);         // record of batch 0
-        idxNext = entryThread && k0 + TILE_BATCH < n ? binEntry(k0 + TILE_BATCH) : 0xFFFFFFFFu;   // bin entry of batch 1
+        idxNext = k0 + TB < n ? binEntry(k0 + TB) : 0xFFFFFFFFu;                 // bin entry of batch 1
     }
     // One batch in two parts, so that the caller can re-load the record registers in between (by value: a record handed over by
     // reference ends up in scratch memory).  batch_setup: the records q0..q2 named `name` of the batch's entries (one per entry
@@ -3487,71 +3419,71 @@ __global__ __launch_bounds__(TB, TILE_MIN_BLOCKS) void raster_tile_kernel(Raster
         const uint32_t offN = offAll & 0xFFFFu, offM = offAll >> 16, totalM = MASKED ? total >> 16 : 0u;
         total &= 0xFFFFu;
         PHASE(3);
-        // my units [off, off + n) of a population, cut to the round's window [r0, r0 + TILE_UNIT_CAP): one LDS word each
+        // my units [off, off + n) of a population, cut to the round's window [r0, r0 + UNIT_CAP): one LDS word each
         auto list_units = [&](uint32_t off, uint32_t n, uint32_t r0) {
             if (!n) return;
             const uint32_t box = prm.w[11][tix];
-            const uint32_t nseg = (UNIT_NSEG_CONST && SEG_SHIFT == 6) ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
-            const uint32_t lo2 = max(off, r0), hi2 = min(off + n, r0 + TILE_UNIT_CAP);
+            const uint32_t nseg = SEG_SHIFT == 6 ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
+            const uint32_t lo2 = max(off, r0), hi2 = min(off + n, r0 + UNIT_CAP);
             if (lo2 < hi2) {
                 uint32_t j = lo2 - off;
                 uint32_t row = y0l + (nseg == 1u ? j : nseg == 2u ? j >> 1 : nseg == 4u ? j >> 2 : j / 3u);
                 uint32_t seg = nseg == 1u ? 0u : nseg == 2u ? (j & 1u) : nseg == 4u ? (j & 3u) : j % 3u;
                 for (uint32_t u = lo2; u < hi2; u++) {
-                    unitList[u - r0] = (unit_t)(tix | (row << 9) | (seg << 15));
+                    unitList[u - r0] = tix | (row << 9) | (seg << 15);
                     if (++seg == nseg) { seg = 0u; row++; }
                 }
             }
         };
-        // rounds of TILE_UNIT_CAP units: every entry thread lists its units of the round, then every thread takes units TB apart -- a
+        // rounds of UNIT_CAP units: every entry thread lists its units of the round, then every thread takes units TB apart -- a
         // unit finds its entry with ONE read instead of a 9-step binary search
-        for (uint32_t r0 = 0; r0 < total; r0 += TILE_UNIT_CAP) {
+        for (uint32_t r0 = 0; r0 < total; r0 += UNIT_CAP) {
             list_units(offN, rowsN, r0);
             __syncthreads();
-            const uint32_t nr = min(total - r0, (uint32_t)TILE_UNIT_CAP);
+            const uint32_t nr = min(total - r0, (uint32_t)UNIT_CAP);
             for (uint32_t ui = tix; ui < nr; ui += TB) {
                 const uint32_t d = unitList[ui];
                 if (ABL(p, DBG_NO_UNITS)) continue;
-                const int32_t trips = entry_unit<MASKED, DEPTH>(p, prm, tile, d & 511u, (d >> 9) & 63u, (d >> 15) & 3u, ox, oy, noPixels);
+                const int32_t trips = entry_unit<DEPTH>(prm, tile, d & 511u, (d >> 9) & 63u, (d >> 15) & 3u, ox, oy, noPixels);
                 if (prof) { cUnits++; cUnitIters += (uint32_t)trips; }
             }
-            if (r0 + TILE_UNIT_CAP < total || totalM) __syncthreads(); // the list is rewritten by the next round
+            if (r0 + UNIT_CAP < total || totalM) __syncthreads(); // the list is rewritten by the next round
         }
-        for (uint32_t r0 = 0; r0 < totalM; r0 += TILE_UNIT_CAP) {      // (MASKED only) the alpha-tested triangles' units
+        for (uint32_t r0 = 0; r0 < totalM; r0 += UNIT_CAP) {      // (MASKED only) the alpha-tested triangles' units
             if (rowsM) {
                 const uint32_t box = prm.w[11][tix];
-                const uint32_t nseg = (UNIT_NSEG_CONST && MASKED_SEG_SHIFT == 6) ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> MASKED_SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
-                const uint32_t lo2 = max(offM, r0), hi2 = min(offM + rowsM, r0 + TILE_UNIT_CAP);
+                const uint32_t nseg = MASKED_SEG_SHIFT == 6 ? 1u : ((((box >> 12) & 63u) - (box & 63u)) >> MASKED_SEG_SHIFT) + 1u, y0l = (box >> 6) & 63u;
+                const uint32_t lo2 = max(offM, r0), hi2 = min(offM + rowsM, r0 + UNIT_CAP);
                 if (lo2 < hi2) {
                     const uint32_t j = lo2 - offM, g = j / nseg;
-                    uint32_t row = y0l + g * MASKED_ROWS, seg = j - g * nseg;
+                    uint32_t row = y0l + g, seg = j - g * nseg;
                     for (uint32_t u = lo2; u < hi2; u++) {
-                        unitList[u - r0] = (unit_t)(tix | (row << 9) | (seg << 15));
-                        if (++seg == nseg) { seg = 0u; row += MASKED_ROWS; }
+                        unitList[u - r0] = tix | (row << 9) | (seg << 15);
+                        if (++seg == nseg) { seg = 0u; row++; }
                     }
                 }
             }
             __syncthreads();
-            const uint32_t nr = min(totalM - r0, (uint32_t)TILE_UNIT_CAP);
+            const uint32_t nr = min(totalM - r0, (uint32_t)UNIT_CAP);
             for (uint32_t ui = tix; ui < nr; ui += TB) {
                 const uint32_t d = unitList[ui];
                 entry_unit_masked<DEPTH>(p, prm, tile, d & 511u, (d >> 9) & 63u, (d >> 15) & 7u, ox, oy, noPixels);
             }
-            if (r0 + TILE_UNIT_CAP < totalM) __syncthreads();
+            if (r0 + UNIT_CAP < totalM) __syncthreads();
         }
         total |= totalM;
         if (total) __syncthreads();                               // prm / the unit list are rewritten by the next batch
         PHASE(4);
     };
     uint32_t batchNo = 0;
-    for (uint32_t base = lo; base < n; base += TILE_BATCH, batchNo++) {
+    for (uint32_t base = lo; base < n; base += TB, batchNo++) {
         window_advance(base);
         const uint32_t k = base + tix;
         const uint4 q0 = nq0, q1 = nq1, q2 = nq2;
         const uint32_t name = nameNext;
         nameNext = idxNext;
         if (nameNext != 0xFFFFFFFFu) FETCH_REC(nameNext, nq0, nq1, nq2);         // record of the next batch
-        idxNext = entryThread && k + 2u * TILE_BATCH < n ? binEntry(k + 2u * TILE_BATCH) : 0xFFFFFFFFu;   // bin entry of the batch after
+        idxNext = k + 2u * TB < n ? binEntry(k + 2u * TB) : 0xFFFFFFFFu;         // bin entry of the batch after
         batch_units(batch_setup(q0, q1, q2, name), batchNo);
     }
     __syncthreads();

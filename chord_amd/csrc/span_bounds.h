@@ -1,4 +1,4 @@
-// The span of one pixel row of a triangle, in steps k of the row loop: the ONE definition that scan_row, scan_span,
+// The span of one pixel row of a triangle, in steps k of the row loop: the ONE definition that scan_row,
 // scan_span_i32 and masked_rows (kernels_raster.hip) bound their loops with.  Compiles for host and device: the device passes
 // __builtin_amdgcn_rcpf as the reciprocal, a host program (tests/span_bounds_main.cpp) whatever it wants to try.
 //
@@ -45,8 +45,9 @@
 // is 0.4 % SLOWER on the flagship workload (profiles/r11_row_units.txt): the ladder is the product.
 //
 // Two entrances, one body.  span_bounds() computes the three reciprocals with the reciprocal it is given; span_bounds_rcp() takes
-// them ready-made (the tile kernel stores a triangle's three with its batch entry: they belong to the triangle, not to the row)
-// and wants of the steps only their signs, so it takes them in any arithmetic type -- the int32 steps as they are, unconverted.
+// them ready-made (they belong to the triangle, not to the row: a tile kernel that stored a triangle's three with its batch entry
+// was measured and rejected, kernels_raster.hip) and wants of the steps only their signs, so it takes them in any arithmetic type
+// -- the int32 steps as they are, unconverted.
 #pragma once
 #include <math.h>
 #include <stdint.h>

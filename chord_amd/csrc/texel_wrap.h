@@ -7,9 +7,6 @@
 
 namespace chord {
 
-#ifndef EXP_MASKED
-#define EXP_MASKED 0            // measurement builds only (results differ): 1 no fetch, 2 nearest everywhere, 4 sizes treated as powers of two, 8 unguarded shared-reciprocal divisions
-#endif
 // Texel indices are 32-bit here: texel_floor maps everything beyond +-1e9 to 0, so an index and its +1 neighbour fit an int32
 // (the oracle's 64-bit arithmetic gives the same values); a 64-bit modulo is ~200 instructions on this GPU and the bilinear
 // fetch of round 2 did eight of them per covered pixel.  Power-of-two periods (every level of a power-of-two texture) wrap with
@@ -19,7 +16,7 @@ namespace chord {
 // multiply-high, one multiply and one conditional subtraction replace the ~50 issue slots of a 32-bit signed remainder.
 __device__ __forceinline__ int32_t period_mod(int32_t i, int32_t period, uint32_t magic, uint32_t bias)
 {
-    if ((EXP_MASKED & 4) || magic == 0u) return i & (period - 1);
+    if (magic == 0u) return i & (period - 1);
     const uint32_t iu = (uint32_t)i + bias;
     uint32_t r = iu - __umulhi(iu, magic) * (uint32_t)period;
     if (r >= (uint32_t)period) r -= (uint32_t)period;

@@ -4,9 +4,10 @@
 // triangles in a 64-px box, seeded triangles of all three kinds, raw edge values and steps up to 2^62 / 2^40 with crossings on
 // pixel centres, at both clamp values and far off the row, zero steps with E <, ==, > 0, n = 0 and 63 -- and for the exact
 // reciprocal and the exact one moved one ulp either way it asks for the SAME (k0, k1) of
-//   span_bounds()       the helper as scan_row, scan_span and masked_rows call it
-//   span_bounds_rcp()   the form that takes the reciprocals ready-made (scan_span_i32: an entry's three, stored once), with the
-//                       steps as floats and as the integers they are (only their signs are read)
+//   span_bounds()       the helper as scan_row, scan_span_i32 and masked_rows call it
+//   span_bounds_rcp()   the form that takes the reciprocals ready-made (the body of span_bounds(); no kernel calls it directly since
+//                       the tile kernel variant that stored an entry's three once was rejected), with the steps as floats and as
+//                       the integers they are (only their signs are read)
 // Built with -DSPAN_SLACK_LEGACY=1 both sides return the earlier bounds.  Prints one line of counts; exit status 1 on a
 // difference or when a case the sweep has to contain did not occur.
 #include "span_bounds.h"

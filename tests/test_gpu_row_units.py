@@ -2,10 +2,11 @@
 the span bounds of a row, the two-pixel trips of the int32 scan -- on hand-made triangles, one frame each, word for word against
 the oracle (visibility image and HZB), in the manner of tests/test_gpu_span_bounds.py, whose scene builder this file uses.
 
-The cases run whatever library is built.  The product build lists units with the constant segment count and keeps the ladder form
-of the bounds and per-unit reciprocals; the measurement variants -DENTRY_RCP=1 (an entry's step reciprocals stored once, three
-more entry words, a 16-bit unit list: what the two-batch case was written for) and -DSPAN_STRAIGHT=1 (the bounds as selects) are
-covered by these cases only when the library is built with their switch.
+The cases run whatever library is built.  The product lists one unit per pixel row of an entry (the segment of the unit word is
+always 0: a row of the 64-pixel tile is one segment) and keeps the ladder form of the bounds and per-unit reciprocals.  The variant
+with an entry's step reciprocals stored once (three more entry words, a 16-bit unit list: what the two-batch case was written for)
+was rejected and its code is in the history at commit bb3c4eb (profiles/r11_row_units.txt); the measurement variant
+-DSPAN_STRAIGHT=1 (the bounds as selects) is covered by these cases only when the library is built with its switch.
 
 Targets of a few tiles whose right and bottom tiles are cut: 136 x 72 (3 x 2 tiles, 8 columns and 8 rows in the last ones) and
 328 x 136 (6 x 3).  The shapes are given tile-local, in pixels, and placed at several tile origins:
