@@ -675,7 +675,7 @@ int chordvis_destroy(ChordCtx* c)
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dTexEncTables);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -2296,6 +2296,46 @@ int chordvis_visible_clusters(ChordCtx* c, ChordCountAndCmd drawed, ChordDrawCmd
         return fail(c, CHORDVIS_E_INVALID, "visible_clusters: the list is not the one the latest chordvis_geometry_feedback was given");
     (void)hipSetDevice(c->device);
     chord::launch_visible_clusters(c, drawed.cmds, drawed.count, deviceOut, deviceCount, capacity);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_query_bounds(ChordCtx* c, const ChordHZB* hzb, int phase, const ChordBoundsQuery* deviceQueries, uint32_t count,
+                          ChordBoundsResult* deviceResults, uint32_t* deviceVisible, uint32_t* deviceVisibleCount, uint32_t capacity)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->viewSet) return fail(c, CHORDVIS_E_INVALID, "query_bounds: no view set (chordvis_set_view comes first)");
+    if (phase != 0 && phase != 1) return fail(c, CHORDVIS_E_INVALID, "query_bounds: phase is 0 (last frame's matrices) or 1");
+    if (count && !deviceQueries) return fail(c, CHORDVIS_E_INVALID, "query_bounds: deviceQueries is NULL with count > 0");
+    if (!deviceResults && !deviceVisible && !deviceVisibleCount) return fail(c, CHORDVIS_E_INVALID, "query_bounds: all three outputs are NULL");
+    if (capacity && !deviceVisible) return fail(c, CHORDVIS_E_INVALID, "query_bounds: deviceVisible is NULL with capacity > 0");
+    if (count > 0x80000000u) return fail(c, CHORDVIS_E_INVALID, "query_bounds: at most 2^31 queries per call");
+    if (((uintptr_t)deviceQueries | (uintptr_t)deviceResults) & 15u)
+        return fail(c, CHORDVIS_E_INVALID, "query_bounds: deviceQueries and deviceResults must be 16-byte aligned");
+    if (hzb) {
+        if (!hzb->minTexels) return fail(c, CHORDVIS_E_INVALID, "query_bounds: hzb given with minTexels NULL");
+        ChordHZBDesc want;
+        if (chordvis_hzb_desc(c->hView.width, c->hView.height, &want) != CHORDVIS_OK || std::memcmp(&want, &hzb->desc, sizeof(want)) != 0)
+            return fail(c, CHORDVIS_E_INVALID, "query_bounds: hzb->desc is not chordvis_hzb_desc(view width, view height): the main-view test has no level clamp");
+        if (c->hView.view.renderDimension[0] != c->hView.iv.renderDimension[0] || c->hView.view.renderDimension[1] != c->hView.iv.renderDimension[1])
+            return fail(c, CHORDVIS_E_INVALID, "query_bounds: the view's ChordCameraView::renderDimension differs from its ChordInstanceCullingView::renderDimension");
+    }
+    (void)hipSetDevice(c->device);
+    if (count == 0) {
+        if (deviceVisibleCount) CHORD_HIP(c, hipMemsetAsync(deviceVisibleCount, 0, 4, c->stream));
+        return CHORDVIS_OK;
+    }
+    { const int rc = flush_pending_tail(c); if (rc) return rc; }
+    const uint32_t words = chord::bounds_query_scratch_words(count);
+    if (words > c->boundsScratchWords) {
+        // (an earlier call on the stream may still be reading the scratch that is about to go)
+        CHORD_HIP(c, hipStreamSynchronize(c->stream));
+        c->boundsScratchWords = 0;
+        const int rc = dalloc(c, &c->dBoundsScratch, (size_t)words);
+        if (rc) return rc;
+        c->boundsScratchWords = words;
+    }
+    chord::launch_bounds_query(c, hzb, phase, deviceQueries, count, deviceResults, deviceVisible, deviceVisibleCount, capacity, c->dBoundsScratch);
     CHORD_HIP(c, hipGetLastError());
     return CHORDVIS_OK;
 }

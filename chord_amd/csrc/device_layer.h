@@ -454,6 +454,8 @@ struct ChordCtx {
     uint32_t* dGeoFeedback = nullptr;
     chord::GeoLayout geoLayout = {};
     const ChordDrawCmd* geoFeedbackCmds = nullptr;   // the list of the latest chordvis_geometry_feedback call; null: none since the last reset
+    uint32_t* dBoundsScratch = nullptr;       // chordvis_query_bounds: a bit per query and a count per workgroup step; grown on demand
+    uint32_t boundsScratchWords = 0;
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     std::vector<uint32_t> texCompress;        // chordvis_set_texture_compress: per texture id, 0 or a CHORD_TEXFMT_BC* target; kept across uploads, read by chordvis_upload_material_textures under CHORD_TEXSTORE_BLOCKS
@@ -681,6 +683,13 @@ void launch_geometry_feedback(ChordCtx* c, const unsigned long long* vis, const 
                               const ChordGeometryFeedbackDesc& desc);
 // the commands whose bit the bitmap holds, in list order, into out[0 .. capacity); *outCount = how many there are.  Two launches.
 void launch_visible_clusters(ChordCtx* c, const ChordDrawCmd* cmds, const uint32_t* cmdCount, ChordDrawCmd* out, uint32_t* outCount, uint32_t capacity);
+// kernels_cull.hip: chordvis_query_bounds' launches (arguments as the entry point's, checked by it; hzb null: no taps).  scratch:
+// bounds_query_scratch_words(count) words -- a bit per query (an even number of words), then a word per workgroup step.  One launch, or
+// two when the list or its count is wanted.
+inline uint32_t bounds_query_bitmap_words(uint32_t count) { return (((count + 31u) / 32u) + 1u) & ~1u; }
+inline uint32_t bounds_query_scratch_words(uint32_t count) { return bounds_query_bitmap_words(count) + (count + 31u) / 32u; }
+void launch_bounds_query(ChordCtx* c, const ChordHZB* hzb, int phase, const ChordBoundsQuery* queries, uint32_t count, ChordBoundsResult* results,
+                         uint32_t* visible, uint32_t* visibleCount, uint32_t capacity, uint32_t* scratch);
 void launch_pack_gbuffer(ChordCtx* c, uint32_t width, uint32_t height, const ChordGBufferSources& sources, const ChordGBufferTargets& targets);
 // kernels_texture.hip: expands the blocks of `count` levels (recs[count] closes the table) from `staging` into RGBA8 words of
 // `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.

@@ -3,6 +3,7 @@
 //   object_frame (device fn)    <- instanceCullingCS          instance_culling.hlsl:47-131 (runs inside group_cull_count_kernel)
 //   group_cull_count/scatter    <- clusterGroupCullingCS      instance_culling.hlsl:133-208
 //   hzb_cull_kernel<PHASE>      <- hzbMainViewCullingCS       hzb_mainview_culling.hlsl:35-213
+//   bounds_query_kernel<PHASE>  the object stage's and the main view's tests for boxes the host owns (chordvis_query_bounds; end of file)
 //
 // Design differences from the reference (results identical as sets; slots deterministic):
 //  * the reference spends a 64-thread group per object with 63 idle lanes and orders objects by
@@ -800,16 +801,21 @@ __device__ __forceinline__ float oct_max(float v)
 // frame_cull_fused_kernel; hzb_cmd_visible below: from a draw command)
 // (hzb_bounds_visible: with the projection matrix in registers already -- frame_cull_fused_kernel asks for it beside the object's other
 // fields, one round trip instead of two)
-template <int PHASE, bool TAIL = false, bool OCT = false>
-__device__ __forceinline__ bool hzb_bounds_visible(const HzbCullParams& p, const DView& dv, const Mat4& mvp, const DMeshlet& m,
-                                                   const float* sTail = nullptr, const uint32_t* sTailOff = nullptr, const uint32_t sub = 0u)
+// (hzb_bounds_core: the one definition.  INFO = false is the frame's test and nothing else -- every `if (INFO)` below is a compile-time
+// branch.  INFO = true is chordvis_query_bounds' form: the test runs whatever dv.flags says, *info receives which way it went (the
+// CHORD_BOUNDS_* bits except IN_FRUSTUM, the level tapped, mx.z and the pixel rectangle), and a null p.hzbMin skips the taps.)
+struct HzbBoundsInfo { uint32_t status; float nearestZ; int rect[4]; };
+template <int PHASE, bool TAIL = false, bool OCT = false, bool INFO = false>
+__device__ __forceinline__ bool hzb_bounds_core(const HzbCullParams& p, const DView& dv, const Mat4& mvp, const float* posMin, const float* posMax,
+                                                const float* sTail = nullptr, const uint32_t* sTailOff = nullptr, const uint32_t sub = 0u,
+                                                HzbBoundsInfo* info = nullptr)
 {
     bool visible = true;
     {
         {
-            if (dv.flags & CHORD_FLAG_HZB_CULL) {
+            if (INFO || (dv.flags & CHORD_FLAG_HZB_CULL)) {
                 f3 c, e;
-                aabb_center_extent(m.posMin, m.posMax, c, e);
+                aabb_center_extent(posMin, posMax, c, e);
 
                 f3 mx = {-10.0f, -10.0f, -10.0f}, mn = {10.0f, 10.0f, 10.0f};
                 if (OCT) {
@@ -824,8 +830,15 @@ __device__ __forceinline__ bool hzb_bounds_visible(const HzbCullParams& p, const
                     mx.x = fmaxf(mx.x, uvz.x); mx.y = fmaxf(mx.y, uvz.y); mx.z = fmaxf(mx.z, uvz.z);
                 }
                 const bool zInRange = mx.z < 1.0f && mn.z > 0.0f;
+                if (INFO) {
+                    const float W = dv.view.renderDimension[0], H = dv.view.renderDimension[1];
+                    info->status = zInRange ? 0u : CHORD_BOUNDS_NEAR;
+                    info->nearestZ = zInRange ? mx.z : 1.0f;
+                    info->rect[0] = 0; info->rect[1] = 0;
+                    info->rect[2] = zInRange ? 0 : (int)(W - 1.0f); info->rect[3] = zInRange ? 0 : (int)(H - 1.0f);
+                }
                 if (zInRange) {
-                    if ((mn.x >= 1.0f || mn.y >= 1.0f) || (mx.x <= 0.0f || mx.y <= 0.0f)) visible = false;
+                    if ((mn.x >= 1.0f || mn.y >= 1.0f) || (mx.x <= 0.0f || mx.y <= 0.0f)) { visible = false; if (INFO) info->status = CHORD_BOUNDS_OFFSCREEN; }
                 }
                 if (visible && zInRange) {
                     mn.x = saturatef(mn.x); mn.y = saturatef(mn.y);
@@ -838,9 +851,11 @@ __device__ __forceinline__ bool hzb_bounds_visible(const HzbCullParams& p, const
                     rx = max(0, rx); ry = max(0, ry);
                     rz = (int)fminf(W - 1.0f, (float)rz);
                     rw = (int)fminf(H - 1.0f, (float)rw);
+                    if (INFO) { info->rect[0] = rx; info->rect[1] = ry; info->rect[2] = rz; info->rect[3] = rw; }
                     if (rz < rx || rw < ry) {
                         visible = false;
-                    } else {
+                        if (INFO) info->status = CHORD_BOUNDS_EMPTY_RECT;
+                    } else if (!INFO || p.hzbMin) {
                         const int mx0 = rx >> 1, my0 = ry >> 1, mz0 = rz >> 1, mw0 = rw >> 1;
                         int lv = max(first_bit_high(mz0 - mx0), first_bit_high(mw0 - my0)) - 1;
                         lv = max(0, lv);
@@ -881,12 +896,21 @@ __device__ __forceinline__ bool hzb_bounds_visible(const HzbCullParams& p, const
                                 zMin = fminf(zMin, f16_to_f32(mip[(uint32_t)sy * mw + (uint32_t)sx]));
                             }
                         if (zMin > mx.z) visible = false;
+                        if (INFO) info->status = (uint32_t)lv << 8;
                     }
                 }
             }
         }
     }
+    if (INFO && visible) info->status |= CHORD_BOUNDS_UNOCCLUDED;
     return visible;
+}
+
+template <int PHASE, bool TAIL = false, bool OCT = false>
+__device__ __forceinline__ bool hzb_bounds_visible(const HzbCullParams& p, const DView& dv, const Mat4& mvp, const DMeshlet& m,
+                                                   const float* sTail = nullptr, const uint32_t* sTailOff = nullptr, const uint32_t sub = 0u)
+{
+    return hzb_bounds_core<PHASE, TAIL, OCT, false>(p, dv, mvp, m.posMin, m.posMax, sTail, sTailOff, sub);
 }
 
 template <int PHASE, bool TAIL = false, bool OCT = false>
@@ -1264,6 +1288,7 @@ __global__ __launch_bounds__(256) void group_cull_scatter_kernel(GroupCullParams
 #ifndef HZB_CULL_OCT
 #define HZB_CULL_OCT 1
 #endif
+#define HZB_CULL_LONG_LIST 65536u          // lists with room for more than this take the one-command-per-thread form (launch_hzb_cull, launch_bounds_query)
 // OCT: eight lanes per command (hzb_cmd_visible<., ., OCT>), THREADS / 8 commands per workgroup and step -- the form of short lists.
 template <int PHASE, uint32_t K, bool TAIL, uint32_t THREADS = 256u, bool OCT = false>
 __global__ __launch_bounds__(THREADS) void hzb_cull_kernel(HzbCullParams p)
@@ -1756,7 +1781,7 @@ void launch_hzb_cull(ChordCtx* c, const HzbBuffers& hzb, int phase, const CmdLis
 #ifndef HZB_CULL_OCT_LONG
 #define HZB_CULL_OCT_LONG 0          // measurement builds: the eight-lane form also for long lists
 #endif
-    const bool longList = in.capacity > 65536u && !HZB_CULL_OCT_LONG;
+    const bool longList = in.capacity > HZB_CULL_LONG_LIST && !HZB_CULL_OCT_LONG;
     const uint32_t threads = longList ? 1024u : 256u;
     uint32_t blocks = (in.capacity + threads - 1u) / threads;
     const uint32_t maxBlocks = (uint32_t)c->numCUs * (longList ? 2u : 8u);
@@ -1781,6 +1806,171 @@ void launch_hzb_cull(ChordCtx* c, const HzbBuffers& hzb, int phase, const CmdLis
     } else          { if (longList)          CHORD_LAUNCH(c, (hzb_cull_kernel<1, 1u, false, 1024u>), dim3(blocks), dim3(1024), 0, c->stream, p);
                       else if (HZB_CULL_OCT) CHORD_LAUNCH(c, (hzb_cull_kernel<1, 1u, false, OT, true>), dim3(octBlocks), dim3(OT), 0, c->stream, p);
                       else                   CHORD_LAUNCH(c, (hzb_cull_kernel<1, 1u, false>), dim3(blocks), dim3(256), 0, c->stream, p); }
+}
+
+// ---- bounds queries: the object stage's frustum test and the main view's occlusion test for boxes the host owns ------------------
+// (chordvis_query_bounds)  The arithmetic is the frame's: obj_mvp / obj_mvp_last / obj_visible and hzb_bounds_core,
+// called, not restated.  The view arrives as a kernel argument (the host copy of the last chordvis_set_view with both cull flags set:
+// a query is a question, not a frame setting), so nothing here reads FrameState, the lists or the published DView.
+// Two forms, chosen as launch_hzb_cull chooses hzb_cull_kernel's: OCT -- eight lanes per query, 32 queries per 256-thread workgroup
+// and step, a corner and two texels per lane -- for lists of up to HZB_CULL_LONG_LIST queries; one query per thread of a 1 024-thread
+// workgroup beyond.  A query's record is read as 16-byte vectors: the phase's matrix and the two bounds rows, six of its ten (the
+// eight lanes of an octet ask for the same six: one fetch of the lines, no exchange between the lanes afterwards).
+// The first launch writes the result records, one bit per query (visible = IN_FRUSTUM and UNOCCLUDED) and the visible count of every
+// workgroup step; the second (bounds_scatter_kernel) scans those counts and writes the indices of the set bits in ascending order --
+// chordvis_visible_clusters' count-then-scatter scheme: the order does not depend on scheduling.
+struct BoundsQueryParams {
+    HzbCullParams h;                       // hzbMin (null: no taps) and desc; nothing else of it is read
+    const ChordBoundsQuery* queries; ChordBoundsResult* results;     // results: null = not wanted
+    uint32_t* bits; uint32_t* stepCounts;  // [ceil(count / 32), rounded up to even], [ceil(count / queries per step)]
+    uint32_t count;
+};
+#define BOUNDS_SCATTER_QUERIES 8192u       // queries of a scatter workgroup's step: a bitmap word per thread
+
+__device__ __forceinline__ Mat4 load_mat_vec4(const float4* __restrict__ cols)       // load_mat of a ChordMat4, a column per 16-byte load
+{
+    Mat4 o;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const float4 v = cols[c];
+        o.r[0][c] = v.x; o.r[1][c] = v.y; o.r[2][c] = v.z; o.r[3][c] = v.w;
+    }
+    return o;
+}
+
+// one query (OCT: by the eight lanes of its octet together; lane sub == 0 stores the record); true = visible
+template <int PHASE, bool OCT>
+__device__ __forceinline__ bool bounds_query_one(const BoundsQueryParams& q, const DView& dv, uint32_t i, uint32_t sub)
+{
+    const float4* __restrict__ rec = reinterpret_cast<const float4*>(q.queries + i);
+    const Mat4 M = load_mat_vec4(rec + (PHASE == 0 ? 4 : 0));
+    const float4 lo = rec[8], hi = rec[9];
+    const float posMin[3] = {lo.x, lo.y, lo.z}, posMax[3] = {hi.x, hi.y, hi.z};
+    uint4 out = make_uint4(0u, 0u, 0u, 0u);
+    bool visible = false;
+    // the object stage on M (instance_culling.hlsl:71-89), then the occlusion test under the phase's projection
+    // (hzb_mainview_culling.hlsl:77-83)
+    const Mat4 mvp = obj_mvp(M, dv);
+    if (obj_visible(M, posMin, posMax, dv, mvp)) {
+        HzbBoundsInfo info;
+        visible = PHASE == 0 ? hzb_bounds_core<0, false, OCT, true>(q.h, dv, obj_mvp_last(M, dv), posMin, posMax, nullptr, nullptr, sub, &info)
+                             : hzb_bounds_core<1, false, OCT, true>(q.h, dv, mvp, posMin, posMax, nullptr, nullptr, sub, &info);
+        out.x = info.status | CHORD_BOUNDS_IN_FRUSTUM;
+        out.y = __float_as_uint(info.nearestZ);
+        out.z = ((uint32_t)info.rect[0] & 0xFFFFu) | ((uint32_t)info.rect[1] << 16);
+        out.w = ((uint32_t)info.rect[2] & 0xFFFFu) | ((uint32_t)info.rect[3] << 16);
+    }
+    if (q.results && sub == 0u) *reinterpret_cast<uint4*>(q.results + i) = out;
+    return visible;
+}
+
+template <int PHASE, uint32_t THREADS, bool OCT>
+__global__ __launch_bounds__(THREADS) void bounds_query_kernel(const BoundsQueryParams q, const DView dv)
+{
+    static_assert(!OCT || THREADS == 256u, "eight lanes per query: a 256-thread workgroup's step is one word of the bitmap");
+    constexpr uint32_t QPS = OCT ? THREADS / 8u : THREADS, WAVES = THREADS / 64u;      // queries of a workgroup's step
+    __shared__ uint32_t sWave[WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t steps = (q.count + QPS - 1u) / QPS;                                  // (count <= 2^31: no wrap)
+    for (uint32_t step = blockIdx.x; step < steps; step += gridDim.x) {
+        const uint32_t base = step * QPS;
+        const uint32_t i = base + (OCT ? threadIdx.x >> 3 : threadIdx.x), sub = OCT ? threadIdx.x & 7u : 0u;
+        bool vis = false;
+        if (i < q.count) vis = bounds_query_one<PHASE, OCT>(q, dv, i, sub);              // (the same for the eight lanes of an octet)
+        const unsigned long long ballot = __ballot(vis && sub == 0u);
+        if (OCT) {
+            // a wave is eight queries: bit 8 j of the ballot is query j's
+            uint32_t byte = 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 8u; j++) byte |= (uint32_t)((ballot >> (8u * j)) & 1ull) << j;
+            if (lane == 0u) sWave[wave] = byte;
+            __syncthreads();
+            if (threadIdx.x == 0u) {
+                const uint32_t word = (sWave[0] | (sWave[1] << 8)) | ((sWave[2] << 16) | (sWave[3] << 24));
+                q.bits[base >> 5] = word;
+                q.stepCounts[step] = (uint32_t)__popc(word);
+            }
+        } else {
+            // a wave is 64 queries: two words of the bitmap (the second may lie past the last query: the bitmap has an even word count)
+            if (lane == 0u) {
+                if (base + wave * 64u < q.count) { q.bits[(base >> 5) + 2u * wave] = (uint32_t)ballot; q.bits[(base >> 5) + 2u * wave + 1u] = (uint32_t)(ballot >> 32); }
+                sWave[wave] = (uint32_t)__popcll(ballot);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0u) {
+                uint32_t n = 0u;
+#pragma unroll
+                for (uint32_t w = 0; w < WAVES; w++) n += sWave[w];
+                q.stepCounts[step] = n;
+            }
+        }
+        __syncthreads();                                            // sWave is rewritten by the next step
+    }
+}
+
+struct BoundsScatterParams {
+    const uint32_t* bits; const uint32_t* stepCounts;
+    uint32_t* visible; uint32_t* visibleCount;     // either may be null
+    uint32_t count, capacity, stepQueries;         // stepQueries: queries per entry of stepCounts (divides BOUNDS_SCATTER_QUERIES)
+};
+
+__global__ __launch_bounds__(256) void bounds_scatter_kernel(const BoundsScatterParams a)
+{
+    const uint32_t words = (a.count + 31u) / 32u, steps = (a.count + a.stepQueries - 1u) / a.stepQueries;
+    const uint32_t stepsPerBlock = BOUNDS_SCATTER_QUERIES / a.stepQueries;
+    const uint32_t blocks = (a.count + BOUNDS_SCATTER_QUERIES - 1u) / BOUNDS_SCATTER_QUERIES;
+    uint32_t total;
+    // `at` walks with the loop: the visible queries in front of this step = those in front of the step before + the counts in between
+    uint32_t at = 0u, summed = 0u;
+    for (uint32_t sb = blockIdx.x; sb < blocks; sb += gridDim.x) {
+        const uint32_t upto = min(sb * stepsPerBlock, steps);
+        uint32_t part = 0u;
+        for (uint32_t g = summed + threadIdx.x; g < upto; g += 256u) part += a.stepCounts[g];
+        (void)block_excl_scan(part, &total);
+        at += total; summed = upto;
+        const uint32_t w = sb * 256u + threadIdx.x;
+        uint32_t bits = w < words ? a.bits[w] : 0u;
+        const uint32_t before = block_excl_scan((uint32_t)__popc(bits), &total);
+        uint32_t slot = at + before;
+        while (a.visible && bits && slot < a.capacity) {
+            const uint32_t b = (uint32_t)__ffs((int)bits) - 1u;
+            bits &= bits - 1u;
+            a.visible[slot++] = w * 32u + b;
+        }
+    }
+    if (blockIdx.x == 0u && a.visibleCount) {
+        uint32_t part = 0u;
+        for (uint32_t g = threadIdx.x; g < steps; g += 256u) part += a.stepCounts[g];
+        (void)block_excl_scan(part, &total);
+        if (threadIdx.x == 0u) *a.visibleCount = total;
+    }
+}
+
+void launch_bounds_query(ChordCtx* c, const ChordHZB* hzb, int phase, const ChordBoundsQuery* queries, uint32_t count, ChordBoundsResult* results,
+                         uint32_t* visible, uint32_t* visibleCount, uint32_t capacity, uint32_t* scratch)
+{
+    BoundsQueryParams q = {};
+    if (hzb) { q.h.hzbMin = hzb->minTexels; q.h.desc = hzb->desc; }
+    q.queries = queries; q.results = results; q.count = count;
+    const bool longList = count > HZB_CULL_LONG_LIST;               // (launch_hzb_cull's switch)
+    const uint32_t stepQueries = longList ? 1024u : 32u, steps = (count + stepQueries - 1u) / stepQueries;
+    q.bits = scratch; q.stepCounts = scratch + bounds_query_bitmap_words(count);
+    DView dv = c->hView;
+    dv.flags |= CHORD_FLAG_FRUSTUM_CULL | CHORD_FLAG_HZB_CULL;
+    // grids: launch_hzb_cull's caps (debug bit 16777216: two workgroups, so that short lists walk the grid-stride loops)
+    const uint32_t cap = (c->debugFlags & 16777216u) ? 2u : (uint32_t)c->numCUs * (longList ? 2u : 32u);
+    const dim3 grid(std::max(1u, std::min(steps, cap)));
+    if (longList) { if (phase == 0) CHORD_LAUNCH(c, (bounds_query_kernel<0, 1024u, false>), grid, dim3(1024), 0, c->stream, q, dv);
+                    else            CHORD_LAUNCH(c, (bounds_query_kernel<1, 1024u, false>), grid, dim3(1024), 0, c->stream, q, dv); }
+    else          { if (phase == 0) CHORD_LAUNCH(c, (bounds_query_kernel<0, 256u, true>), grid, dim3(256), 0, c->stream, q, dv);
+                    else            CHORD_LAUNCH(c, (bounds_query_kernel<1, 256u, true>), grid, dim3(256), 0, c->stream, q, dv); }
+    if (!visibleCount && !visible) return;
+    BoundsScatterParams a;
+    a.bits = q.bits; a.stepCounts = q.stepCounts; a.visible = capacity ? visible : nullptr; a.visibleCount = visibleCount;
+    a.count = count; a.capacity = capacity; a.stepQueries = stepQueries;
+    const uint32_t scatterBlocks = (count + BOUNDS_SCATTER_QUERIES - 1u) / BOUNDS_SCATTER_QUERIES;
+    const uint32_t scatterCap = (c->debugFlags & 16777216u) ? 2u : (uint32_t)c->numCUs * 4u;
+    CHORD_LAUNCH(c, bounds_scatter_kernel, dim3(std::max(1u, std::min(scatterBlocks, scatterCap))), dim3(256), 0, c->stream, a);
 }
 
 } // namespace chord

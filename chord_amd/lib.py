@@ -124,6 +124,17 @@ class HZB(C.Structure):
     _fields_ = [("desc", R.HZBDesc), ("minTexels", C.c_void_p), ("maxTexels", C.c_void_p), ("validRange", C.c_void_p)]
 
 
+class BoundsQuery(C.Structure):
+    """ChordBoundsQuery: one host-owned box of chordvis_query_bounds (numpy: records.BOUNDS_QUERY)."""
+    _fields_ = [("localToTranslatedWorld", C.c_float * 16), ("localToTranslatedWorldLastFrame", C.c_float * 16),
+                ("posMin", C.c_float * 3), ("user", C.c_uint32), ("posMax", C.c_float * 3), ("pad", C.c_uint32)]
+
+
+class BoundsResult(C.Structure):
+    """ChordBoundsResult: what chordvis_query_bounds says about one box (numpy: records.BOUNDS_RESULT)."""
+    _fields_ = [("status", C.c_uint32), ("nearestZ", C.c_float), ("rect", C.c_uint16 * 4)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [
         ("position", C.c_double * 3), ("front", C.c_double * 3), ("worldUp", C.c_double * 3),
@@ -286,6 +297,7 @@ def _load():
         "chordvis_readback_geometry_feedback": (i32, [vp, P(GeometryFeedback), u32, u32]),
         "chordvis_visible_clusters": (i32, [vp, CountAndCmd, vp, vp, u32]),
         "chordvis_geometry_feedback_seen": (i32, [vp, vp, u32]),
+        "chordvis_query_bounds": (i32, [vp, P(HZB), i32, vp, u32, vp, vp, vp, u32]),
         "chordvis_set_texture_first_level": (i32, [vp, P(u32), u32]),
         "chordvis_texture_first_level": (i32, [vp, u32, P(u32)]),
         "chordvis_material_texture_levels": (i32, [vp, u32, P(u32), P(u32)]),

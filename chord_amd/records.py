@@ -88,6 +88,18 @@ FLAG_FRUSTUM_CULL = 1 << 0
 FLAG_HZB_CULL = 1 << 1
 FLAG_CONE_CULL = 1 << 2
 
+# chordvis_query_bounds (ChordBoundsQuery / ChordBoundsResult)
+BOUNDS_QUERY = np.dtype([
+    ("localToTranslatedWorld", f32, 16),
+    ("localToTranslatedWorldLastFrame", f32, 16),
+    ("posMin", f32, 3), ("user", u32),
+    ("posMax", f32, 3), ("pad", u32),
+])
+BOUNDS_RESULT = np.dtype([("status", u32), ("nearestZ", f32), ("rect", np.uint16, 4)])
+assert BOUNDS_QUERY.itemsize == 160 and BOUNDS_RESULT.itemsize == 16
+BOUNDS_IN_FRUSTUM, BOUNDS_UNOCCLUDED, BOUNDS_NEAR, BOUNDS_OFFSCREEN, BOUNDS_EMPTY_RECT = 1, 2, 4, 8, 16
+BOUNDS_LEVEL_SHIFT, BOUNDS_LEVEL_MASK = 8, 0xF
+
 HZB_MAX_MIPS = 12
 
 

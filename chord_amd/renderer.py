@@ -238,6 +238,43 @@ class VisibilityRenderer:
         total = int(host[3 * capacity:3 * capacity + 1].view(np.uint32)[0])
         return host[:3 * min(capacity, total)].copy().view(R.DRAW_CMD), total
 
+    def query_bounds(self, queries, hzb=None, phase=1, want_results=True, capacity=None, want_count=True):
+        """chordvis_query_bounds: the frame's frustum and occlusion tests for host-owned boxes.  queries: a numpy array of
+        records.BOUNDS_QUERY, or a contiguous CUDA tensor holding such records (160 bytes each) on the context's device.  hzb: an
+        L.HZB handle (history_hzb()), or None for everything but the taps.  phase: 1 tests with the current matrices, 0 with last
+        frame's.  Returns (results, visible_indices, visible_count), read back: records.BOUNDS_RESULT per query (None unless
+        want_results), the uint32 indices of the visible queries in ascending order (at most `capacity` of them; default: room for
+        all) and their number, which may exceed capacity (None unless want_count).  The call is ordered behind the current torch
+        stream and that one behind the call (as resolve_gbuffer does it)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(queries, np.ndarray):
+            host = np.ascontiguousarray(queries, dtype=R.BOUNDS_QUERY).reshape(-1)
+            count = len(host)
+            with torch.cuda.device(dev):
+                q = torch.from_numpy(host.view(np.uint8).copy()).to(dev) if count else torch.zeros(16, dtype=torch.uint8, device=dev)
+        else:
+            q = queries
+            nbytes = q.numel() * q.element_size()
+            assert q.is_cuda and q.is_contiguous() and nbytes % R.BOUNDS_QUERY.itemsize == 0, "query_bounds: a contiguous CUDA tensor of 160-byte records"
+            count = nbytes // R.BOUNDS_QUERY.itemsize
+        capacity = count if capacity is None else int(capacity)
+        with torch.cuda.device(dev):
+            res = torch.zeros(4 * count, dtype=torch.int32, device=dev) if want_results else None
+            vis = torch.zeros(capacity, dtype=torch.int32, device=dev) if capacity else None
+            cnt = torch.zeros(1, dtype=torch.int32, device=dev) if want_count else None
+        used = [t for t in (q, res, vis, cnt) if t is not None]
+        self._on_my_stream(used, lambda: self._check(L.lib.chordvis_query_bounds(
+            self._ctx, C.byref(hzb) if hzb is not None else None, int(phase), q.data_ptr() if count else None, count,
+            res.data_ptr() if res is not None and count else None, vis.data_ptr() if vis is not None else None,
+            cnt.data_ptr() if cnt is not None else None, capacity), "query_bounds"))
+        self.sync()
+        total = int(cnt.cpu().numpy().view(np.uint32)[0]) if cnt is not None else None
+        results = res.cpu().numpy().view(R.BOUNDS_RESULT).copy() if res is not None else None
+        listed = capacity if total is None else min(capacity, total)
+        indices = vis.cpu().numpy().view(np.uint32)[:listed].copy() if vis is not None else np.zeros(0, dtype=np.uint32)
+        return results, indices, total
+
     def texture_mips(self, texture):
         """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""
         m = L.TextureMips()

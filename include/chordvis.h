@@ -844,6 +844,44 @@ int chordvis_geometry_feedback(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd,
 int chordvis_readback_geometry_feedback(ChordCtx* ctx, const ChordGeometryFeedback* out, uint32_t objectCount, uint32_t primitiveCount);
 int chordvis_visible_clusters(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, ChordDrawCmd* deviceOut, uint32_t* deviceCount, uint32_t capacity);
 int chordvis_geometry_feedback_seen(ChordCtx* ctx, uint32_t* hostWords, uint32_t wordCount);
+/* Bounds queries -- the frame's frustum and occlusion tests for boxes the HOST owns (light volumes, particle systems, decals, portal
+ * volumes: things the library never rasters): `count` ChordBoundsQuery records in device memory in, a ChordBoundsResult per box and a
+ * compacted, ordered list of the visible ones out.  Stream-ordered: the call runs on the context's stream behind the work that made the
+ * chain, and returns without synchronising.  Every test runs whatever switchFlags chordvis_set_view was given -- a query is a question,
+ * not a frame setting.  
+ *   1. Frustum.  M = localToTranslatedWorld (phase 1) or localToTranslatedWorldLastFrame (phase 0).  The test is the object stage's
+ *      (instance_culling.hlsl:79-89) for an object whose primitive bounds are the box and whose localToTranslatedWorld is M: the
+ *      current view's planes, and translatedWorldToClip * M where the orthographic branch projects.  A culled box's record is all zero
+ *      and nothing further runs for it.
+ *   2. Occlusion.  mvp = translatedWorldToClip * M (phase 1) or translatedWorldToClipLastFrame * M_last (phase 0); the test is the main
+ *      view's (hzb_mainview_culling.hlsl:60-161) on (posMin, posMax): eight corners, zInRange, the uv reject, the pixel rectangle, the
+ *      level choice, 4 x 4 clamped taps of hzb->minTexels, rejected when the farthest of them is nearer than the box (zMin > mx.z).
+ *      UNOCCLUDED is that test's answer; the other bits, rect, nearestZ and the level say which way it went:
+ *        NEAR         the box reaches the near plane or lies behind the camera: kept untested; nearestZ 1.0f, rect (0, 0, W-1, H-1)
+ *        OFFSCREEN    rejected before any tap; rect 0, nearestZ = mx.z
+ *        EMPTY_RECT   rejected before any tap; rect as computed (rz < rx or rw < ry), nearestZ = mx.z
+ *        otherwise    rect, nearestZ = mx.z, and the level tapped in bits 8..11
+ *      With hzb == NULL everything but the taps runs: UNOCCLUDED is set unless OFFSCREEN or EMPTY_RECT is, and the level bits are 0.
+ *   3. Visible list.  A query is visible when IN_FRUSTUM and UNOCCLUDED are both set.  deviceVisible receives the indices of the visible
+ *      queries in ASCENDING order, *deviceVisibleCount their number even when it exceeds `capacity`; nothing is written at or beyond
+ *      `capacity`.  The order is part of the contract and does not depend on scheduling.
+ *   4. View, stream and frame state.  The view is the host copy of the last chordvis_set_view: the call is valid straight after it,
+ *      before or after a frame, with or without an uploaded scene.  It flushes a pending HZB tail first like every other reader of the
+ *      chain (chordvis_history_hzb's handle is the usual `hzb`), and touches neither the frame's lists and counts, chordvis_stats'
+ *      counters nor the history.  Two launches (one when neither the list nor the count is wanted; none for count == 0, which
+ *      succeeds and writes *deviceVisibleCount = 0).  The context keeps a scratch of one bit per query and one word per workgroup step.
+ *   5. CHORDVIS_E_INVALID, chordvis_last_error naming the rule: no view set; phase other than 0 or 1; count > 0 with deviceQueries NULL;
+ *      all three outputs NULL; capacity > 0 with deviceVisible NULL; hzb given with minTexels NULL; hzb->desc not byte-equal to
+ *      chordvis_hzb_desc(view width, view height) -- the main-view test has no level clamp, and this rule is what keeps its level
+ *      choice inside the chain --; with hzb given, a view whose ChordCameraView::renderDimension differs from its
+ *      ChordInstanceCullingView::renderDimension (the rectangle is formed in the former, the chain sized by the latter);
+ *      deviceQueries or deviceResults not 16-byte aligned (the records move as 16-byte vectors). */
+int chordvis_query_bounds(ChordCtx* ctx, const ChordHZB* hzb /* NULL: frustum only */, int phase /* 0 or 1 */,
+                          const ChordBoundsQuery* deviceQueries, uint32_t count,
+                          ChordBoundsResult* deviceResults      /* [count] or NULL */,
+                          uint32_t* deviceVisible               /* [capacity] query indices, or NULL when capacity == 0 */,
+                          uint32_t* deviceVisibleCount          /* one word, or NULL */,
+                          uint32_t capacity);
 /* The G-buffer in the reference's packed image formats -- what exportGbuffer (lighting.hlsl:62-73) writes into GBufferTextures
  * (render_textures.h:27-49) and every later pass reads: 28 bytes per pixel for the six images, where the float images of
  * chordvis_resolve_material take 88.  The packing is pinned; float32, source order, unfused; R in the low bits:
@@ -945,7 +983,8 @@ int chordvis_stats(ChordCtx* ctx, ChordStats* out);
  * keep the replicated group cull instead of the sharded one (A / B measurements; every rank of a frame must agree), 4194304
  * chordvis_material_feedback's workgroups use 2 entries of their on-chip count tables instead of 512, so that most adds find
  * the table full and go to global memory (the same counts, slower), 8388608 chordvis_geometry_feedback's workgroups likewise use
- * 2 entries of their count tables instead of 1024. */
+ * 2 entries of their count tables instead of 1024, 16777216 chordvis_query_bounds launches grids of at most two workgroups, so that
+ * short lists walk the grid-stride loops of its kernels. */
 int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 /* measurement / test aid: fills EVERY rank's chunk of the cull exchange buffer on this context for the current view (what the
  * all-gather would deliver), so that one rank of a sharded frame can be timed alone on one device (tools/shard_time.py) */

@@ -282,8 +282,33 @@ typedef struct ChordHZBDesc {
     uint32_t totalTexels;
 } ChordHZBDesc;
 
+/* chordvis_query_bounds (chordvis.h): one host-owned box, and what the frustum and occlusion tests said about it. */
+typedef struct ChordBoundsQuery {               /* 160 bytes, DEVICE memory, caller-owned, 16-byte aligned */
+    ChordMat4 localToTranslatedWorld;           /* as ChordObject::basicData's (chordvis_object_basic_data makes them) */
+    ChordMat4 localToTranslatedWorldLastFrame;  /* read by phase 0 only */
+    float posMin[3]; uint32_t user;             /* local-space box; `user` is carried, never read */
+    float posMax[3]; uint32_t pad;              /* 0 */
+} ChordBoundsQuery;
+
+#define CHORD_BOUNDS_IN_FRUSTUM  1u    /* the object-stage frustum test keeps it                                   */
+#define CHORD_BOUNDS_UNOCCLUDED  2u    /* the main-view occlusion test keeps it                                    */
+#define CHORD_BOUNDS_NEAR        4u    /* !(max z < 1 && min z > 0): kept untested, as the reference does          */
+#define CHORD_BOUNDS_OFFSCREEN   8u    /* z in range, uv box outside [0,1]^2: rejected before any tap             */
+#define CHORD_BOUNDS_EMPTY_RECT 16u    /* rz < rx || rw < ry: covers no pixel, rejected                            */
+/* bits 8..11: the HZB level tapped (0 when nothing was tapped) */
+#define CHORD_BOUNDS_LEVEL_SHIFT 8u
+#define CHORD_BOUNDS_LEVEL_MASK  0xFu
+
+typedef struct ChordBoundsResult {              /* 16 bytes, 16-byte aligned */
+    uint32_t status;
+    float    nearestZ;      /* max projected z of the 8 corners (reverse-Z: nearest); 1.0f with NEAR */
+    uint16_t rect[4];       /* rx, ry, rz, rw: the inclusive pixel rectangle the test formed; (0, 0, W-1, H-1) with NEAR */
+} ChordBoundsResult;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
+static_assert(sizeof(ChordBoundsResult) == 16, "ChordBoundsResult");
 static_assert(sizeof(ChordMeshlet) == 64, "GPUGLTFMeshlet");
 static_assert(sizeof(ChordMeshletGroup) == 40, "GPUGLTFMeshletGroup");
 static_assert(sizeof(ChordBVHNode) == 60, "GPUBVHNode");
