@@ -675,7 +675,7 @@ int chordvis_destroy(ChordCtx* c)
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
-    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dTexEncTables);
+    dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dBoundsTilesScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
@@ -2336,6 +2336,68 @@ int chordvis_query_bounds(ChordCtx* c, const ChordHZB* hzb, int phase, const Cho
         c->boundsScratchWords = words;
     }
     chord::launch_bounds_query(c, hzb, phase, deviceQueries, count, deviceResults, deviceVisible, deviceVisibleCount, capacity, c->dBoundsScratch);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+uint32_t chordvis_bounds_tile_count(uint32_t width, uint32_t height, uint32_t tileSize, uint32_t* tilesX, uint32_t* tilesY)
+{
+    uint64_t tx = 0, ty = 0;
+    if (tileSize == 8u || tileSize == 16u || tileSize == 32u || tileSize == 64u) {
+        tx = ((uint64_t)width + tileSize - 1u) / tileSize; ty = ((uint64_t)height + tileSize - 1u) / tileSize;
+        if (tx * ty > 0xFFFFFFFFull) tx = ty = 0;
+    }
+    if (tilesX) *tilesX = (uint32_t)tx;
+    if (tilesY) *tilesY = (uint32_t)ty;
+    return (uint32_t)(tx * ty);
+}
+
+int chordvis_bin_bounds(ChordCtx* c, const ChordBoundsTilesDesc* desc, const ChordBoundsResult* deviceResults, const ChordBoundsQuery* deviceQueries,
+                        uint32_t count, const ChordBoundsTiles* out)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!desc || !out) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: desc or out is NULL");
+    if (!out->tileCounts && !out->tileItems && !out->tileDepth && !out->totals) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: all four outputs are NULL");
+    if (desc->tileSize != 8u && desc->tileSize != 16u && desc->tileSize != 32u && desc->tileSize != 64u)
+        return fail(c, CHORDVIS_E_INVALID, "bin_bounds: tileSize is 8, 16, 32 or 64");
+    if (desc->flags & ~(CHORD_BOUNDS_TILES_NEAR | CHORD_BOUNDS_TILES_FAR)) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: unknown flags bits");
+    if (desc->phase > 1u) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: phase is 0 (last frame's matrices) or 1");
+    const bool farSide = (desc->flags & CHORD_BOUNDS_TILES_FAR) != 0u;
+    if (farSide && !deviceQueries) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: CHORD_BOUNDS_TILES_FAR needs deviceQueries");
+    if (count && !deviceResults) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: deviceResults is NULL with count > 0");
+    if (out->tileItems && desc->maxPerTile == 0u) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: tileItems given with maxPerTile == 0");
+    if (((uintptr_t)deviceResults | (uintptr_t)deviceQueries) & 15u)
+        return fail(c, CHORDVIS_E_INVALID, "bin_bounds: deviceResults and deviceQueries must be 16-byte aligned");
+    if (!c->dVis) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: no G-buffer allocated (chordvis_allocate_gbuffer comes first)");
+    if (!c->viewSet) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: no view set (chordvis_set_view comes first)");
+    {
+        const float W = (float)c->width, H = (float)c->height;
+        const ChordCameraView& v = c->hView.view; const ChordInstanceCullingView& iv = c->hView.iv;
+        if (v.renderDimension[0] != W || v.renderDimension[1] != H || iv.renderDimension[0] != W || iv.renderDimension[1] != H)
+            return fail(c, CHORDVIS_E_INVALID, "bin_bounds: the view's renderDimension differs from the image's size");
+    }
+    const uint32_t tiles = chordvis_bounds_tile_count(c->width, c->height, desc->tileSize, nullptr, nullptr);
+    if ((uint64_t)tiles * desc->maxPerTile > 0xFFFFFFFFull) return fail(c, CHORDVIS_E_INVALID, "bin_bounds: tiles * maxPerTile is beyond 2^32 - 1");
+    (void)hipSetDevice(c->device);
+    // the lists are wanted: the records that take part go through the scratch (tileDepth alone reads no record)
+    const bool lists = count && (out->tileCounts || out->tileItems || out->totals);
+    if (lists) {
+        const size_t words = chord::bounds_tiles_scratch_words(count, chord::bounds_tiles_blocks(c->width, c->height));
+        if (words > c->boundsTilesScratchWords) {
+            // (an earlier call on the stream may still be reading the scratch that is about to go)
+            CHORD_HIP(c, hipStreamSynchronize(c->stream));
+            c->boundsTilesScratchWords = 0;
+            const int rc = dalloc(c, &c->dBoundsTilesScratch, words);
+            if (rc) return rc;
+            c->boundsTilesScratchWords = words;
+        }
+    }
+    const unsigned long long* vis = (const unsigned long long*)(c->shard.ranks > 1 ? c->dVisResolved : c->dVis);
+    // (pipelined group frames: the image is gathered and resolved beside the context's stream)
+    if (c->visReadyEvent[0]) CHORD_HIP(c, hipStreamWaitEvent(c->stream, c->visReadyEvent[0], 0));
+    if (out->totals && !lists) CHORD_HIP(c, hipMemsetAsync(out->totals, 0, 16, c->stream));    // (with records the launches write all four)
+    if (lists) chord::launch_bounds_tiles_prepare(c, *desc, deviceResults, deviceQueries, count, c->dBoundsTilesScratch, out->totals);
+    chord::launch_bounds_tiles(c, vis, *desc, count, lists, c->dBoundsTilesScratch, *out);
     CHORD_HIP(c, hipGetLastError());
     return CHORDVIS_OK;
 }

@@ -456,6 +456,8 @@ struct ChordCtx {
     const ChordDrawCmd* geoFeedbackCmds = nullptr;   // the list of the latest chordvis_geometry_feedback call; null: none since the last reset
     uint32_t* dBoundsScratch = nullptr;       // chordvis_query_bounds: a bit per query and a count per workgroup step; grown on demand
     uint32_t boundsScratchWords = 0;
+    uint32_t* dBoundsTilesScratch = nullptr;  // chordvis_bin_bounds: the records that take part, in order, and a count per workgroup step; grown on demand
+    size_t boundsTilesScratchWords = 0;
     bool matAnyNormalTexture = false;         // some material has an uploaded normal texture (pixelNormal then needs tangents)
     uint32_t matAnisotropy = 1u;              // chordvis_set_material_anisotropy: 1 (off), 2, 4, 8 or 16; kept across uploads
     std::vector<uint32_t> texCompress;        // chordvis_set_texture_compress: per texture id, 0 or a CHORD_TEXFMT_BC* target; kept across uploads, read by chordvis_upload_material_textures under CHORD_TEXSTORE_BLOCKS
@@ -690,6 +692,22 @@ inline uint32_t bounds_query_bitmap_words(uint32_t count) { return (((count + 31
 inline uint32_t bounds_query_scratch_words(uint32_t count) { return bounds_query_bitmap_words(count) + (count + 31u) / 32u; }
 void launch_bounds_query(ChordCtx* c, const ChordHZB* hzb, int phase, const ChordBoundsQuery* queries, uint32_t count, ChordBoundsResult* results,
                          uint32_t* visible, uint32_t* visibleCount, uint32_t capacity, uint32_t* scratch);
+// chordvis_bin_bounds' launches (arguments as the entry point's, checked by it).  kernels_cull.hip: launch_bounds_tiles_prepare -- two
+// launches that put the records that take part into `scratch` in ascending order; kernels_tiles.hip: launch_bounds_tiles -- the tiles'
+// depth bounds and lists, one launch, and one more for the totals when they are wanted (haveRecords false: no record is read and
+// the scratch is not touched; the totals are then zero and the caller's to clear).  scratch, in words: [0] the number of records,
+// [4 ..) three words per 64 x 64-pixel block of the image (what it adds to totals[1 .. 3]), a count per 256-query step, then a uint4
+// (rectangle, nearestZ, farZ) and after those an index word per record.
+// (`blocks` = bounds_tiles_blocks of the image: the one number both the size of that area and the tile kernel's loop come from)
+inline uint32_t bounds_tiles_blocks(uint32_t width, uint32_t height) { return ((width + 63u) / 64u) * ((height + 63u) / 64u); }
+inline size_t bounds_tiles_step_words(uint32_t count) { return ((((size_t)count + 255u) / 256u) + 3u) & ~(size_t)3u; }
+inline size_t bounds_tiles_steps_at(uint32_t blocks) { return 4u + ((3u * (size_t)blocks + 3u) & ~(size_t)3u); }
+inline size_t bounds_tiles_records_at(uint32_t count, uint32_t blocks) { return bounds_tiles_steps_at(blocks) + bounds_tiles_step_words(count); }
+inline size_t bounds_tiles_scratch_words(uint32_t count, uint32_t blocks) { return bounds_tiles_records_at(count, blocks) + 5u * (size_t)count; }
+void launch_bounds_tiles_prepare(ChordCtx* c, const ChordBoundsTilesDesc& desc, const ChordBoundsResult* results, const ChordBoundsQuery* queries,
+                                 uint32_t count, uint32_t* scratch, uint32_t* totals);
+void launch_bounds_tiles(ChordCtx* c, const unsigned long long* vis, const ChordBoundsTilesDesc& desc, uint32_t count, bool haveRecords,
+                         uint32_t* scratch, const ChordBoundsTiles& out);
 void launch_pack_gbuffer(ChordCtx* c, uint32_t width, uint32_t height, const ChordGBufferSources& sources, const ChordGBufferTargets& targets);
 // kernels_texture.hip: expands the blocks of `count` levels (recs[count] closes the table) from `staging` into RGBA8 words of
 // `texels`, or -- alphaOnly: BC3 levels only -- their alpha bytes into `alpha`.  One launch on the context's stream.

@@ -4,6 +4,7 @@
 //   group_cull_count/scatter    <- clusterGroupCullingCS      instance_culling.hlsl:133-208
 //   hzb_cull_kernel<PHASE>      <- hzbMainViewCullingCS       hzb_mainview_culling.hlsl:35-213
 //   bounds_query_kernel<PHASE>  the object stage's and the main view's tests for boxes the host owns (chordvis_query_bounds; end of file)
+//   bounds_tiles_count / prepare  the results that take part in chordvis_bin_bounds, compacted in order with their farthest depth (end of file)
 //
 // Design differences from the reference (results identical as sets; slots deterministic):
 //  * the reference spends a 64-thread group per object with 63 idle lanes and orders objects by
@@ -1971,6 +1972,105 @@ void launch_bounds_query(ChordCtx* c, const ChordHZB* hzb, int phase, const Chor
     const uint32_t scatterBlocks = (count + BOUNDS_SCATTER_QUERIES - 1u) / BOUNDS_SCATTER_QUERIES;
     const uint32_t scatterCap = (c->debugFlags & 16777216u) ? 2u : (uint32_t)c->numCUs * 4u;
     CHORD_LAUNCH(c, bounds_scatter_kernel, dim3(std::max(1u, std::min(scatterBlocks, scatterCap))), dim3(256), 0, c->stream, a);
+}
+
+// ---- bounds tile lists, first step: the records that take part, in order ------------------------------------------------------------
+// (chordvis_bin_bounds; the tile kernel that reads them is kernels_tiles.hip's.)  A result takes part when it has
+// IN_FRUSTUM and UNOCCLUDED.  Count-then-scatter as above, a step = 256 queries: bounds_tiles_count_kernel writes every step's number
+// of such results; bounds_tiles_prepare_kernel sums the counts in front of its step, scans its 256 flags and writes, for every result
+// that takes part, {rect[0] | rect[1] << 16, rect[2] | rect[3] << 16, nearestZ, farZ} and the query's index at its rank among them --
+// ascending by construction, whatever the scheduling.  farZ (FAR only; else 0): 0.0f for a NEAR record, otherwise the smallest projected z
+// of the box's corners -- hzb_bounds_core's mn.z, from the same functions in the same order -- under the phase's obj_mvp / obj_mvp_last
+// and the view as a kernel argument, as bounds_query_kernel receives it.  Workgroup 0 also writes the number of records.
+struct BoundsTilesPrepareParams {
+    const ChordBoundsResult* results; const ChordBoundsQuery* queries;      // queries: read by FAR only
+    uint32_t* stepCounts; uint32_t* recordCount; uint4* records; uint32_t* recordIndex;
+    uint32_t* totals;                      // null: not wanted; [0] = the number of records
+    uint32_t count;
+};
+
+__device__ __forceinline__ bool bounds_tiles_takes_part(uint32_t status)
+{
+    return (status & (CHORD_BOUNDS_IN_FRUSTUM | CHORD_BOUNDS_UNOCCLUDED)) == (CHORD_BOUNDS_IN_FRUSTUM | CHORD_BOUNDS_UNOCCLUDED);
+}
+
+__global__ __launch_bounds__(256) void bounds_tiles_count_kernel(const BoundsTilesPrepareParams a)
+{
+    const uint32_t steps = a.count / 256u + (a.count % 256u ? 1u : 0u);                 // (no wrap at any count)
+    for (uint32_t step = blockIdx.x; step < steps; step += gridDim.x) {
+        const uint32_t i = step * 256u + threadIdx.x;
+        uint32_t total;
+        (void)block_excl_scan(i < a.count && bounds_tiles_takes_part(a.results[i].status) ? 1u : 0u, &total);
+        if (threadIdx.x == 0u) a.stepCounts[step] = total;
+    }
+}
+
+template <int PHASE>
+__device__ __forceinline__ float bounds_tiles_far_z(const ChordBoundsQuery* __restrict__ query, const DView& dv)
+{
+    const float4* __restrict__ rec = reinterpret_cast<const float4*>(query);
+    const Mat4 M = load_mat_vec4(rec + (PHASE == 0 ? 4 : 0));
+    const float4 lo = rec[8], hi = rec[9];
+    const float posMin[3] = {lo.x, lo.y, lo.z}, posMax[3] = {hi.x, hi.y, hi.z};
+    const Mat4 mvp = PHASE == 0 ? obj_mvp_last(M, dv) : obj_mvp(M, dv);
+    f3 c, e;
+    aabb_center_extent(posMin, posMax, c, e);
+    float z = 10.0f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) z = fminf(z, project_pos_to_uvz(extent_corner(c, e, k), mvp).z);
+    return z;
+}
+
+template <int PHASE, bool FAR>
+__global__ __launch_bounds__(256) void bounds_tiles_prepare_kernel(const BoundsTilesPrepareParams a, const DView dv)
+{
+    const uint32_t steps = a.count / 256u + (a.count % 256u ? 1u : 0u);
+    uint32_t total;
+    // `at` walks with the loop, as bounds_scatter_kernel's does
+    uint32_t at = 0u, summed = 0u;
+    for (uint32_t step = blockIdx.x; step < steps; step += gridDim.x) {
+        uint32_t part = 0u;
+        for (uint32_t g = summed + threadIdx.x; g < step; g += 256u) part += a.stepCounts[g];
+        (void)block_excl_scan(part, &total);
+        at += total; summed = step;
+        const uint32_t i = step * 256u + threadIdx.x;
+        uint4 res = make_uint4(0u, 0u, 0u, 0u);
+        if (i < a.count) res = *reinterpret_cast<const uint4*>(a.results + i);
+        const bool in = bounds_tiles_takes_part(res.x);
+        const uint32_t slot = at + block_excl_scan(in ? 1u : 0u, &total);
+        if (in) {
+            float farZ = 0.0f;
+            if (FAR && !(res.x & CHORD_BOUNDS_NEAR)) farZ = bounds_tiles_far_z<PHASE>(a.queries + i, dv);
+            a.records[slot] = make_uint4(res.z, res.w, res.y, __float_as_uint(farZ));
+            a.recordIndex[slot] = i;
+        }
+    }
+    if (blockIdx.x == 0u) {
+        uint32_t part = 0u;
+        for (uint32_t g = threadIdx.x; g < steps; g += 256u) part += a.stepCounts[g];
+        (void)block_excl_scan(part, &total);
+        if (threadIdx.x == 0u) { *a.recordCount = total; if (a.totals) a.totals[0] = total; }
+    }
+}
+
+void launch_bounds_tiles_prepare(ChordCtx* c, const ChordBoundsTilesDesc& desc, const ChordBoundsResult* results, const ChordBoundsQuery* queries,
+                                 uint32_t count, uint32_t* scratch, uint32_t* totals)
+{
+    BoundsTilesPrepareParams a;
+    a.results = results; a.queries = queries; a.count = count; a.totals = totals;
+    const uint32_t blocks = bounds_tiles_blocks(c->width, c->height);
+    a.recordCount = scratch; a.stepCounts = scratch + bounds_tiles_steps_at(blocks);
+    a.records = reinterpret_cast<uint4*>(scratch + bounds_tiles_records_at(count, blocks));
+    a.recordIndex = reinterpret_cast<uint32_t*>(a.records + count);
+    const uint32_t steps = count / 256u + (count % 256u ? 1u : 0u);
+    // (debug bit 33554432: two workgroups, so that short lists walk the grid-stride loops)
+    const uint32_t cap = (c->debugFlags & 33554432u) ? 2u : (uint32_t)c->numCUs * 8u;
+    const dim3 grid(std::max(1u, std::min(steps, cap)));
+    CHORD_LAUNCH(c, bounds_tiles_count_kernel, grid, dim3(256), 0, c->stream, a);
+    const bool farSide = (desc.flags & CHORD_BOUNDS_TILES_FAR) != 0u;
+    if (!farSide)             CHORD_LAUNCH(c, (bounds_tiles_prepare_kernel<1, false>), grid, dim3(256), 0, c->stream, a, c->hView);
+    else if (desc.phase == 0) CHORD_LAUNCH(c, (bounds_tiles_prepare_kernel<0, true>), grid, dim3(256), 0, c->stream, a, c->hView);
+    else                      CHORD_LAUNCH(c, (bounds_tiles_prepare_kernel<1, true>), grid, dim3(256), 0, c->stream, a, c->hView);
 }
 
 } // namespace chord

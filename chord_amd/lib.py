@@ -135,6 +135,16 @@ class BoundsResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("nearestZ", C.c_float), ("rect", C.c_uint16 * 4)]
 
 
+class BoundsTilesDesc(C.Structure):
+    """ChordBoundsTilesDesc: tile size, list stride, phase and depth tests of chordvis_bin_bounds (numpy: records.BOUNDS_TILES_DESC)."""
+    _fields_ = [("tileSize", C.c_uint32), ("maxPerTile", C.c_uint32), ("phase", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BoundsTiles(C.Structure):
+    """ChordBoundsTiles: chordvis_bin_bounds' four outputs, device pointers or None (numpy: records.BOUNDS_TILES)."""
+    _fields_ = [("tileCounts", C.c_void_p), ("tileItems", C.c_void_p), ("tileDepth", C.c_void_p), ("totals", C.c_void_p)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [
         ("position", C.c_double * 3), ("front", C.c_double * 3), ("worldUp", C.c_double * 3),
@@ -298,6 +308,8 @@ def _load():
         "chordvis_visible_clusters": (i32, [vp, CountAndCmd, vp, vp, u32]),
         "chordvis_geometry_feedback_seen": (i32, [vp, vp, u32]),
         "chordvis_query_bounds": (i32, [vp, P(HZB), i32, vp, u32, vp, vp, vp, u32]),
+        "chordvis_bounds_tile_count": (u32, [u32, u32, u32, P(u32), P(u32)]),
+        "chordvis_bin_bounds": (i32, [vp, P(BoundsTilesDesc), vp, vp, u32, P(BoundsTiles)]),
         "chordvis_set_texture_first_level": (i32, [vp, P(u32), u32]),
         "chordvis_texture_first_level": (i32, [vp, u32, P(u32)]),
         "chordvis_material_texture_levels": (i32, [vp, u32, P(u32), P(u32)]),

@@ -100,6 +100,12 @@ assert BOUNDS_QUERY.itemsize == 160 and BOUNDS_RESULT.itemsize == 16
 BOUNDS_IN_FRUSTUM, BOUNDS_UNOCCLUDED, BOUNDS_NEAR, BOUNDS_OFFSCREEN, BOUNDS_EMPTY_RECT = 1, 2, 4, 8, 16
 BOUNDS_LEVEL_SHIFT, BOUNDS_LEVEL_MASK = 8, 0xF
 
+# chordvis_bin_bounds (ChordBoundsTilesDesc / ChordBoundsTiles: four device pointers)
+BOUNDS_TILES_DESC = np.dtype([("tileSize", u32), ("maxPerTile", u32), ("phase", u32), ("flags", u32)])
+BOUNDS_TILES = np.dtype([("tileCounts", np.uint64), ("tileItems", np.uint64), ("tileDepth", np.uint64), ("totals", np.uint64)])
+assert BOUNDS_TILES_DESC.itemsize == 16 and BOUNDS_TILES.itemsize == 32
+BOUNDS_TILES_NEAR, BOUNDS_TILES_FAR = 1, 2
+
 HZB_MAX_MIPS = 12
 
 

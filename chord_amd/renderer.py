@@ -275,6 +275,57 @@ class VisibilityRenderer:
         indices = vis.cpu().numpy().view(np.uint32)[:listed].copy() if vis is not None else np.zeros(0, dtype=np.uint32)
         return results, indices, total
 
+    def bin_bounds(self, results, queries=None, tile_size=16, max_per_tile=0, phase=1, flags=0, want_counts=True, want_depth=True,
+                   want_totals=True, item_fill=0xFFFFFFFF):
+        """chordvis_bin_bounds: the visible boxes of a bounds query binned into screen tiles of tile_size pixels.  results: a numpy
+        array of records.BOUNDS_RESULT (what query_bounds returned), or a contiguous CUDA tensor of such records (16 bytes each) on
+        the context's device; queries (needed by records.BOUNDS_TILES_FAR only): records.BOUNDS_QUERY, likewise.  Returns a dict, read
+        back: tiles (tilesX, tilesY); counts uint32[tiles] (None unless want_counts); items uint32[tiles, max_per_tile] (None when
+        max_per_tile is 0) -- row t holds min(counts[t], max_per_tile) ascending query indices, the words behind them keep
+        item_fill --; depth uint32[tiles, 2], far and near bits (None unless want_depth); totals uint32[4] (None unless want_totals).
+        The call is ordered behind the current torch stream and that one behind the call (as query_bounds does it); a caller's
+        tensor handed in has the context's stream recorded on it, so release it before close()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def records(a, dtype, what):
+            if a is None:
+                return None, 0
+            if isinstance(a, np.ndarray):
+                host = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+                with torch.cuda.device(dev):
+                    t = torch.from_numpy(host.view(np.uint8).copy()).to(dev) if len(host) else torch.zeros(16, dtype=torch.uint8, device=dev)
+                return t, len(host)
+            nbytes = a.numel() * a.element_size()
+            assert a.is_cuda and a.is_contiguous() and nbytes % dtype.itemsize == 0, "bin_bounds: %s: a contiguous CUDA tensor of %d-byte records" % (what, dtype.itemsize)
+            return a, nbytes // dtype.itemsize
+
+        res, count = records(results, R.BOUNDS_RESULT, "results")
+        qry, qcount = records(queries, R.BOUNDS_QUERY, "queries")
+        assert qry is None or qcount == count, "bin_bounds: results and queries belong together"
+        tx, ty = C.c_uint32(0), C.c_uint32(0)
+        tiles = int(L.lib.chordvis_bounds_tile_count(self.width, self.height, int(tile_size), C.byref(tx), C.byref(ty)))
+        max_per_tile = int(max_per_tile)
+        with torch.cuda.device(dev):
+            cnt = torch.zeros(max(tiles, 1), dtype=torch.int32, device=dev) if want_counts else None
+            fill = int(np.uint32(item_fill).view(np.int32))
+            items = torch.full((max(tiles * max_per_tile, 1),), fill, dtype=torch.int32, device=dev) if max_per_tile else None
+            depth = torch.zeros(max(2 * tiles, 1), dtype=torch.int32, device=dev) if want_depth else None
+            totals = torch.zeros(4, dtype=torch.int32, device=dev) if want_totals else None
+        desc = L.BoundsTilesDesc(int(tile_size), max_per_tile, int(phase), int(flags))
+        out = L.BoundsTiles(*(t.data_ptr() if t is not None else None for t in (cnt, items, depth, totals)))
+        used = [t for t in (res, qry, cnt, items, depth, totals) if t is not None]
+        self._on_my_stream(used, lambda: self._check(L.lib.chordvis_bin_bounds(
+            self._ctx, C.byref(desc), res.data_ptr() if res is not None and count else None,
+            qry.data_ptr() if qry is not None else None, count, C.byref(out)), "bin_bounds"))
+        self.sync()
+        host = lambda t, n: t.cpu().numpy().view(np.uint32)[:n].copy() if t is not None else None
+        got_items = host(items, tiles * max_per_tile)
+        got_depth = host(depth, 2 * tiles)
+        return dict(tiles=(tx.value, ty.value), counts=host(cnt, tiles),
+                    items=got_items.reshape(tiles, max_per_tile) if got_items is not None else None,
+                    depth=got_depth.reshape(tiles, 2) if got_depth is not None else None, totals=host(totals, 4))
+
     def texture_mips(self, texture):
         """(levels, flags, alphaCutoff8, pad) set for a texture id; zeros where nothing is set."""
         m = L.TextureMips()

@@ -882,6 +882,51 @@ int chordvis_query_bounds(ChordCtx* ctx, const ChordHZB* hzb /* NULL: frustum on
                           uint32_t* deviceVisible               /* [capacity] query indices, or NULL when capacity == 0 */,
                           uint32_t* deviceVisibleCount          /* one word, or NULL */,
                           uint32_t capacity);
+/* Bounds tile lists -- the per-tile answer to the question chordvis_query_bounds answers for the whole screen: which of the visible
+ * boxes can touch the pixels of each screen tile (the tile list of tiled deferred lighting, of decal and fog-volume application).
+ * `count` ChordBoundsResult records in device memory in -- what chordvis_query_bounds wrote, or records the host made --, per tile the
+ * number and the ascending indices of the boxes kept, the tile's depth bounds, and four totals out.  
+ *   1. Image.  The row-major (resolved) visibility image chordvis_visibility_mark reads, waited for the same way; a rank of a sharded
+ *      context bins the whole resolved image.  A pixel's depth word is the high 32 bits of its word; depth is reverse-Z and an empty
+ *      pixel is 0, as chordvis_clear_gbuffer leaves it.  The low word is never looked at.
+ *   2. Tiles.  T = desc->tileSize; tilesX = ceil(W / T), tilesY = ceil(H / T) (chordvis_bounds_tile_count); tile t = ty * tilesX + tx
+ *      owns the pixels [tx T, min(W, tx T + T)) x [ty T, min(H, ty T + T)).  far(t) is the unsigned minimum of the tile's depth words,
+ *      near(t) the unsigned maximum: the image is assumed to hold non-negative, non-NaN depths, as every raster path writes, so the
+ *      order of the bits is the order of the floats.  tileDepth[2 t] = far(t), tileDepth[2 t + 1] = near(t).
+ *   3. Participation.  Query i < count takes part when its status has both CHORD_BOUNDS_IN_FRUSTUM and CHORD_BOUNDS_UNOCCLUDED.
+ *   4. Pair test.  A query that takes part is kept in tile t when all of these hold:
+ *        rectangle   rect[0] <= x1 && rect[2] >= x0 && rect[1] <= y1 && rect[3] >= y0, with (x0, y0) the tile's first and (x1, y1) its
+ *                    last pixel (a rectangle that reaches past the image overlaps nothing there);
+ *        near side   with CHORD_BOUNDS_TILES_NEAR: not nearestZ < asfloat(far(t)) -- rejected is a box whose nearest point lies behind
+ *                    every surface of the tile; a CHORD_BOUNDS_NEAR record (nearestZ == 1.0f) is therefore always kept;
+ *        far side    with CHORD_BOUNDS_TILES_FAR: not farZ(i) > asfloat(near(t)) -- rejected is a box that ends in front of every
+ *                    surface of the tile.  farZ(i) is 0.0f for a record with CHORD_BOUNDS_NEAR set; otherwise it is the smallest
+ *                    projected z of the eight corners of deviceQueries[i]'s box -- the mn.z of the main view's occlusion test: fminf,
+ *                    from 10.0f, in corner order -- under rule 2 of chordvis_query_bounds' mvp for desc->phase and the host copy of
+ *                    the last chordvis_set_view.  A tile of empty pixels (near(t) == 0) under FAR keeps only the CHORD_BOUNDS_NEAR
+ *                    records: by design -- there is nothing to shade there.
+ *   5. Outputs, each optional (NULL), at least one given.  tileCounts[t] = the number of queries kept, even beyond maxPerTile.
+ *      tileItems[t * maxPerTile + k], k < min(tileCounts[t], maxPerTile), = the kept queries' indices in ASCENDING order; no other word
+ *      of tileItems is written.  The order is part of the contract and does not depend on scheduling.  totals[0] = the queries that
+ *      take part, totals[1] = the sum of tileCounts (modulo 2^32), totals[2] = the tiles with tileCounts > maxPerTile, totals[3] = the
+ *      largest tileCounts.
+ *   6. Stream, state and launches.  Runs on the context's stream and returns without synchronising.  Needs an allocated G-buffer and a
+ *      set view; no scene.  Touches neither the frame's lists and counts, chordvis_stats' counters nor the history.  count == 0
+ *      succeeds: zero counts and totals, and tileDepth if asked.  Three launches, four with totals: two put the records that take part
+ *      (rectangle, nearestZ, farZ, index) into a scratch of the context's in ascending order, one reduces the tiles' depth bounds and
+ *      bins, one folds the totals; with count == 0, or when only tileDepth is asked for, the third alone (and a 16-byte memset when
+ *      totals is given).  The scratch grows on demand and is freed with the context.
+ *   7. The caller's part.  Results and queries belong together: the same array order, the same phase, the same view.
+ *   8. CHORDVIS_E_INVALID, chordvis_last_error naming the rule: desc or out NULL; all four outputs NULL; tileSize not 8, 16, 32 or 64;
+ *      unknown flag bits; phase not 0 or 1; FAR without deviceQueries; count > 0 with deviceResults NULL; tileItems with
+ *      maxPerTile == 0; tiles * maxPerTile beyond 2^32 - 1; deviceResults or deviceQueries not 16-byte aligned; no G-buffer allocated;
+ *      no view set; a view whose ChordCameraView::renderDimension or ChordInstanceCullingView::renderDimension differs from the
+ *      image's size. */
+uint32_t chordvis_bounds_tile_count(uint32_t width, uint32_t height, uint32_t tileSize,
+                                    uint32_t* tilesX, uint32_t* tilesY);   /* tilesX * tilesY; 0 for a tileSize not allowed */
+int chordvis_bin_bounds(ChordCtx* ctx, const ChordBoundsTilesDesc* desc,
+                        const ChordBoundsResult* deviceResults, const ChordBoundsQuery* deviceQueries /* NULL unless FAR */,
+                        uint32_t count, const ChordBoundsTiles* out);
 /* The G-buffer in the reference's packed image formats -- what exportGbuffer (lighting.hlsl:62-73) writes into GBufferTextures
  * (render_textures.h:27-49) and every later pass reads: 28 bytes per pixel for the six images, where the float images of
  * chordvis_resolve_material take 88.  The packing is pinned; float32, source order, unfused; R in the low bits:
@@ -984,7 +1029,9 @@ int chordvis_stats(ChordCtx* ctx, ChordStats* out);
  * chordvis_material_feedback's workgroups use 2 entries of their on-chip count tables instead of 512, so that most adds find
  * the table full and go to global memory (the same counts, slower), 8388608 chordvis_geometry_feedback's workgroups likewise use
  * 2 entries of their count tables instead of 1024, 16777216 chordvis_query_bounds launches grids of at most two workgroups, so that
- * short lists walk the grid-stride loops of its kernels. */
+ * short lists walk the grid-stride loops of its kernels, 33554432 chordvis_bin_bounds likewise launches grids of at most two
+ * workgroups and streams its records in chunks of 64 instead of 256, so that small counts walk every loop and chunk boundary of its
+ * kernels (the same results). */
 int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 /* measurement / test aid: fills EVERY rank's chunk of the cull exchange buffer on this context for the current view (what the
  * all-gather would deliver), so that one rank of a sharded frame can be timed alone on one device (tools/shard_time.py) */

@@ -305,8 +305,27 @@ typedef struct ChordBoundsResult {              /* 16 bytes, 16-byte aligned */
     uint16_t rect[4];       /* rx, ry, rz, rw: the inclusive pixel rectangle the test formed; (0, 0, W-1, H-1) with NEAR */
 } ChordBoundsResult;
 
+/* chordvis_bin_bounds (chordvis.h): the visible boxes of a ChordBoundsResult array binned into screen tiles. */
+#define CHORD_BOUNDS_TILES_NEAR 1u   /* near-side depth test on */
+#define CHORD_BOUNDS_TILES_FAR  2u   /* far-side depth test on (needs deviceQueries) */
+
+typedef struct ChordBoundsTilesDesc {           /* 16 bytes */
+    uint32_t tileSize;     /* 8, 16, 32 or 64 pixels */
+    uint32_t maxPerTile;   /* stride of tileItems per tile; 0 allowed only when tileItems is NULL */
+    uint32_t phase;        /* 0 or 1: the phase the results were made with (read by the far side only) */
+    uint32_t flags;        /* CHORD_BOUNDS_TILES_*; other bits refused */
+} ChordBoundsTilesDesc;
+
+typedef struct ChordBoundsTiles {               /* caller-owned DEVICE memory, NULL = not wanted; at least one non-NULL */
+    uint32_t* tileCounts;  /* [tiles]               */
+    uint32_t* tileItems;   /* [tiles * maxPerTile]  */
+    uint32_t* tileDepth;   /* [tiles * 2]: far bits, near bits */
+    uint32_t* totals;      /* [4] */
+} ChordBoundsTiles;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(ChordBoundsTilesDesc) == 16, "ChordBoundsTilesDesc");
 static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
 static_assert(sizeof(ChordBoundsResult) == 16, "ChordBoundsResult");
 static_assert(sizeof(ChordMeshlet) == 64, "GPUGLTFMeshlet");
