@@ -222,7 +222,10 @@ int chordvis_sync(ChordCtx* ctx);
 /* GPUScene / asset upload (gpu_scene.h:20-165, asset_gltf.h:278): copies and flattens.  Limits of a scene (CHORDVIS_E_INVALID
  * beyond them): 0x55555555 vertices over all assets (vertex index x 3 is formed in 32 bits; the reference's ByteAddressBuffer
  * offsets are 32-bit BYTE offsets, a third of that), meshlets of at most 255 vertices / 128 triangles, groups of at most four
- * meshlets, alpha-tested textures of at most 16384 x 16384 texels and 15 levels. */
+ * meshlets, alpha-tested textures of at most 16384 x 16384 texels and 15 levels.  A ChordMeshlet of ANY vertex count V <= 255 and
+ * triangle count T <= 128 whose triangle words name local indices below V is accepted -- V need not be bounded by T (disjoint
+ * triangles: V up to 3T), the vertex-id table need not ascend, meshlets may share vertices, T may be 0 -- and every such shape is
+ * held to the oracle through each set-up kernel, the clipper, the depth-only pass and the resolve (tests/test_gpu_meshlet_shapes.py). */
 int chordvis_upload_scene(ChordCtx* ctx, const ChordSceneDesc* scene);
 /* uploadBufferToGPU("GLTFObjectInfo", ...) renderer.cpp:229 — per-frame object records
  * (count must equal the uploaded scene's objectCount; primitive/material ids must not change). */
