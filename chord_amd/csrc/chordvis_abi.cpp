@@ -447,6 +447,12 @@ int ready(ChordCtx* c, const char* fn)
         std::snprintf(buf, sizeof(buf), "%s: upload_scene, allocate_gbuffer and set_view must come first", fn);
         return fail(c, CHORDVIS_E_INVALID, buf);
     }
+    if (!chord::view_fits_target(c)) {
+        // (chordvis_set_view holds a view to the target it meets; chordvis_allocate_gbuffer may have come after it)
+        char buf[224];
+        std::snprintf(buf, sizeof(buf), "%s: the view's renderDimension differs from the allocated gbuffer (chordvis_set_view must follow a chordvis_allocate_gbuffer of another size)", fn);
+        return fail(c, CHORDVIS_E_INVALID, buf);
+    }
     return CHORDVIS_OK;
 }
 
@@ -704,7 +710,25 @@ int chordvis_sync(ChordCtx* c)
 
 // -------------------------------------------------------------------------------------- scene --
 
+static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s);
+
+// A refused upload leaves NO scene behind (include/chordvis.h): the host tables and device buffers are replaced one by one, so
+// after a failure part of them may be the new scene's and part the old one's.
 int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
+{
+    const int rc = upload_scene_impl(c, s);
+    if (rc && c) {
+        c->sceneLoaded = false;
+        if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }   // (it aliases scene buffers that may be gone)
+        c->shadowHistoryValid = false;
+        c->resolveFrame = false;
+        c->historySlot = 0; c->pendingTailSlot = 0;
+        c->fullListStale = false; c->mineValid = false; c->cullPhaseDone = false;
+    }
+    return rc;
+}
+
+static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
 {
     if (c) c->orderAge = c->orderAge1 = 0xFFFFFFFFu;                    // (the kept tile schedule of launch_raster is made again)
 
@@ -1431,6 +1455,7 @@ int chordvis_bind_objects(ChordCtx* c, const ChordObject* deviceObjects, uint32_
 {
     if (!c || !c->sceneLoaded || !deviceObjects || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "bind_objects: count must equal the uploaded scene's objectCount");
     c->dObjects = deviceObjects;
+    c->resolveStale = true;                               // (like chordvis_update_objects: the array a resolve would read is no longer the frame's)
     return CHORDVIS_OK;
 }
 
@@ -1439,10 +1464,11 @@ int chordvis_set_view(ChordCtx* c, const ChordCameraView* view, const ChordInsta
     if (!c || !view || !iv) return fail(c, CHORDVIS_E_INVALID, "set_view: null argument");
     // (the rank masks on their way through the all-gather were computed with the current view, cull mode and tile map)
     if (c->cullPhaseDone) return fail(c, CHORDVIS_E_INVALID, "set_view: not between chordvis_frame_phase_cull and chordvis_frame_phase_a");
+    // (refused before anything is taken over: the view set before stays the context's)
+    if (c->dVis && ((uint32_t)iv->renderDimension[0] != c->width || (uint32_t)iv->renderDimension[1] != c->height))
+        return fail(c, CHORDVIS_E_INVALID, "set_view: renderDimension differs from the allocated gbuffer");
     c->hView.view = *view; c->hView.iv = *iv; c->hView.flags = switchFlags;
     c->hView.width = (uint32_t)iv->renderDimension[0]; c->hView.height = (uint32_t)iv->renderDimension[1];
-    if (c->dVis && (c->hView.width != c->width || c->hView.height != c->height))
-        return fail(c, CHORDVIS_E_INVALID, "set_view: renderDimension differs from the allocated gbuffer");
     // the 600-byte constant block travels as a kernel argument of the frame's first kernel (object_cull),
     // which publishes it for the later passes; see flush_view() for passes called out of frame order
     c->viewDirty = true;
@@ -1458,6 +1484,7 @@ int chordvis_allocate_gbuffer(ChordCtx* c, uint32_t width, uint32_t height, uint
     CHORD_HIP(c, hipSetDevice(c->device));
     c->width = width; c->height = height;
     dfree(c->dTileMarker); dfree(c->dShadingTiles);                             // sized by the render size; re-made on demand
+    // (a view of another size stays set but no longer fits: ready() refuses the passes until chordvis_set_view has come again)
     return configure_targets(c, deviceVisibility);
 }
 
@@ -2070,7 +2097,7 @@ static int resolve_checks(ChordCtx* c, const char* fn, ChordCountAndCmd drawed, 
     auto refuse = [&](const char* why) { std::snprintf(buf, sizeof(buf), "%s: %s", fn, why); return fail(c, CHORDVIS_E_INVALID, buf); };
     if (!c || !c->dVis || !c->sceneLoaded) return refuse("no scene / gbuffer");
     if (!c->resolveFrame) return refuse("no frame rendered yet");
-    if (c->resolveStale) return refuse("chordvis_update_objects / chordvis_set_view came after the frame (the image's matrices are gone)");
+    if (c->resolveStale) return refuse("chordvis_update_objects / chordvis_bind_objects / chordvis_set_view came after the frame (the image's matrices are gone)");
     if (!drawed.count || !drawed.cmds) return refuse("null command list");
     if (!anyTarget) return refuse("no target");
     if (wantDebug && d.debugMode > CHORD_NANITE_DEBUG_BARYCENTRICS) return refuse("debugMode beyond 4");
@@ -2550,6 +2577,9 @@ int chordvis_prepare_shading_tile_param(ChordCtx* c, uint32_t shadingType, const
 {
     if (!c || !marker || !out || !marker->marker || marker->marker != c->dTileMarker)
         return fail(c, CHORDVIS_E_INVALID, "prepare_shading_tile_param: marker is not this context's");
+    // (a handle from before chordvis_allocate_gbuffer may carry the address of the new marker: its dims place the count behind the list)
+    if (marker->markerDim[0] != (c->width + 7u) / 8u || marker->markerDim[1] != (c->height + 7u) / 8u)
+        return fail(c, CHORDVIS_E_INVALID, "prepare_shading_tile_param: the marker was made for another render size (call chordvis_visibility_mark again)");
     if (shadingType >= 128u) return fail(c, CHORDVIS_E_INVALID, "prepare_shading_tile_param: shading type does not fit the 128-bit marker");
     const uint32_t total = marker->markerDim[0] * marker->markerDim[1];
     uint32_t* count = c->dShadingTiles + (size_t)total * 2;

@@ -53,6 +53,7 @@ int chordvis_allocate_depth_views(ChordCtx* c, uint32_t dim, uint32_t viewCount)
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }
     for (float*& d : c->dDepthImages) if (d) { (void)hipFree(d); d = nullptr; }
     c->fusedDepthView = -1;                               // (the child's chain 0 goes with the child: no image of the new views is in it)
+    c->shadowHistoryValid = false;                        // (bCacheValid, :367-371, wants depth images that exist: the new ones were never rendered)
     ChordCtx* k = nullptr;
     int rc = chordvis_create(c->device, c->stream, &k);
     if (rc) return fail(c, rc, "allocate_depth_views: child context");
@@ -106,6 +107,7 @@ int chordvis_instance_culling_view(ChordCtx* c, uint32_t instanceViewOffset, Cho
     int rc = need_child(c, "instance_culling_view");
     if (rc) return rc;
     if (!c->viewSet) return fail(c, CHORDVIS_E_INVALID, "instance_culling_view: set_view (the main camera: the LOD cut uses it) must come first");
+    if (!view_fits_target(c)) return fail(c, CHORDVIS_E_INVALID, "instance_culling_view: the main view's renderDimension differs from the allocated gbuffer (set_view must follow allocate_gbuffer)");
     if (instanceViewOffset >= c->instanceViews.size()) return fail(c, CHORDVIS_E_INVALID, "instance_culling_view: instanceViewOffset beyond set_instance_views");
     ChordCtx* k = c->depthCtx;
     const ChordInstanceCullingView& iv = c->instanceViews[instanceViewOffset];
@@ -207,6 +209,7 @@ int chordvis_build_hzb_from_depth(ChordCtx* c, const ChordDepthTarget* depth, Ch
     if (!depth || !depth->depth || depth->width != k->width || depth->height != k->height)
         return fail(c, CHORDVIS_E_INVALID, "build_hzb_from_depth: not a depth target of this context's depth views");
     k->viewSet = true;
+    k->hView.width = k->width; k->hView.height = k->height;          // (no chordvis_instance_culling_view need have come: the build reads no view)
     if (c->fusedDepthView >= 0 && (size_t)c->fusedDepthView < c->dDepthImages.size() && depth->depth == c->dDepthImages[c->fusedDepthView]) {
         // the image came straight out of chordvis_render_mesh_depth: levels 0..5 of its min chain are already in chain 0
         // (tile kernel); the one-block tail finishes it -- the values chordvis_build_hzb computes from the image
@@ -239,6 +242,7 @@ int chordvis_render_shadow(ChordCtx* c, const ChordCascadeConfig* cfg, const flo
 {
     if (!c || !cfg || !lightDir) return fail(c, CHORDVIS_E_INVALID, "render_shadow: null argument");
     if (!c->viewSet || !c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "render_shadow: upload_scene and set_view (the main camera) must come first");
+    if (!view_fits_target(c)) return fail(c, CHORDVIS_E_INVALID, "render_shadow: the main view's renderDimension differs from the allocated gbuffer (set_view must follow allocate_gbuffer)");
     if (cfg->cascadeCount < 1 || (uint32_t)cfg->cascadeCount > CHORD_MAX_CASCADES || cfg->realtimeCascadeCount < 0 || cfg->realtimeCascadeCount > cfg->cascadeCount)
         return fail(c, CHORDVIS_E_INVALID, "render_shadow: cascade counts out of range");
     const uint32_t count = (uint32_t)cfg->cascadeCount, realtime = (uint32_t)cfg->realtimeCascadeCount;

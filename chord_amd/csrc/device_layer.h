@@ -582,7 +582,7 @@ struct ChordCtx {
     chord::ClipTri* dClipTris = nullptr;
     uint32_t clipTriCap = 0;
     bool resolveFrame = false;         // a raster pass of the main view has written the image since the last upload / gbuffer (chordvis_resolve_attributes)
-    bool resolveStale = false;         // ... and chordvis_update_objects / chordvis_set_view came after it: the image's matrices are gone
+    bool resolveStale = false;         // ... and chordvis_update_objects / chordvis_bind_objects / chordvis_set_view came after it: the image's matrices are gone
     uint32_t* dTileMarker = nullptr;   // [markerDim.y][markerDim.x] uint4: shading types present per 8x8 pixels
     uint32_t* dShadingTiles = nullptr; // [markerDim.x * markerDim.y] uint2 + {count, pad, uint4 dispatch args} behind them
     uint32_t* dTileOrder = nullptr;    // [1 + tileItemCap]: item count, then work items heaviest first
@@ -635,6 +635,9 @@ struct ChordCtx {
 namespace chord {
 
 int fail(ChordCtx* ctx, int code, const char* what, hipError_t e = hipSuccess);
+// the view chordvis_set_view left is of the allocated target's size (chordvis_allocate_gbuffer of another size may have come after
+// it); without a target there is nothing to fit
+inline bool view_fits_target(const ChordCtx* c) { return !c->dVis || (c->hView.width == c->width && c->hView.height == c->height); }
 int alloc_scene_work_buffers(ChordCtx* c);
 
 #define CHORD_HIP(ctx, call)                                                         \

@@ -225,13 +225,24 @@ int chordvis_sync(ChordCtx* ctx);
  * meshlets, alpha-tested textures of at most 16384 x 16384 texels and 15 levels.  A ChordMeshlet of ANY vertex count V <= 255 and
  * triangle count T <= 128 whose triangle words name local indices below V is accepted -- V need not be bounded by T (disjoint
  * triangles: V up to 3T), the vertex-id table need not ascend, meshlets may share vertices, T may be 0 -- and every such shape is
- * held to the oracle through each set-up kernel, the clipper, the depth-only pass and the resolve (tests/test_gpu_meshlet_shapes.py). */
+ * held to the oracle through each set-up kernel, the clipper, the depth-only pass and the resolve (tests/test_gpu_meshlet_shapes.py).
+ * A context may take scene after scene.  An upload drops what belonged to the scene before: the history HZB (the next frame is a
+ * frame without history), the kept tile schedules, the depth views and the cascade cache, the material textures and the geometry
+ * feedback, and objects bound with chordvis_bind_objects (the library's copy of the new scene's objects is read again).  The
+ * G-buffer, the view, the cull mode, the debug switches and the limits stay.
+ * A REFUSED upload (any error code, the refusal of a scene without BVHs under chordvis_set_cull_mode(ctx, 1) included) leaves the
+ * context with NO scene: the scene before is gone too, and every call that needs a scene returns CHORDVIS_E_INVALID until an upload
+ * succeeds.  The G-buffer and every setting stay, so that upload may follow at once (after chordvis_set_cull_mode(ctx, 0), say). */
 int chordvis_upload_scene(ChordCtx* ctx, const ChordSceneDesc* scene);
 /* uploadBufferToGPU("GLTFObjectInfo", ...) renderer.cpp:229 — per-frame object records
  * (count must equal the uploaded scene's objectCount; primitive/material ids must not change). */
 int chordvis_update_objects(ChordCtx* ctx, const ChordObject* hostObjects, uint32_t count);
-/* Same, for a caller-owned DEVICE array (no copy; must stay valid while bound, and unchanged from a frame until
- * chordvis_resolve_attributes of that frame has run). */
+/* Same, for a caller-owned DEVICE array (no copy; must stay valid while bound).  The array stays bound -- the depth views read
+ * it too -- until chordvis_update_objects or chordvis_upload_scene returns the context to its own copy.  The caller may rewrite
+ * the array between frames without telling the library, ordered behind the context's stream; what the library cannot see it
+ * cannot check, so between a frame and the chordvis_resolve_* calls on that frame's image the CALLER guarantees that the array
+ * is not written.  The call itself counts as a change of the objects, exactly like chordvis_update_objects: a chordvis_resolve_*
+ * after it is refused (CHORDVIS_E_INVALID) until the next frame has run -- also when the same array is bound again. */
 int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint32_t count);
 
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
@@ -261,7 +272,14 @@ uint32_t chordvis_tile_schedule_keep(ChordCtx* ctx);
 
 /* allocateGBufferTextures (render_textures.cpp:20-45): size the visibility target.  deviceVisibility
  * may be a caller-owned device buffer of chordvis_visibility_words(ctx) uint64 (used for the
- * multi-GPU all-gather), or NULL for a context-owned one. */
+ * multi-GPU all-gather), or NULL for a context-owned one.
+ * May be called again on a live context, with any size and either kind of buffer.  Everything sized by the target or made for
+ * it goes: the history HZB (chordvis_history_hzb is refused until a frame has run; that frame is one without history), the kept
+ * tile schedules and the passes' reports, handles of tile markers and shading-tile lists (chordvis_prepare_shading_tile_param
+ * refuses a marker made for another size).  A view of another renderDimension no longer fits: until chordvis_set_view has come
+ * with the new size, the passes, chordvis_render_frame, the frame phases, chordvis_instance_culling_view and
+ * chordvis_render_shadow are refused (CHORDVIS_E_INVALID), and a chordvis_set_view with any other size is refused and changes
+ * nothing.  The scene, bound objects, the depth views and the cascade cache (which depend on the view, not on the size) stay. */
 int chordvis_allocate_gbuffer(ChordCtx* ctx, uint32_t width, uint32_t height, uint64_t* deviceVisibility);
 
 int chordvis_set_limits(ChordCtx* ctx, const ChordLimits* limits);
@@ -453,7 +471,9 @@ typedef struct ChordDepthTarget {     /* a VK_FORMAT_D32_SFLOAT image (mesh_rast
     float*   depth;
     uint32_t width, height;
 } ChordDepthTarget;
-/* after upload_scene: targets + work lists for `viewCount` views of dim x dim pixels */
+/* after upload_scene: targets + work lists for `viewCount` views of dim x dim pixels.  Called again -- with the same dim and count
+ * too -- it makes new, empty images and drops the cascade cache of chordvis_render_shadow with the old ones (bCacheValid,
+ * mesh_raster.cpp:367-371, wants depth images that exist): the next chordvis_render_shadow renders every cascade. */
 int chordvis_allocate_depth_views(ChordCtx* ctx, uint32_t dim, uint32_t viewCount);
 /* the InstanceCullingViewInfo[] of the views ("CascadeViewInfos", mesh_raster.cpp:417-421); host array, copied */
 int chordvis_set_instance_views(ChordCtx* ctx, const ChordInstanceCullingView* hostViews, uint32_t count);
@@ -533,8 +553,9 @@ typedef struct ChordResolveTargets {
 } ChordResolveTargets;
 /* One launch on the context's stream over the image chordvis_visibility_mark reads (the resolved one of a sharded context), after
  * the same wait for it.  drawedMeshletCmd = the list the ids index (chordvis_last_frame_cmds).  The matrices are the objects' and
- * the view's of the frame that made the image: CHORDVIS_E_INVALID after chordvis_update_objects / chordvis_set_view until the next
- * frame, and before the first one.  Objects bound with chordvis_bind_objects must stay unchanged until the resolve has run.
+ * the view's of the frame that made the image: CHORDVIS_E_INVALID after chordvis_update_objects / chordvis_bind_objects /
+ * chordvis_set_view until the next frame, and before the first one.  The contents of an array bound with chordvis_bind_objects
+ * are the caller's to keep unchanged from the frame until the resolve has run (the library cannot see a write into it).
  * desc NULL: all zero. */
 int chordvis_resolve_attributes(ChordCtx* ctx, ChordCountAndCmd drawedMeshletCmd, const ChordResolveDesc* desc,
                                 const ChordResolveTargets* targets);
