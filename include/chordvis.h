@@ -215,6 +215,40 @@ int chordvis_load_gltf_binary(const char* path, ChordBuiltAsset** outAsset);
  * hands over the stream it issues them on (PyTorch: a torch.cuda.Stream made current; its default stream has handle 0,
  * which arrives here as NULL), or passes hipStreamLegacy / hipStreamPerThread ((void*)1 / (void*)2), which go through. */
 int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
+/* STREAM CONTRACT.  A host may enqueue frame after frame without waiting for the device; what every call does with unfinished work
+ * on the context's stream in front of it is one of three things.  tests/test_gpu_frames_in_flight.py holds each statement, on a
+ * caller-owned stream and on hipStreamLegacy, with the device kept from starting anything until the last call has returned, and
+ * keeps the list of the calls that wait as a table (WAITS) asserted both ways.
+ *   ENQUEUED, RETURNS AT ONCE (never waits for the stream): chordvis_set_view, chordvis_bind_objects, chordvis_reset_history (host
+ *     state only); chordvis_update_objects (see below for large arrays); chordvis_render_frame; the passes called one by one
+ *     (chordvis_clear_gbuffer, chordvis_instance_culling, chordvis_visibility_stage0 / 1, chordvis_build_hzb);
+ *     chordvis_render_shadow once the depth views exist (chordvis_allocate_depth_views allocates); chordvis_resolve_attributes and
+ *     chordvis_resolve_gbuffer; chordvis_last_frame_cmds and chordvis_history_hzb (handles of device memory that the frames in flight
+ *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain).
+ *     The kernels a frame launches are chosen from reports the device leaves when a pass finishes; the host may hold a report any
+ *     number of frames old, or none: the choice costs or saves time, never a pixel, a list entry or an HZB texel.
+ *   MAY WAIT for everything enqueued before it: chordvis_upload_scene, chordvis_upload_material_textures,
+ *     chordvis_allocate_gbuffer, chordvis_upload_history_hzb, chordvis_sync, every chordvis_readback_* call, chordvis_stats and
+ *     chordvis_destroy, which lets the stream run empty before it frees anything: frames in flight finish on memory that is still
+ *     theirs.  (Read from the code, not among the tested calls: chordvis_set_shard, chordvis_set_tile_owners and
+ *     chordvis_allocate_depth_views re-make buffers and wait likewise.)  chordvis_update_objects waits too when the array is
+ *     large: its copy from the caller's pageable memory is the HIP runtime's hipMemcpyAsync, which was measured (HIP 7.0, MI355X) to
+ *     return at once for arrays of 4 KB to 1 MB (4 681 objects) and to wait for the stream for arrays of 2 MB (9 362 objects) to
+ *     16 MB; where between 1 and 2 MB it changes was not measured, and another runtime may draw the line elsewhere.  A host that
+ *     must not wait binds a device array.
+ *   CALLER MEMORY.  Host arrays are read before the call returns and are the caller's again on return, whether or not the frame that
+ *     uses them has started.  For the records of chordvis_set_view, the chain of chordvis_upload_history_hzb and the scene of the
+ *     uploads the library sees to that itself: it copies them into memory of its own or waits.  A second chordvis_set_view may
+ *     follow a frame at once and the frame keeps its view, on both ways a view reaches the device: as an argument of the frame's
+ *     cull kernel (chordvis_render_frame, chordvis_instance_culling), and through the asynchronous copy from the context's own host
+ *     record that a pass makes when the view was set after the cull (chordvis_hzb_culling, chordvis_render_mesh and the stage
+ *     calls built on them).  For hostObjects of chordvis_update_objects -- it may be overwritten or freed at once -- the library
+ *     relies on the HIP runtime reading a pageable source before hipMemcpyAsync returns: held by the tests with the scenes of 352
+ *     and 22 528 objects and with plain copies of 4 KB, 77 KB, 256 KB, 1, 2, 4, 4.8 and 16 MB; no other size was measured.
+ *     Device memory the caller owns is read and written WHEN THE FRAME RUNS, in stream order: an array bound with
+ *     chordvis_bind_objects may be rewritten between frames by work on the context's stream, and the image handed to
+ *     chordvis_allocate_gbuffer and the targets of the resolves may be cleared, copied and read there; a write from another stream
+ *     that is not ordered against the context's reaches whichever frame runs next. */
 int chordvis_destroy(ChordCtx* ctx);
 const char* chordvis_last_error(ChordCtx* ctx);
 int chordvis_sync(ChordCtx* ctx);
