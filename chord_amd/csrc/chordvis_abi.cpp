@@ -311,6 +311,13 @@ void drop_material_textures(ChordCtx* c)
     c->matTexturesLoaded = false; c->matAnyNormalTexture = false; c->matTex.clear();
 }
 
+// what chordvis_upload_world_transforms keeps (hipFree waits for the device: a build in flight finishes on memory that is still its own)
+void drop_world_transforms(ChordCtx* c)
+{
+    dfree(c->dWorldCur); dfree(c->dWorldPrev); dfree(c->dBuildStatus);
+    c->buildCount = 0;
+}
+
 void record(ChordCtx* c, int tag) { chord::stamp(c, tag); }
 
 void begin_frame_stamps(ChordCtx* c)
@@ -683,6 +690,7 @@ int chordvis_destroy(ChordCtx* c)
     dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
     dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dBoundsTilesScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
+    drop_world_transforms(c);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
     dfree(c->dCullLookback);
@@ -716,6 +724,11 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s);
 // after a failure part of them may be the new scene's and part the old one's.
 int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
 {
+    if (c && !c->sharedScene) {                          // (the world transforms are per scene upload, refused uploads included)
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        drop_world_transforms(c);
+    }
     const int rc = upload_scene_impl(c, s);
     if (rc && c) {
         c->sceneLoaded = false;
@@ -1456,6 +1469,98 @@ int chordvis_bind_objects(ChordCtx* c, const ChordObject* deviceObjects, uint32_
     if (!c || !c->sceneLoaded || !deviceObjects || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "bind_objects: count must equal the uploaded scene's objectCount");
     c->dObjects = deviceObjects;
     c->resolveStale = true;                               // (like chordvis_update_objects: the array a resolve would read is no longer the frame's)
+    return CHORDVIS_OK;
+}
+
+// ---- object records built on the device from resident f64 world transforms (kernels_objects.hip) ----
+
+int chordvis_upload_world_transforms(ChordCtx* c, const double* hostLocalToWorld, const double* hostPrevLocalToWorld, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (c->sharedScene) return fail(c, CHORDVIS_E_INVALID, "upload_world_transforms: not on a depth-view context");
+    if (!c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "upload_world_transforms: no scene (call chordvis_upload_scene first)");
+    if (!hostLocalToWorld || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "upload_world_transforms: count must equal the uploaded scene's objectCount");
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));                         // (a build in flight reads and writes the arrays being replaced)
+    const size_t doubles = (size_t)count * 16u;
+    if (!c->dWorldCur) {
+        int rc;
+        if ((rc = dalloc(c, &c->dWorldCur, doubles)) || (rc = dalloc(c, &c->dWorldPrev, doubles)) || (rc = dalloc(c, &c->dBuildStatus, (size_t)4))) {
+            drop_world_transforms(c);
+            return rc;
+        }
+    }
+    const uint32_t cleared[4] = {0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu};
+    CHORD_HIP(c, hipMemcpy(c->dWorldCur, hostLocalToWorld, doubles * sizeof(double), hipMemcpyHostToDevice));
+    CHORD_HIP(c, hipMemcpy(c->dWorldPrev, hostPrevLocalToWorld ? hostPrevLocalToWorld : hostLocalToWorld, doubles * sizeof(double), hipMemcpyHostToDevice));
+    CHORD_HIP(c, hipMemcpy(c->dBuildStatus, cleared, sizeof(cleared), hipMemcpyHostToDevice));
+    c->buildCount = 0;
+    return CHORDVIS_OK;
+}
+
+int chordvis_scatter_world_transforms(ChordCtx* c, const uint32_t* deviceIndices, const double* deviceLocalToWorld, uint32_t n)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->sceneLoaded || !c->dWorldCur) return fail(c, CHORDVIS_E_INVALID, "scatter_world_transforms: no chordvis_upload_world_transforms since the last chordvis_upload_scene");
+    if (n == 0) return CHORDVIS_OK;
+    if (!deviceIndices || !deviceLocalToWorld) return fail(c, CHORDVIS_E_INVALID, "scatter_world_transforms: null array with n > 0");
+    if (((uintptr_t)deviceLocalToWorld & 15u) || ((uintptr_t)deviceIndices & 3u))
+        return fail(c, CHORDVIS_E_INVALID, "scatter_world_transforms: deviceLocalToWorld must be 16-byte aligned (deviceIndices: 4-byte)");
+    (void)hipSetDevice(c->device);
+    chord::launch_scatter_world_transforms(c, deviceIndices, deviceLocalToWorld, n);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+int chordvis_build_objects(ChordCtx* c, const double cameraPos[3], const double cameraPosLast[3])
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "build_objects: no scene (call chordvis_upload_scene first)");
+    if (!c->dWorldCur) return fail(c, CHORDVIS_E_INVALID, "build_objects: no chordvis_upload_world_transforms since the last chordvis_upload_scene");
+    if (!cameraPos) return fail(c, CHORDVIS_E_INVALID, "build_objects: cameraPos is NULL");
+    (void)hipSetDevice(c->device);
+    const uint32_t slot = (uint32_t)(c->buildCount & 1u);
+    chord::launch_build_objects(c, cameraPos, cameraPosLast ? cameraPosLast : cameraPos, c->dBuildStatus + 2u * slot, c->dBuildStatus + 2u * (slot ^ 1u));
+    CHORD_HIP(c, hipGetLastError());
+    c->buildCount++;
+    c->dObjects = c->dObjectsOwned;
+    c->resolveStale = true;                               // (like chordvis_update_objects)
+    return CHORDVIS_OK;
+}
+
+int chordvis_build_objects_status(ChordCtx* c, uint32_t* singularCount, uint32_t* firstSingular)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    uint32_t words[2] = {0u, 0xFFFFFFFFu};
+    if (c->dWorldCur && c->buildCount) {
+        (void)hipSetDevice(c->device);
+        CHORD_HIP(c, hipStreamSynchronize(c->stream));
+        CHORD_HIP(c, hipMemcpy(words, c->dBuildStatus + 2u * (uint32_t)((c->buildCount - 1u) & 1u), sizeof(words), hipMemcpyDeviceToHost));
+    }
+    if (singularCount) *singularCount = words[0];
+    if (firstSingular) *firstSingular = words[1];
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_objects(ChordCtx* c, ChordObject* host, uint32_t count)
+{
+    if (!c || !c->sceneLoaded || !host || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "readback_objects: count must equal the uploaded scene's objectCount");
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    CHORD_HIP(c, hipMemcpy(host, c->dObjects, sizeof(ChordObject) * count, hipMemcpyDeviceToHost));
+    return CHORDVIS_OK;
+}
+
+int chordvis_readback_world_transforms(ChordCtx* c, double* hostCur, double* hostPrev, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!c->sceneLoaded || !c->dWorldCur) return fail(c, CHORDVIS_E_INVALID, "readback_world_transforms: no chordvis_upload_world_transforms since the last chordvis_upload_scene");
+    if (count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "readback_world_transforms: count must equal the uploaded scene's objectCount");
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)count * 16u * sizeof(double);
+    if (hostCur) CHORD_HIP(c, hipMemcpy(hostCur, c->dWorldCur, bytes, hipMemcpyDeviceToHost));
+    if (hostPrev) CHORD_HIP(c, hipMemcpy(hostPrev, c->dWorldPrev, bytes, hipMemcpyDeviceToHost));
     return CHORDVIS_OK;
 }
 

@@ -481,6 +481,12 @@ struct ChordCtx {
     std::vector<ChordInstanceCullingView> instanceViews;   // chordvis_set_instance_views (cascadeViewInfos)
     ChordObject* dObjectsOwned = nullptr;
     const ChordObject* dObjects = nullptr;
+    // resident world transforms (chordvis_upload_world_transforms; kernels_objects.hip): objectCount x 16 doubles each, made by the
+    // first upload after a scene upload, dropped by the next scene upload
+    double* dWorldCur = nullptr;
+    double* dWorldPrev = nullptr;
+    uint32_t* dBuildStatus = nullptr;  // two slots of {singular count, first singular index}: build k adds into slot k & 1 and clears the other
+    uint64_t buildCount = 0;           // builds since the transforms were uploaded (0: chordvis_build_objects_status reports none)
     std::vector<chord::DPrim> hPrims;
     std::vector<chord::DObjStatic> hObjStatic;
 
@@ -732,6 +738,12 @@ void launch_texture_coverage(ChordCtx* c, const DTexCovRec* recs, uint32_t count
 // units); tables: CHORD_TEXENC_TABLE_WORDS words.  One launch on the context's stream.
 void launch_texture_encode(ChordCtx* c, const DTexEncRec* recs, uint32_t count, uint32_t totalBlocks, const uint32_t* tables,
                            const uint32_t* texels, void* blocks);
+// kernels_objects.hip: chordvis_scatter_world_transforms' and chordvis_build_objects' launches (arguments checked by the entry points).
+// scatter: cur[indices[k]] = matrices[k] for k < n, indices >= objectCount skipped.  build: the basicData of objects[0 .. objectCount)
+// from cur / prev and the two camera positions, prev = cur; status: the slot this build adds into, clearNext: the slot it clears.
+// One launch each on the context's stream.
+void launch_scatter_world_transforms(ChordCtx* c, const uint32_t* indices, const double* matrices, uint32_t n);
+void launch_build_objects(ChordCtx* c, const double cameraPos[3], const double cameraPosLast[3], uint32_t* status, uint32_t* clearNext);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

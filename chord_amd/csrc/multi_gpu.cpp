@@ -632,6 +632,18 @@ int chordvis_group_update_objects(ChordGroup* g, const ChordObject* hostObjects,
     return run_all(g, [&](uint32_t r) { return chordvis_update_objects(g->ctx[r], hostObjects, count); }, "group_update_objects");
 }
 
+int chordvis_group_upload_world_transforms(ChordGroup* g, const double* hostLocalToWorld, const double* hostPrevLocalToWorld, uint32_t count)
+{
+    if (!g || !hostLocalToWorld) return gfail(g, CHORDVIS_E_INVALID, "group_upload_world_transforms: null argument");
+    return run_all(g, [&](uint32_t r) { return chordvis_upload_world_transforms(g->ctx[r], hostLocalToWorld, hostPrevLocalToWorld, count); }, "group_upload_world_transforms");   // replicated
+}
+
+int chordvis_group_build_objects(ChordGroup* g, const double cameraPos[3], const double cameraPosLast[3])
+{
+    if (!g || !cameraPos) return gfail(g, CHORDVIS_E_INVALID, "group_build_objects: null argument");
+    return run_all(g, [&](uint32_t r) { return chordvis_build_objects(g->ctx[r], cameraPos, cameraPosLast); }, "group_build_objects");
+}
+
 int chordvis_group_set_view(ChordGroup* g, const ChordCameraView* view, const ChordInstanceCullingView* iv, uint32_t switchFlags)
 {
     if (!g || !view || !iv) return gfail(g, CHORDVIS_E_INVALID, "group_set_view: null argument");

@@ -228,6 +228,12 @@ def _load():
         "chordvis_upload_scene": (i32, [vp, P(R.SceneDesc)]),
         "chordvis_update_objects": (i32, [vp, vp, u32]),
         "chordvis_bind_objects": (i32, [vp, vp, u32]),
+        "chordvis_upload_world_transforms": (i32, [vp, vp, vp, u32]),
+        "chordvis_scatter_world_transforms": (i32, [vp, vp, vp, u32]),
+        "chordvis_build_objects": (i32, [vp, vp, vp]),
+        "chordvis_build_objects_status": (i32, [vp, P(u32), P(u32)]),
+        "chordvis_readback_objects": (i32, [vp, vp, u32]),
+        "chordvis_readback_world_transforms": (i32, [vp, vp, vp, u32]),
         "chordvis_set_view": (i32, [vp, vp, vp, u32]),
         "chordvis_allocate_gbuffer": (i32, [vp, u32, u32, vp]),
         "chordvis_set_shard": (i32, [vp, u32, u32]),
@@ -332,6 +338,8 @@ def _load():
         "chordvis_group_allocate_gbuffer": (i32, [vp, u32, u32]),
         "chordvis_group_rebalance": (i32, [vp, vp]),
         "chordvis_group_update_objects": (i32, [vp, vp, u32]),
+        "chordvis_group_upload_world_transforms": (i32, [vp, vp, vp, u32]),
+        "chordvis_group_build_objects": (i32, [vp, vp, vp]),
         "chordvis_group_set_view": (i32, [vp, vp, vp, u32]),
         "chordvis_group_render_frame": (i32, [vp]),
         "chordvis_group_sync": (i32, [vp]),

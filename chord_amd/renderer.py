@@ -339,6 +339,58 @@ class VisibilityRenderer:
     def bind_objects(self, device_ptr, count):
         self._check(L.lib.chordvis_bind_objects(self._ctx, device_ptr, count), "bind_objects")
 
+    # -- object records built on the device (chordvis_build_objects) -------------------------------
+    def upload_world_transforms(self, local_to_world, prev_local_to_world=None):
+        """chordvis_upload_world_transforms: the objects' f64 world matrices (n, 16) or (n, 4, 4) glm column-major, resident on the
+        device from here on; prev_local_to_world None: = current.  Waits for the stream."""
+        cur = np.ascontiguousarray(local_to_world, dtype=np.float64).reshape(-1, 16)
+        prev = None if prev_local_to_world is None else np.ascontiguousarray(prev_local_to_world, dtype=np.float64).reshape(-1, 16)
+        assert prev is None or prev.shape == cur.shape
+        self._check(L.lib.chordvis_upload_world_transforms(self._ctx, cur.ctypes.data, prev.ctypes.data if prev is not None else None, len(cur)),
+                    "upload_world_transforms")
+
+    def scatter_world_transforms(self, indices, matrices, n=None):
+        """chordvis_scatter_world_transforms, one launch that never waits: cur[indices[k]] = matrices[k].  indices / matrices: CUDA
+        tensors on the context's device (int32 / uint32 words, float64 x 16 per matrix, contiguous; ordered against the context's
+        stream both ways like the resolves' tensors), or raw device pointers (ints) with n given -- those are the caller's to order."""
+        if isinstance(indices, int) or isinstance(matrices, int):
+            assert isinstance(indices, int) and isinstance(matrices, int) and n is not None, "scatter_world_transforms: raw pointers come with n"
+            self._check(L.lib.chordvis_scatter_world_transforms(self._ctx, indices or None, matrices or None, int(n)), "scatter_world_transforms")
+            return
+        import torch
+        assert indices.is_cuda and matrices.is_cuda and indices.is_contiguous() and matrices.is_contiguous()
+        assert indices.element_size() == 4 and matrices.dtype == torch.float64
+        count = indices.numel() if n is None else int(n)
+        assert count <= indices.numel() and matrices.numel() >= 16 * count
+        self._on_my_stream([indices, matrices], lambda: self._check(L.lib.chordvis_scatter_world_transforms(
+            self._ctx, indices.data_ptr() if count else None, matrices.data_ptr() if count else None, count), "scatter_world_transforms"))
+
+    def build_objects(self, camera_pos, camera_pos_last=None):
+        """chordvis_build_objects, one launch that never waits: the camera-relative records of every object from the resident
+        transforms.  camera_pos / camera_pos_last: three doubles each (a scenes.Camera's .position); None: = camera_pos."""
+        cam = (C.c_double * 3)(*[float(v) for v in camera_pos])
+        last = None if camera_pos_last is None else (C.c_double * 3)(*[float(v) for v in camera_pos_last])
+        self._check(L.lib.chordvis_build_objects(self._ctx, cam, last), "build_objects")
+
+    def build_objects_status(self):
+        """(singular objects of the latest build, the first one's index or 0xFFFFFFFF).  Synchronises."""
+        n, first = C.c_uint32(0), C.c_uint32(0)
+        self._check(L.lib.chordvis_build_objects_status(self._ctx, C.byref(n), C.byref(first)), "build_objects_status")
+        return n.value, first.value
+
+    def read_objects(self, count=None):
+        """records.OBJECT array: the object array frames read now (chordvis_readback_objects).  Synchronises."""
+        out = np.zeros(len(self.scene.objects) if count is None else int(count), dtype=R.OBJECT)
+        self._check(L.lib.chordvis_readback_objects(self._ctx, out.ctypes.data, len(out)), "readback_objects")
+        return out
+
+    def read_world_transforms(self, count=None):
+        """(cur, prev) float64 (n, 16): the resident world transforms (chordvis_readback_world_transforms).  Synchronises."""
+        n = len(self.scene.objects) if count is None else int(count)
+        cur, prev = np.zeros((n, 16), dtype=np.float64), np.zeros((n, 16), dtype=np.float64)
+        self._check(L.lib.chordvis_readback_world_transforms(self._ctx, cur.ctypes.data, prev.ctypes.data, n), "readback_world_transforms")
+        return cur, prev
+
     def allocate_gbuffer(self, width, height, device_visibility=None):
         self._check(L.lib.chordvis_allocate_gbuffer(self._ctx, width, height, device_visibility), "allocate_gbuffer")
         self.width, self.height = width, height
@@ -838,6 +890,20 @@ class VisibilityGroup:
     def update_objects(self, objects):
         objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
         self._check(L.lib.chordvis_group_update_objects(self._g, objects.ctypes.data, len(objects)), "group_update_objects")
+
+    def upload_world_transforms(self, local_to_world, prev_local_to_world=None):
+        """chordvis_group_upload_world_transforms: every rank keeps the f64 world matrices (see VisibilityRenderer)."""
+        cur = np.ascontiguousarray(local_to_world, dtype=np.float64).reshape(-1, 16)
+        prev = None if prev_local_to_world is None else np.ascontiguousarray(prev_local_to_world, dtype=np.float64).reshape(-1, 16)
+        assert prev is None or prev.shape == cur.shape
+        self._check(L.lib.chordvis_group_upload_world_transforms(self._g, cur.ctypes.data, prev.ctypes.data if prev is not None else None, len(cur)),
+                    "group_upload_world_transforms")
+
+    def build_objects(self, camera_pos, camera_pos_last=None):
+        """chordvis_group_build_objects: chordvis_build_objects on every rank."""
+        cam = (C.c_double * 3)(*[float(v) for v in camera_pos])
+        last = None if camera_pos_last is None else (C.c_double * 3)(*[float(v) for v in camera_pos_last])
+        self._check(L.lib.chordvis_group_build_objects(self._g, cam, last), "group_build_objects")
 
     def set_view(self, view, instance_view, flags):
         self._views = (view, instance_view)

@@ -224,18 +224,22 @@ int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
  *     (chordvis_clear_gbuffer, chordvis_instance_culling, chordvis_visibility_stage0 / 1, chordvis_build_hzb);
  *     chordvis_render_shadow once the depth views exist (chordvis_allocate_depth_views allocates); chordvis_resolve_attributes and
  *     chordvis_resolve_gbuffer; chordvis_last_frame_cmds and chordvis_history_hzb (handles of device memory that the frames in flight
- *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain).
+ *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain);
+ *     chordvis_scatter_world_transforms and chordvis_build_objects (one launch each, of any size: the way to new object records
+ *     for a host that must not wait).
  *     The kernels a frame launches are chosen from reports the device leaves when a pass finishes; the host may hold a report any
  *     number of frames old, or none: the choice costs or saves time, never a pixel, a list entry or an HZB texel.
  *   MAY WAIT for everything enqueued before it: chordvis_upload_scene, chordvis_upload_material_textures,
- *     chordvis_allocate_gbuffer, chordvis_upload_history_hzb, chordvis_sync, every chordvis_readback_* call, chordvis_stats and
+ *     chordvis_allocate_gbuffer, chordvis_upload_history_hzb, chordvis_sync, every chordvis_readback_* call (chordvis_readback_objects and
+ *     chordvis_readback_world_transforms among them), chordvis_upload_world_transforms (a build in flight keeps its inputs),
+ *     chordvis_build_objects_status, chordvis_stats and
  *     chordvis_destroy, which lets the stream run empty before it frees anything: frames in flight finish on memory that is still
  *     theirs.  (Read from the code, not among the tested calls: chordvis_set_shard, chordvis_set_tile_owners and
  *     chordvis_allocate_depth_views re-make buffers and wait likewise.)  chordvis_update_objects waits too when the array is
  *     large: its copy from the caller's pageable memory is the HIP runtime's hipMemcpyAsync, which was measured (HIP 7.0, MI355X) to
  *     return at once for arrays of 4 KB to 1 MB (4 681 objects) and to wait for the stream for arrays of 2 MB (9 362 objects) to
  *     16 MB; where between 1 and 2 MB it changes was not measured, and another runtime may draw the line elsewhere.  A host that
- *     must not wait binds a device array.
+ *     must not wait binds a device array, or keeps the world transforms resident and calls chordvis_build_objects.
  *   CALLER MEMORY.  Host arrays are read before the call returns and are the caller's again on return, whether or not the frame that
  *     uses them has started.  For the records of chordvis_set_view, the chain of chordvis_upload_history_hzb and the scene of the
  *     uploads the library sees to that itself: it copies them into memory of its own or waits.  A second chordvis_set_view may
@@ -245,6 +249,7 @@ int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
  *     calls built on them).  For hostObjects of chordvis_update_objects -- it may be overwritten or freed at once -- the library
  *     relies on the HIP runtime reading a pageable source before hipMemcpyAsync returns: held by the tests with the scenes of 352
  *     and 22 528 objects and with plain copies of 4 KB, 77 KB, 256 KB, 1, 2, 4, 4.8 and 16 MB; no other size was measured.
+ *     The two camera positions of chordvis_build_objects travel as kernel arguments: the caller's arrays are free on return.
  *     Device memory the caller owns is read and written WHEN THE FRAME RUNS, in stream order: an array bound with
  *     chordvis_bind_objects may be rewritten between frames by work on the context's stream, and the image handed to
  *     chordvis_allocate_gbuffer and the targets of the resolves may be cleared, copied and read there; a write from another stream
@@ -262,7 +267,8 @@ int chordvis_sync(ChordCtx* ctx);
  * held to the oracle through each set-up kernel, the clipper, the depth-only pass and the resolve (tests/test_gpu_meshlet_shapes.py).
  * A context may take scene after scene.  An upload drops what belonged to the scene before: the history HZB (the next frame is a
  * frame without history), the kept tile schedules, the depth views and the cascade cache, the material textures and the geometry
- * feedback, and objects bound with chordvis_bind_objects (the library's copy of the new scene's objects is read again).  The
+ * feedback, and objects bound with chordvis_bind_objects (the library's copy of the new scene's objects is read again), and the
+ * resident world transforms of chordvis_upload_world_transforms (dropped by a refused upload too).  The
  * G-buffer, the view, the cull mode, the debug switches and the limits stay.
  * A REFUSED upload (any error code, the refusal of a scene without BVHs under chordvis_set_cull_mode(ctx, 1) included) leaves the
  * context with NO scene: the scene before is gone too, and every call that needs a scene returns CHORDVIS_E_INVALID until an upload
@@ -278,6 +284,55 @@ int chordvis_update_objects(ChordCtx* ctx, const ChordObject* hostObjects, uint3
  * is not written.  The call itself counts as a change of the objects, exactly like chordvis_update_objects: a chordvis_resolve_*
  * after it is refused (CHORDVIS_E_INVALID) until the next frame has run -- also when the same array is bound again. */
 int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint32_t count);
+
+/* OBJECT RECORDS BUILT ON THE DEVICE.  Every field of ChordObject::basicData is camera-relative, so a moving camera changes the record
+ * of every object, static ones included.  Instead of filling the records on the host (chordvis_object_basic_data_batch) and copying
+ * 224 bytes per object (chordvis_update_objects), a host may keep the objects' double-precision world matrices RESIDENT on the device
+ * and have the records built there: per frame one scatter of the matrices that moved (the counterpart of the reference's sparse
+ * GPUScene upload, gpu_scene.cpp:30-64) and one build call, neither of which ever waits for the stream.  Opt-in: a host that calls
+ * none of these gets the launches and the bytes it got before.
+ *   RESIDENT STATE.  Two device arrays of objectCount x 16 doubles (glm column-major), `cur` and `prev`, allocated by the first
+ *     chordvis_upload_world_transforms after a scene upload, dropped by every chordvis_upload_scene (refused ones included), freed by
+ *     chordvis_destroy.  `count` is the scene's objectCount in every call that takes one: otherwise CHORDVIS_E_INVALID, and
+ *     chordvis_last_error names the rule.
+ *   chordvis_upload_world_transforms sets cur and prev from host arrays (hostPrevLocalToWorld NULL: prev = cur).  MAY WAIT: it lets the
+ *     stream run empty first, so that a build in flight keeps its inputs.  The host arrays are the caller's again on return.
+ *   chordvis_scatter_world_transforms is ONE launch on the context's stream: cur[deviceIndices[k]] = deviceLocalToWorld[k] for k < n.
+ *     Both arrays are caller-owned DEVICE memory, read when the launch runs, in stream order.  An index at or beyond objectCount is
+ *     skipped: nothing is written for it.  Indices within one call are the caller's to keep distinct (with a duplicate one of the given
+ *     matrices lands, unspecified which); calls are ordered by the stream, so a later call wins.  n == 0 succeeds without a launch.
+ *     Never waits.  deviceLocalToWorld must be 16-byte aligned (CHORDVIS_E_INVALID otherwise).
+ *   chordvis_build_objects is ONE launch on the context's stream over all objects.  For object i it writes into the context's own object
+ *     array the 208 bytes of basicData that chordvis_object_basic_data(cur[i], prev[i], cameraPos, cameraPosLast) writes, then sets
+ *     prev[i] = cur[i]: an object that was not scattered since the last build is a static object under a moving camera at the next one,
+ *     and last-frame matrices -- motion vectors -- come from the library's own copy of the previous transforms.  The 16 bytes behind
+ *     basicData (GLTFPrimitiveDetail, GLTFMaterialData, the pads) are never written and never read-modify-written: they stay what
+ *     chordvis_upload_scene or chordvis_update_objects put there.  cameraPosLast NULL: = cameraPos.  Both positions travel by value as
+ *     kernel arguments: the call returns at once and the caller's arrays are free on return.  Like chordvis_update_objects it returns
+ *     the context to its own array after chordvis_bind_objects, and it counts as a change of the objects: chordvis_resolve_*, the
+ *     feedback calls and everything else that needs the frame's matrices is refused until the next frame.  CHORDVIS_E_INVALID without
+ *     a scene, or without a chordvis_upload_world_transforms since the scene upload.  The depth views read the same array.
+ *   ARITHMETIC.  Bit for bit the host function's, for finite inputs: m[12..14] minus the camera in binary64, one round-to-nearest-even
+ *     conversion per element to binary32, the cofactor inverse in the host function's source order (products left to right, sums left
+ *     to right, 1 / det once, sixteen multiplies), the three column lengths through a correctly rounded square root, and their maximum;
+ *     no contraction; binary32 subnormals are kept, not flushed.  Finite inputs can still end in a NaN of the inverse (a determinant
+ *     in the subnormal range has an infinite reciprocal, and infinity times a zero of the last row is invalid): such a NaN has the
+ *     bits an x86 host's function produces, 0xFFC00000 (the device's own pattern for an invalid operation).  Non-finite inputs do not fault; their bits are unspecified.
+ *   SINGULAR MATRICES.  chordvis_object_basic_data returns an error for a matrix with det == 0 and leaves localToTranslatedWorld and
+ *     the last-frame matrix filled, the inverse and the scale zero.  The build writes exactly those bytes for that object and goes on;
+ *     it counts such objects and keeps the smallest of their indices.  chordvis_build_objects_status SYNCHRONISES and reports both for
+ *     the latest build since the transforms were uploaded: 0 and 0xFFFFFFFF when there was none (either pointer may be NULL).  The two
+ *     words are cleared for each build on the stream.
+ *   chordvis_readback_objects (the array frames read now: the bound one after chordvis_bind_objects) and
+ *     chordvis_readback_world_transforms (either array may be NULL) SYNCHRONISE and copy to the host.
+ * tests/test_gpu_object_build.py holds the kernel to chordvis_object_basic_data byte by byte; DESIGN.md 4.14 has the layout and timings. */
+int chordvis_upload_world_transforms(ChordCtx* ctx, const double* hostLocalToWorld /* count x 16 */,
+                                     const double* hostPrevLocalToWorld /* or NULL: = current */, uint32_t count);
+int chordvis_scatter_world_transforms(ChordCtx* ctx, const uint32_t* deviceIndices, const double* deviceLocalToWorld /* n x 16 */, uint32_t n);
+int chordvis_build_objects(ChordCtx* ctx, const double cameraPos[3], const double cameraPosLast[3] /* NULL: = cameraPos */);
+int chordvis_build_objects_status(ChordCtx* ctx, uint32_t* singularCount, uint32_t* firstSingular);
+int chordvis_readback_objects(ChordCtx* ctx, ChordObject* host, uint32_t count);
+int chordvis_readback_world_transforms(ChordCtx* ctx, double* hostCur, double* hostPrev, uint32_t count);
 
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
  * and the r.instanceculling.* cvars -> switchFlags (instance_culling.cpp:22-68). */
@@ -484,6 +539,10 @@ int chordvis_group_allocate_gbuffer(ChordGroup* group, uint32_t width, uint32_t 
 /* chordvis_rebalance on every rank (drains the frames in flight first) */
 int chordvis_group_rebalance(ChordGroup* group, uint32_t* imbalancePermille);
 int chordvis_group_update_objects(ChordGroup* group, const ChordObject* hostObjects, uint32_t count);
+/* chordvis_upload_world_transforms / chordvis_build_objects on every rank (the transforms are replicated like the scene).  There is no
+ * group scatter: the device arrays are per device, so a host that needs one goes through the ranks' contexts (chordvis_group_ctx). */
+int chordvis_group_upload_world_transforms(ChordGroup* group, const double* hostLocalToWorld, const double* hostPrevLocalToWorld, uint32_t count);
+int chordvis_group_build_objects(ChordGroup* group, const double cameraPos[3], const double cameraPosLast[3]);
 int chordvis_group_set_view(ChordGroup* group, const ChordCameraView* view, const ChordInstanceCullingView* instanceView, uint32_t switchFlags);
 /* DeferredRenderer::render hot segment (renderer.cpp:315-345,489) on n devices; returns when the frame is ENQUEUED on every
  * device (no host synchronisation; chordvis_group_sync waits) */
