@@ -318,6 +318,51 @@ void drop_world_transforms(ChordCtx* c)
     c->buildCount = 0;
 }
 
+// Device memory chordvis_set_object_list drops: hipFree waits for the device, and that call must not, so the pointers are kept until a
+// call that waits anyway comes by (chordvis_upload_scene, chordvis_destroy, a chordvis_set_object_list that has to grow).
+template <typename T>
+void retire(ChordCtx* c, T*& p) { if (p) { c->retired.push_back((void*)p); p = nullptr; } }
+
+void free_retired(ChordCtx* c)      // (the caller has let the stream run empty)
+{
+    for (void* p : c->retired) (void)hipFree(p);
+    c->retired.clear();
+    for (ChordCtx* k : c->retiredChildren) chordvis_destroy(k);
+    c->retiredChildren.clear();
+}
+
+// The per-object static table and the totals every launch is sized by, from an object list and the resident scene's tables (hPrims,
+// hPrimMeshlets, hPrimTriangles, hMatFlags, hMatType), in O(count): what chordvis_upload_scene and chordvis_set_object_list share.
+// Nothing of the context is written but `out` (the caller's) and, on a refusal, the error text.
+struct ObjectListTotals { uint64_t groupInst = 0, cmdCap = 0, instTriangles = 0; };
+
+int derive_object_list(ChordCtx* c, const char* fn, const ChordObject* objects, uint32_t count, std::vector<DObjStatic>& out, ObjectListTotals& t)
+{
+    char buf[224];
+    auto refuse = [&](int code, const char* why) { std::snprintf(buf, sizeof(buf), "%s: %s", fn, why); return fail(c, code, buf); };
+    const size_t primCount = c->hPrims.size(), materialCount = c->hMatFlags.size();
+    out.assign(count, DObjStatic{});
+    t = ObjectListTotals{};
+    for (uint32_t o = 0; o < count; o++) {
+        const ChordObject& ob = objects[o];
+        if (ob.GLTFPrimitiveDetail >= primCount || ob.GLTFMaterialData >= materialCount)
+            return refuse(CHORDVIS_E_INVALID, "object primitive/material id out of range");
+        if (ob.GLTFMaterialData >= (1u << 24)) return refuse(CHORDVIS_E_CAPACITY, "more than 2^24 materials");
+        DObjStatic& d = out[o];
+        d.prim = ob.GLTFPrimitiveDetail;
+        d.matFlags = c->hMatFlags[ob.GLTFMaterialData] | (ob.GLTFMaterialData << 8);
+        d.shadingType = c->hMatType[ob.GLTFMaterialData];
+        d.groupBase = (uint32_t)t.groupInst;            // (a list past 2^31 - 1 group instances is refused below: the wrapped values are never used)
+        for (int i = 0; i < 3; i++) { d.posMin[i] = c->hPrims[d.prim].posMin[i]; d.posMax[i] = c->hPrims[d.prim].posMax[i]; }
+        t.groupInst += c->hPrims[d.prim].groupCount;
+        t.cmdCap += c->hPrimMeshlets[d.prim];
+        t.instTriangles += c->hPrimTriangles[d.prim];
+    }
+    if (t.cmdCap >= CHORD_MAX_INSTANCE_ID || t.groupInst > 0x7FFFFFFFull)
+        return refuse(CHORDVIS_E_CAPACITY, "more than 2^24-2 cluster instances do not fit the 24-bit visibility id (base.h:412)");
+    return CHORDVIS_OK;
+}
+
 void record(ChordCtx* c, int tag) { chord::stamp(c, tag); }
 
 void begin_frame_stamps(ChordCtx* c)
@@ -604,7 +649,6 @@ int prepare_cull_exchange(ChordCtx* c)
 int alloc_scene_work_buffers(ChordCtx* c)
 {
     int rc;
-    const uint64_t instTriangles = c->instTriangles;
     if ((rc = dalloc(c, &c->dObjectsOwned, (size_t)c->objectCount))) return rc;
     if ((rc = dalloc(c, &c->dObjFrame, (size_t)c->objectCount))) return rc;
     if ((rc = dalloc(c, &c->dGroupMask, (size_t)c->groupInstances + 16))) return rc;   // (+16: zeroed in 16-byte vectors)
@@ -615,6 +659,24 @@ int alloc_scene_work_buffers(ChordCtx* c)
         c->lists[i].count = c->dCounts + i;
         c->lists[i].capacity = c->cmdCapacity;
     }
+    scene_work_caps(c);
+    if ((rc = dalloc(c, &c->dTris, (size_t)c->triCap))) return rc;
+    if ((rc = dalloc(c, &c->dTrisC, (size_t)c->triCapC))) return rc;
+    if ((rc = dalloc(c, &c->dBlockPool, (size_t)c->blockCap * CHORD_LIST_SHARDS * 2u))) return rc;
+    if ((rc = dalloc(c, &c->dClipTris, (size_t)c->clipTriCap))) return rc;
+    if ((rc = dalloc(c, &c->dLargeList, (size_t)c->largeCap))) return rc;
+    // (what the buffers hold: the list's own counts here; chordvis_set_object_list grows them)
+    c->allocObjects = std::max<size_t>(c->objectCount, 1); c->allocGroupInst = std::max<size_t>(c->groupInstances, 1);
+    c->allocCullBlocks = c->cullBlocks; c->allocCmds = c->cmdCapacity;
+    c->allocTris = c->triCap; c->allocTrisC = c->triCapC; c->allocBlocks = c->blockCap;
+    return CHORDVIS_OK;
+}
+
+// The capacities the raster kernels see, from the list's triangles and the limits: the same for an uploaded list and for one set by
+// chordvis_set_object_list, whatever the buffers hold.
+void scene_work_caps(ChordCtx* c)
+{
+    const uint64_t instTriangles = c->instTriangles;
     // raster work lists, sized from the scene like the reference sizes its command buffers from lod0MeshletCount
     // (instance_culling.cpp:141): a triangle instance is set up at most once per frame (stage 0 or stage 1), so the
     // records of a frame never exceed the triangles of every meshlet instance (all LODs) plus the pieces the clipper
@@ -626,16 +688,10 @@ int alloc_scene_work_buffers(ChordCtx* c)
     c->triCapC = (uint32_t)std::min<uint64_t>(c->limitRecords, need);
     c->triCap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c->limitRecords / 4, 1u << 20), need) & ~(CHORD_LIST_SHARDS - 1u);
     c->clipTriCap = 1u << 20;
-    if ((rc = dalloc(c, &c->dTris, (size_t)c->triCap))) return rc;
-    if ((rc = dalloc(c, &c->dTrisC, (size_t)c->triCapC))) return rc;
     // pixel blocks of small clusters: a cluster takes the block form only when that is fewer bytes than its records would
     // be, so the compact list's byte budget bounds the pool too
     c->blockCap = (uint32_t)std::min<uint64_t>((uint64_t)c->triCapC * 2u / CHORD_LIST_SHARDS, CHORD_REC_INDEX_MASK / CHORD_LIST_SHARDS);
-    if ((rc = dalloc(c, &c->dBlockPool, (size_t)c->blockCap * CHORD_LIST_SHARDS * 2u))) return rc;
-    if ((rc = dalloc(c, &c->dClipTris, (size_t)c->clipTriCap))) return rc;
     c->largeCap = 8u << 20;
-    if ((rc = dalloc(c, &c->dLargeList, (size_t)c->largeCap))) return rc;
-    return CHORDVIS_OK;
 }
 }
 
@@ -678,6 +734,7 @@ int chordvis_destroy(ChordCtx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     (void)chordvis_comm_destroy(c);
+    free_retired(c);
     if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }
     for (float*& d : c->dDepthImages) dfree(d);
     if (c->sharedScene) {       // a depth-view child: the scene buffers are the parent's
@@ -713,6 +770,7 @@ int chordvis_sync(ChordCtx* c)
     if (!c) return CHORDVIS_E_INVALID;
     { const int rc = flush_pending_tail(c); if (rc) return rc; }
     CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    free_retired(c);                                      // (what chordvis_set_object_list dropped without waiting)
     return CHORDVIS_OK;
 }
 
@@ -728,6 +786,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         drop_world_transforms(c);
+        free_retired(c);
     }
     const int rc = upload_scene_impl(c, s);
     if (rc && c) {
@@ -909,29 +968,19 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
         }
     }
 
-    // objects
-    c->hObjStatic.assign(s->objectCount, DObjStatic{});
-    uint64_t groupInst = 0, cmdCap = 0, instTriangles = 0;
-    for (uint32_t o = 0; o < s->objectCount; o++) {
-        const ChordObject& ob = s->objects[o];
-        if (ob.GLTFPrimitiveDetail >= s->primitiveCount || ob.GLTFMaterialData >= s->materialCount)
-            return fail(c, CHORDVIS_E_INVALID, "upload_scene: object primitive/material id out of range");
-        DObjStatic& d = c->hObjStatic[o];
-        d.prim = ob.GLTFPrimitiveDetail;
-        const ChordMaterial& mat = s->materials[ob.GLTFMaterialData];
+    // objects (the per-primitive and per-material facts stay with the context: chordvis_set_object_list derives its lists from them)
+    c->hPrimMeshlets = primMeshlets; c->hPrimTriangles = primTriangles;
+    c->hMatFlags.assign(s->materialCount, 0u); c->hMatType.assign(s->materialCount, 0u);
+    for (uint32_t m = 0; m < s->materialCount; m++) {
+        const ChordMaterial& mat = s->materials[m];
         // alphaMode 0 / 1 / 2 = opaque / mask / blend (FILTER_CHECK of pipeline_filter.hlsl:100-101); anything else never
         // matches a bucket's targetAlphaMode and draws nothing, like blend
-        d.matFlags = (mat.bTwoSided != 0 ? CHORD_MATFLAG_TWO_SIDED : 0u) | ((mat.alphaMode > 2u ? 2u : mat.alphaMode) << 1) | (ob.GLTFMaterialData << 8);
-        if (ob.GLTFMaterialData >= (1u << 24)) return fail(c, CHORDVIS_E_CAPACITY, "upload_scene: more than 2^24 materials");
-        d.shadingType = s->materials[ob.GLTFMaterialData].materialType;
-        d.groupBase = (uint32_t)groupInst;
-        for (int i = 0; i < 3; i++) { d.posMin[i] = c->hPrims[d.prim].posMin[i]; d.posMax[i] = c->hPrims[d.prim].posMax[i]; }
-        groupInst += c->hPrims[d.prim].groupCount;
-        cmdCap += primMeshlets[d.prim];
-        instTriangles += primTriangles[d.prim];
+        c->hMatFlags[m] = (mat.bTwoSided != 0 ? CHORD_MATFLAG_TWO_SIDED : 0u) | ((mat.alphaMode > 2u ? 2u : mat.alphaMode) << 1);
+        c->hMatType[m] = mat.materialType;
     }
-    if (cmdCap >= CHORD_MAX_INSTANCE_ID || groupInst > 0x7FFFFFFFull)
-        return fail(c, CHORDVIS_E_CAPACITY, "upload_scene: more than 2^24-2 cluster instances do not fit the 24-bit visibility id (base.h:412)");
+    ObjectListTotals totals;
+    { const int orc = derive_object_list(c, "upload_scene", s->objects, s->objectCount, c->hObjStatic, totals); if (orc) return orc; }
+    const uint64_t groupInst = totals.groupInst, cmdCap = totals.cmdCap, instTriangles = totals.instTriangles;
     // the flattened (object, group) instances, every indirection of the group cull resolved (DGroupRef)
     std::vector<DGroupRef> refs((size_t)groupInst);
     for (uint32_t o = 0; o < s->objectCount; o++) {
@@ -1470,6 +1519,96 @@ int chordvis_bind_objects(ChordCtx* c, const ChordObject* deviceObjects, uint32_
     c->dObjects = deviceObjects;
     c->resolveStale = true;                               // (like chordvis_update_objects: the array a resolve would read is no longer the frame's)
     return CHORDVIS_OK;
+}
+
+// ---- the object list of a resident scene (include/chordvis.h OBJECTS COME AND GO; kernels_objects.hip) ----
+
+// Everything is derived and checked before anything of the context is touched; the buffers a longer list needs are all made before
+// the first old one is let go, so a refusal -- an allocation failure too -- leaves the context rendering the list it had.
+int chordvis_set_object_list(ChordCtx* c, const ChordObject* hostObjects, uint32_t count)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (c->sharedScene) return fail(c, CHORDVIS_E_INVALID, "set_object_list: not on a depth-view context");
+    if (!c->sceneLoaded) return fail(c, CHORDVIS_E_INVALID, "set_object_list: no scene (call chordvis_upload_scene first)");
+    if (!hostObjects || count == 0) return fail(c, CHORDVIS_E_INVALID, "set_object_list: count must be at least 1 (and hostObjects not NULL), as for chordvis_upload_scene");
+    // (the rank masks on their way through the all-gather name the old list's group instances)
+    if (c->cullPhaseDone) return fail(c, CHORDVIS_E_INVALID, "set_object_list: not between chordvis_frame_phase_cull and chordvis_frame_phase_a");
+    std::vector<DObjStatic> stat;
+    ObjectListTotals t;
+    int rc = derive_object_list(c, "set_object_list", hostObjects, count, stat, t);
+    if (rc) return rc;
+    (void)hipSetDevice(c->device);
+
+    // the logical counts and capacities of a fresh upload of this list (scene_work_caps reads instTriangles and the limits only)
+    const uint32_t groupInstances = (uint32_t)t.groupInst, cmdCapacity = (uint32_t)std::max<uint64_t>(t.cmdCap, 1);
+    const uint32_t cullBlocks = std::max(1u, (groupInstances + 255u) / 256u);
+    ChordCtx caps;                                       // (a scratch record for the five capacities: no device state)
+    caps.instTriangles = t.instTriangles; caps.limitRecords = c->limitRecords;
+    chord::scene_work_caps(&caps);
+
+    // grow what is too short: every new buffer first, then the old ones go
+    struct Grow { void** slot; size_t bytes; void* fresh; };
+    std::vector<Grow> grow;
+    auto want = [&grow](auto*& p, size_t n) { grow.push_back(Grow{(void**)&p, std::max<size_t>(n, 1) * sizeof(*p), nullptr}); };
+    const bool growObjects = count > c->allocObjects, growGroups = groupInstances > c->allocGroupInst, growBlocks = cullBlocks > c->allocCullBlocks;
+    const bool growCmds = cmdCapacity > c->allocCmds, growTris = caps.triCap > c->allocTris, growTrisC = caps.triCapC > c->allocTrisC;
+    const bool growPool = caps.blockCap > c->allocBlocks;
+    if (growObjects) { want(c->dObjectsOwned, count); want(c->dObjFrame, count); want(c->dObjStatic, count); }
+    if (growGroups) { want(c->dGroupRefs, groupInstances); want(c->dGroupMask, (size_t)groupInstances + 16); }
+    if (growBlocks) want(c->dBlockCounts, (size_t)cullBlocks * 3);
+    if (growCmds) for (int i = 0; i < 3; i++) want(c->lists[i].cmds, cmdCapacity);
+    if (growTris) want(c->dTris, caps.triCap);
+    if (growTrisC) want(c->dTrisC, caps.triCapC);
+    if (growPool) want(c->dBlockPool, (size_t)caps.blockCap * CHORD_LIST_SHARDS * 2u);
+    if (!grow.empty()) {
+        for (Grow& g : grow) {
+            const hipError_t e = hipMalloc(&g.fresh, g.bytes);
+            if (e != hipSuccess) {
+                for (Grow& u : grow) if (u.fresh) (void)hipFree(u.fresh);
+                return fail(c, CHORDVIS_E_HIP, "set_object_list: hipMalloc of a buffer the longer list needs", e);
+            }
+        }
+        CHORD_HIP(c, hipStreamSynchronize(c->stream));    // (a frame in flight keeps its buffers)
+        // (the depth views' child aliases dObjStatic and dGroupRefs, and its own lists are sized by the old counts)
+        if (c->depthCtx) { chordvis_destroy(c->depthCtx); c->depthCtx = nullptr; }
+        for (Grow& g : grow) { if (*g.slot) (void)hipFree(*g.slot); *g.slot = g.fresh; }
+        if (growObjects) c->allocObjects = count;
+        if (growGroups) c->allocGroupInst = groupInstances;
+        if (growBlocks) c->allocCullBlocks = cullBlocks;
+        if (growCmds) {
+            c->allocCmds = cmdCapacity;
+            dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);     // (sized by allocCmds; re-made on demand)
+        }
+        if (growTris) c->allocTris = caps.triCap;
+        if (growTrisC) c->allocTrisC = caps.triCapC;
+        if (growPool) c->allocBlocks = caps.blockCap;
+        free_retired(c);
+    }
+
+    // (a host that re-makes what the call drops after every call and never calls anything that waits: the parked memory is bounded)
+    if (c->retired.size() + c->retiredChildren.size() >= 32u) { CHORD_HIP(c, hipStreamSynchronize(c->stream)); free_retired(c); }
+
+    // commit: host state, then one copy of the records, one of the static table, one launch -- all behind the frames in flight
+    c->hObjStatic.swap(stat);
+    c->objectCount = count; c->groupInstances = groupInstances; c->cmdCapacity = cmdCapacity; c->cullBlocks = cullBlocks;
+    c->instTriangles = t.instTriangles;
+    chord::scene_work_caps(c);
+    for (int i = 0; i < 3; i++) c->lists[i].capacity = cmdCapacity;
+    // what was sized by or named the old list goes, as with chordvis_upload_scene (the history HZB and a pending tail stay)
+    c->mineValid = false; c->listMine[1] = c->listMine[2] = false; c->fullListStale = false;
+    retire(c, c->dGeoFeedback); c->geoFeedbackCmds = nullptr;
+    retire(c, c->dWorldCur); retire(c, c->dWorldPrev); retire(c, c->dBuildStatus); c->buildCount = 0;
+    if (c->depthCtx) { c->retiredChildren.push_back(c->depthCtx); c->depthCtx = nullptr; }
+    c->shadowHistoryValid = false; c->fusedDepthView = -1;
+    c->resolveFrame = false;
+    c->dObjects = c->dObjectsOwned;
+    // (hostObjects and the static table are pageable: the copies read them before they return, as chordvis_update_objects' does)
+    CHORD_HIP(c, hipMemcpyAsync(c->dObjectsOwned, hostObjects, sizeof(ChordObject) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    CHORD_HIP(c, hipMemcpyAsync(c->dObjStatic, c->hObjStatic.data(), sizeof(DObjStatic) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    chord::launch_group_refs_build(c);
+    CHORD_HIP(c, hipGetLastError());
+    // (a sharded context: cullChunkBlocks follows the new cullBlocks -- what chordvis_upload_scene runs)
+    return chord::prepare_cull_exchange(c);
 }
 
 // ---- object records built on the device from resident f64 world transforms (kernels_objects.hip) ----
@@ -2856,8 +2995,9 @@ int chordvis_debug_graph_frames(ChordCtx* c, uint32_t pairs, float* msPerFrameSt
 }
 
 // Debugging aid: raw read of an internal buffer.  which: 0 tile counts (FrameState::tileCount), 1 fixed bins, 2 chunk table,
-// 3 bin pool, 4 compact records, 5 wide records, 6 the fused cull kernel's look-back words, 7 the alpha plane (dTexAlpha).
-// offset / bytes in bytes.
+// 3 bin pool, 4 compact records, 5 wide records, 6 the fused cull kernel's look-back words, 7 the alpha plane (dTexAlpha),
+// 8 the flattened (object, group) table (DGroupRef, 24 bytes per group instance), 9 the per-object static table (DObjStatic, 48
+// bytes per object) -- the two checked against the current list's size.  offset / bytes in bytes.
 int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes, void* host)
 {
     if (!c || !host) return fail(c, CHORDVIS_E_INVALID, "debug_read: null argument");
@@ -2874,6 +3014,12 @@ int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes,
     case 7: base = (const char*)c->dTexAlpha;                  // the alpha plane of the masked buckets
         if (!base) return fail(c, CHORDVIS_E_INVALID, "debug_read: the scene has no alpha plane (no masked material samples a texture)");
         break;
+    case 8: case 9: {                                          // the group-ref table (groupInstances x 24 bytes) / the per-object static table (objectCount x 48)
+        const uint64_t have = which == 8 ? (uint64_t)c->groupInstances * sizeof(chord::DGroupRef) : (uint64_t)c->objectCount * sizeof(chord::DObjStatic);
+        if (!c->sceneLoaded || offset > have || bytes > have - offset) return fail(c, CHORDVIS_E_INVALID, "debug_read: no scene, or a range beyond the current object list's table");
+        base = which == 8 ? (const char*)c->dGroupRefs : (const char*)c->dObjStatic;
+        break;
+    }
     default: return fail(c, CHORDVIS_E_INVALID, "debug_read: unknown buffer");
     }
     CHORD_HIP(c, hipMemcpy(host, base + offset, bytes, hipMemcpyDeviceToHost));

@@ -489,6 +489,23 @@ struct ChordCtx {
     uint64_t buildCount = 0;           // builds since the transforms were uploaded (0: chordvis_build_objects_status reports none)
     std::vector<chord::DPrim> hPrims;
     std::vector<chord::DObjStatic> hObjStatic;
+    // chordvis_set_object_list: what the host needs of the resident scene to validate a new list and derive its
+    // DObjStatic and totals in O(count) -- per primitive its meshlets and triangles over all groups, per material DObjStatic's
+    // matFlags without the index and its materialType.  Retained from the upload, dropped with the scene.
+    std::vector<uint32_t> hPrimMeshlets;
+    std::vector<uint64_t> hPrimTriangles;
+    std::vector<uint32_t> hMatFlags, hMatType;
+    // What the buffers sized by the object list HOLD, in elements of the count each is sized by.  chordvis_upload_scene allocates them
+    // for its list exactly; chordvis_set_object_list only ever grows them, and the kernels see the logical counts above and below
+    // (objectCount, groupInstances, cullBlocks, cmdCapacity, triCap, triCapC, blockCap), which are a fresh upload's whatever is allocated.
+    size_t allocObjects = 0;          // dObjectsOwned, dObjFrame, dObjStatic
+    size_t allocGroupInst = 0;        // dGroupRefs, dGroupMask (+ 16)
+    size_t allocCullBlocks = 0;       // dBlockCounts (x 3)
+    size_t allocCmds = 0;             // lists[0..2].cmds, and dRankCmds / dLeftCmds / dMineCmds when they are made
+    size_t allocTris = 0, allocTrisC = 0, allocBlocks = 0;   // dTris, dTrisC, dBlockPool (x CHORD_LIST_SHARDS x 2)
+    // device memory chordvis_set_object_list dropped without waiting for the device (hipFree waits): freed by whichever call waits next
+    std::vector<void*> retired;
+    std::vector<ChordCtx*> retiredChildren;
 
     // frame
     chord::DView hView{};
@@ -645,6 +662,7 @@ int fail(ChordCtx* ctx, int code, const char* what, hipError_t e = hipSuccess);
 // it); without a target there is nothing to fit
 inline bool view_fits_target(const ChordCtx* c) { return !c->dVis || (c->hView.width == c->width && c->hView.height == c->height); }
 int alloc_scene_work_buffers(ChordCtx* c);
+void scene_work_caps(ChordCtx* c);              // chordvis_abi.cpp: triCap, triCapC, blockCap, clipTriCap, largeCap from instTriangles and the limits
 
 #define CHORD_HIP(ctx, call)                                                         \
     do {                                                                             \
@@ -744,6 +762,9 @@ void launch_texture_encode(ChordCtx* c, const DTexEncRec* recs, uint32_t count, 
 // One launch each on the context's stream.
 void launch_scatter_world_transforms(ChordCtx* c, const uint32_t* indices, const double* matrices, uint32_t n);
 void launch_build_objects(ChordCtx* c, const double cameraPos[3], const double cameraPosLast[3], uint32_t* status, uint32_t* clearNext);
+// chordvis_set_object_list's launch: dGroupRefs[0 .. groupInstances) from dObjStatic[0 .. objectCount), dPrims, dGroups and
+// dGroupIndices, byte for byte what chordvis_upload_scene fills on the host.  One launch on the context's stream; none for no instances.
+void launch_group_refs_build(ChordCtx* c);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

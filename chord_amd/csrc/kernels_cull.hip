@@ -1602,7 +1602,7 @@ void launch_group_cull(ChordCtx* c, const CmdList& out)
     c->mineValid = false;
     if (c->shard.ranks > 1 && c->height && c->shard.ownedRows) {
         // sharded frame: the rank's own commands leave the cull as a list of their own (no pass over the full list later)
-        if (!c->dMineCmds && hipMalloc((void**)&c->dMineCmds, sizeof(ChordDrawCmd) * (size_t)c->cmdCapacity) != hipSuccess) c->dMineCmds = nullptr;
+        if (!c->dMineCmds && hipMalloc((void**)&c->dMineCmds, sizeof(ChordDrawCmd) * c->allocCmds) != hipSuccess) c->dMineCmds = nullptr;
         if (c->dMineCmds) { p.mineCmds = c->dMineCmds; p.mineCount = c->dCounts + 4; c->mineValid = true; }
         else p.shard.ranks = 1;                              // (allocation failed: launch_raster falls back to the rank filter)
     } else p.shard.ranks = 1;

@@ -1,5 +1,6 @@
 // chordvis -- object records built on the device from resident f64 world transforms (chordvis_upload_world_transforms,
-// chordvis_scatter_world_transforms, chordvis_build_objects).
+// chordvis_scatter_world_transforms, chordvis_build_objects), and the flattened (object, group) table built on the
+// device for chordvis_set_object_list (group_refs_build_kernel, further down).
 //
 //   scatter_world_transforms_kernel   a lane per 16-byte vector of the given matrices (8 per matrix): consecutive lanes read consecutive
 //                                     addresses of `matrices` and write 128 contiguous bytes of cur per matrix.  An index at or beyond
@@ -153,6 +154,53 @@ __global__ __launch_bounds__(64) void build_objects_kernel(const BuildArgs a)
         const uint32_t v = t + 64u * k, o = v / 13u;
         if (o < here) a.objects[(uint64_t)(base + o) * 14u + (v - o * 13u)] = flat[v];
     }
+}
+
+// ---- the flattened (object, group) table of chordvis_set_object_list ----
+//
+//   group_refs_build_kernel   a lane per group instance i.  Its owner is the last object whose groupBase is <= i (objects of no groups
+//                             share their successor's base and own nothing): a bisection over DObjStatic::groupBase, whose probes are
+//                             the same few lines for every lane of a wave.  Then the walk chordvis_upload_scene does on the host --
+//                             object -> primitive -> group -> group indices -- and the 24-byte record as three 8-byte stores: a wave
+//                             writes 1536 contiguous bytes in three instructions, every byte of every line it touches.  The work per
+//                             lane is the same whatever the objects' sizes; a grid-stride loop takes lists longer than the grid.
+//                             (A form that gathered a workgroup's records in LDS and stored them as 16-byte vectors took the same
+//                             time -- the kernel waits for its chain of dependent loads, not for its stores -- and was dropped.)
+constexpr uint32_t kRefsThreads = 256u;
+
+__global__ __launch_bounds__(kRefsThreads) void group_refs_build_kernel(const DObjStatic* __restrict__ objStatic, const DPrim* __restrict__ prims,
+                                                                         const DGroup* __restrict__ groups, const uint32_t* __restrict__ groupIndices,
+                                                                         DGroupRef* __restrict__ refs, uint32_t objectCount, uint32_t groupInstances)
+{
+    // (groupInstances <= 2^31 - 1 and the grid is at most 2^19 lanes: neither i nor the stride wraps)
+    for (uint32_t i = blockIdx.x * kRefsThreads + threadIdx.x; i < groupInstances; i += gridDim.x * kRefsThreads) {
+        uint32_t lo = 0u, hi = objectCount;                   // the first object whose groupBase is > i, in [lo, hi]
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (objStatic[mid].groupBase <= i) lo = mid + 1u; else hi = mid;
+        }
+        const uint32_t o = lo - 1u;                           // (object 0's base is 0 <= i: lo >= 1)
+        const DObjStatic& d = objStatic[o];
+        const DPrim& pr = prims[d.prim];
+        const uint32_t g = pr.groupBase + (i - d.groupBase);
+        const uint32_t meshletOffset = groups[g].meshletOffset, meshletCount = groups[g].meshletCount;
+        const uint32_t cnt = meshletCount < (uint32_t)CHORD_GROUP_MAX_MESHLETS ? meshletCount : (uint32_t)CHORD_GROUP_MAX_MESHLETS;
+        uint32_t m[CHORD_GROUP_MAX_MESHLETS];
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)CHORD_GROUP_MAX_MESHLETS; k++)
+            m[k] = cnt ? pr.meshletBase + groupIndices[pr.groupIndicesBase + meshletOffset + (k < cnt ? k : 0u)] : 0u;
+        uint2* out = reinterpret_cast<uint2*>(refs + i);
+        out[0] = make_uint2(o, g | (cnt << 28)); out[1] = make_uint2(m[0], m[1]); out[2] = make_uint2(m[2], m[3]);
+    }
+}
+
+void launch_group_refs_build(ChordCtx* c)
+{
+    if (c->groupInstances == 0u) return;
+    const uint32_t blocks = (c->groupInstances + kRefsThreads - 1u) / kRefsThreads;
+    const uint32_t grid = blocks < (uint32_t)c->numCUs * 8u ? blocks : (uint32_t)c->numCUs * 8u;
+    CHORD_LAUNCH(c, group_refs_build_kernel, dim3(grid), dim3(kRefsThreads), 0, c->stream, c->dObjStatic, c->dPrims, c->dGroups, c->dGroupIndices,
+                 c->dGroupRefs, c->objectCount, c->groupInstances);
 }
 
 void launch_scatter_world_transforms(ChordCtx* c, const uint32_t* indices, const double* matrices, uint32_t n)

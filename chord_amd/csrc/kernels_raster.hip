@@ -3583,7 +3583,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
         else if (in.cmds == c->dMineCmds && c->mineValid) mine = true;
         else for (int k = 1; k < 3; k++) if (in.cmds == c->lists[k].cmds && c->listMine[k]) mine = true;
         if (!mine) {
-            if (!c->dRankCmds) LR_HIP(hipMalloc((void**)&c->dRankCmds, sizeof(ChordDrawCmd) * (size_t)c->cmdCapacity));
+            if (!c->dRankCmds) LR_HIP(hipMalloc((void**)&c->dRankCmds, sizeof(ChordDrawCmd) * c->allocCmds));
             CmdList filtered;
             filtered.count = c->dCounts + 5; filtered.cmds = c->dRankCmds; filtered.capacity = in.capacity;
             LR_HIP(hipMemsetAsync(filtered.count, 0, sizeof(uint32_t), c->stream));
@@ -3671,7 +3671,7 @@ hipError_t launch_raster(ChordCtx* c, const CmdList& in, bool clearTiles)
     }
     if (blocksWorthLaunching) {
         if (c->dBinHint) p.binHint = c->dBinHint + pass;          // (host-visible word per pass, allocated with the G-buffer)
-        if (!c->dLeftCmds) LR_HIP(hipMalloc((void**)&c->dLeftCmds, sizeof(ChordDrawCmd) * (size_t)c->cmdCapacity));
+        if (!c->dLeftCmds) LR_HIP(hipMalloc((void**)&c->dLeftCmds, sizeof(ChordDrawCmd) * c->allocCmds));
         p.leftCount = c->dCounts + 6 + pass; p.leftCmds = c->dLeftCmds;
         if (!c->inFrame || c->rasterCalls >= 2) LR_HIP(hipMemsetAsync(p.leftCount, 0, sizeof(uint32_t), c->stream));
     }

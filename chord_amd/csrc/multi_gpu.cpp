@@ -632,6 +632,13 @@ int chordvis_group_update_objects(ChordGroup* g, const ChordObject* hostObjects,
     return run_all(g, [&](uint32_t r) { return chordvis_update_objects(g->ctx[r], hostObjects, count); }, "group_update_objects");
 }
 
+int chordvis_group_set_object_list(ChordGroup* g, const ChordObject* hostObjects, uint32_t count)
+{
+    if (!g || !hostObjects) return gfail(g, CHORDVIS_E_INVALID, "group_set_object_list: null argument");
+    // (replicated; every rank derives the same totals, so a list one rank refuses every rank refuses, and each keeps its old list)
+    return run_all(g, [&](uint32_t r) { return chordvis_set_object_list(g->ctx[r], hostObjects, count); }, "group_set_object_list");
+}
+
 int chordvis_group_upload_world_transforms(ChordGroup* g, const double* hostLocalToWorld, const double* hostPrevLocalToWorld, uint32_t count)
 {
     if (!g || !hostLocalToWorld) return gfail(g, CHORDVIS_E_INVALID, "group_upload_world_transforms: null argument");

@@ -228,6 +228,7 @@ def _load():
         "chordvis_upload_scene": (i32, [vp, P(R.SceneDesc)]),
         "chordvis_update_objects": (i32, [vp, vp, u32]),
         "chordvis_bind_objects": (i32, [vp, vp, u32]),
+        "chordvis_set_object_list": (i32, [vp, vp, u32]),
         "chordvis_upload_world_transforms": (i32, [vp, vp, vp, u32]),
         "chordvis_scatter_world_transforms": (i32, [vp, vp, vp, u32]),
         "chordvis_build_objects": (i32, [vp, vp, vp]),
@@ -338,6 +339,7 @@ def _load():
         "chordvis_group_allocate_gbuffer": (i32, [vp, u32, u32]),
         "chordvis_group_rebalance": (i32, [vp, vp]),
         "chordvis_group_update_objects": (i32, [vp, vp, u32]),
+        "chordvis_group_set_object_list": (i32, [vp, vp, u32]),
         "chordvis_group_upload_world_transforms": (i32, [vp, vp, vp, u32]),
         "chordvis_group_build_objects": (i32, [vp, vp, vp]),
         "chordvis_group_set_view": (i32, [vp, vp, vp, u32]),

@@ -339,6 +339,17 @@ class VisibilityRenderer:
     def bind_objects(self, device_ptr, count):
         self._check(L.lib.chordvis_bind_objects(self._ctx, device_ptr, count), "bind_objects")
 
+    def set_object_list(self, objects):
+        """chordvis_set_object_list: another object list -- any count >= 1, any primitives and materials of the resident scene -- without
+        uploading the scene again; the history HZB and the material textures stay.  objects: records.OBJECT records, or a records.Scene
+        over the same assets (scene.with_objects(...)), which then becomes self.scene (what read_objects and the other helpers size
+        their arrays by).  Never waits while the list fits what earlier lists had allocated.  A refusal leaves the context as it was."""
+        scene = objects if isinstance(objects, R.Scene) else None
+        records = np.ascontiguousarray(scene.objects if scene is not None else objects, dtype=R.OBJECT)
+        self._check(L.lib.chordvis_set_object_list(self._ctx, records.ctypes.data if len(records) else None, len(records)), "set_object_list")
+        if scene is not None:
+            self.scene = scene
+
     # -- object records built on the device (chordvis_build_objects) -------------------------------
     def upload_world_transforms(self, local_to_world, prev_local_to_world=None):
         """chordvis_upload_world_transforms: the objects' f64 world matrices (n, 16) or (n, 4, 4) glm column-major, resident on the
@@ -890,6 +901,16 @@ class VisibilityGroup:
     def update_objects(self, objects):
         objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
         self._check(L.lib.chordvis_group_update_objects(self._g, objects.ctypes.data, len(objects)), "group_update_objects")
+
+    def set_object_list(self, objects):
+        """chordvis_group_set_object_list: VisibilityRenderer.set_object_list on every rank (records.OBJECT records, or a Scene)."""
+        scene = objects if isinstance(objects, R.Scene) else None
+        records = np.ascontiguousarray(scene.objects if scene is not None else objects, dtype=R.OBJECT)
+        self._check(L.lib.chordvis_group_set_object_list(self._g, records.ctypes.data if len(records) else None, len(records)), "group_set_object_list")
+        if scene is not None:
+            self.scene = scene
+            for r in self.ranks:
+                r.scene = scene
 
     def upload_world_transforms(self, local_to_world, prev_local_to_world=None):
         """chordvis_group_upload_world_transforms: every rank keeps the f64 world matrices (see VisibilityRenderer)."""

@@ -226,7 +226,8 @@ int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
  *     chordvis_resolve_gbuffer; chordvis_last_frame_cmds and chordvis_history_hzb (handles of device memory that the frames in flight
  *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain);
  *     chordvis_scatter_world_transforms and chordvis_build_objects (one launch each, of any size: the way to new object records
- *     for a host that must not wait).
+ *     for a host that must not wait); chordvis_set_object_list while the new list fits what is allocated (it MAY WAIT when a buffer
+ *     has to grow: OBJECTS COME AND GO below).
  *     The kernels a frame launches are chosen from reports the device leaves when a pass finishes; the host may hold a report any
  *     number of frames old, or none: the choice costs or saves time, never a pixel, a list entry or an HZB texel.
  *   MAY WAIT for everything enqueued before it: chordvis_upload_scene, chordvis_upload_material_textures,
@@ -275,7 +276,8 @@ int chordvis_sync(ChordCtx* ctx);
  * succeeds.  The G-buffer and every setting stay, so that upload may follow at once (after chordvis_set_cull_mode(ctx, 0), say). */
 int chordvis_upload_scene(ChordCtx* ctx, const ChordSceneDesc* scene);
 /* uploadBufferToGPU("GLTFObjectInfo", ...) renderer.cpp:229 — per-frame object records
- * (count must equal the uploaded scene's objectCount; primitive/material ids must not change). */
+ * (count must equal the current list's count -- the uploaded scene's objectCount, or that of the latest chordvis_set_object_list;
+ * primitive/material ids must not change: a list of other objects goes through chordvis_set_object_list). */
 int chordvis_update_objects(ChordCtx* ctx, const ChordObject* hostObjects, uint32_t count);
 /* Same, for a caller-owned DEVICE array (no copy; must stay valid while bound).  The array stays bound -- the depth views read
  * it too -- until chordvis_update_objects or chordvis_upload_scene returns the context to its own copy.  The caller may rewrite
@@ -284,6 +286,49 @@ int chordvis_update_objects(ChordCtx* ctx, const ChordObject* hostObjects, uint3
  * is not written.  The call itself counts as a change of the objects, exactly like chordvis_update_objects: a chordvis_resolve_*
  * after it is refused (CHORDVIS_E_INVALID) until the next frame has run -- also when the same array is bound again. */
 int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint32_t count);
+
+/* OBJECTS COME AND GO.  The reference collects its object list anew every frame (getPerframeCollected + uploadBufferToGPU("GLTFObjectInfo"),
+ * renderer.cpp:217,229) over geometry that stays resident in the GPUScene pools (gpu_scene.h:20-165).  chordvis_set_object_list is
+ * that for this library: it replaces the object LIST of the resident scene -- any count >= 1, any primitive and any material of the
+ * uploaded scene in any order and any number of times, primitives no object named at upload included -- and copies no vertex, meshlet
+ * or texture.  hostObjects are complete records (basicData for the next frame and the two ids), as in ChordSceneDesc::objects.
+ *   EQUIVALENCE.  After a successful call the context behaves, for everything that depends on the objects, exactly like a context that
+ *     uploaded the same scene descriptor with objects = hostObjects, objectCount = count: the image, the three command lists (order,
+ *     slot fields and counts), the HZB chains, chordvis_stats' counts and the handles' `capacity` are bit for bit that context's, in
+ *     every cull path (fused, three-launch, quad, hierarchical, sharded, the depth views).  The capacities the kernels see are always
+ *     those of such an upload, whatever the buffers hold.
+ *   KEPT: every asset, primitive and material table, the alpha plane; the material textures of chordvis_upload_material_textures with
+ *     their block store, first levels and feedback counts; the G-buffer, the view, the limits, the cull mode, the debug switches, the
+ *     kept tile schedules; and the HISTORY HZB -- the next frame is a two-pass frame against the previous frame's chain, with the new
+ *     objects' own last-frame matrices, and a previous frame's HZB tail that still waits to ride in the next cull launch still runs.
+ *   DROPPED, as chordvis_upload_scene drops them and with the same refusals afterwards, because each is sized by or names the old list:
+ *     the geometry feedback buffer (chordvis_geometry_feedback is refused until chordvis_geometry_feedback_reset); the resident world
+ *     transforms (chordvis_build_objects is refused until chordvis_upload_world_transforms); a chordvis_bind_objects binding (the
+ *     context reads its own array again, which receives hostObjects); the depth views and the cascade cache (the next
+ *     chordvis_render_shadow makes the views again and renders every cascade; the view-by-view depth calls are refused until
+ *     chordvis_allocate_depth_views); the sharded lists and the cull exchange buffer
+ *     (re-made on demand, as at upload); the resolve state -- chordvis_resolve_*, the feedback calls and everything else that needs a
+ *     frame's image are refused until a frame has run.
+ *   VALIDATE FIRST, COMMIT SECOND.  CHORDVIS_E_INVALID: count == 0 or hostObjects NULL; a primitive or material id out of range; no
+ *     scene; a depth-view child context; a call between chordvis_frame_phase_cull and chordvis_frame_phase_a.  CHORDVIS_E_CAPACITY:
+ *     2^24 - 2 or more cluster instances, or more than 2^31 - 1 group instances.  A refused call changes NOTHING -- unlike a refused
+ *     chordvis_upload_scene: the context still renders the list it had, with its history, and chordvis_last_error names the rule.  The
+ *     same holds when a buffer the longer list needs cannot be allocated (CHORDVIS_E_HIP): every new buffer is made before an old one
+ *     is let go.
+ *   STREAM ORDER AND MEMORY.  The device buffers sized by the list (object records and frames, the static and the group tables, group
+ *     masks, block counts, the three command lists, the raster record lists and the block pool) only ever grow.  When the new list
+ *     fits what is allocated the call is stream-ordered behind the frames in flight and NEVER WAITS for the device: one copy of the
+ *     records, one copy of the 48-byte static records, one kernel launch that builds the flattened (object, group) table on the
+ *     device (kernels_objects.hip), and what it drops is parked and freed by a later call that waits anyway (chordvis_sync,
+ *     chordvis_upload_scene, a chordvis_set_object_list that grows, chordvis_destroy; with 32 allocations parked the call itself waits once).  hostObjects is read before the call
+ *     returns and is the caller's again on return, under the rule of chordvis_update_objects above (a large pageable array makes the
+ *     HIP runtime's copy wait).  When something must grow the call MAY WAIT: it lets the stream run empty first, because a frame in
+ *     flight keeps its buffers, then swaps the buffers.  Allocations never shrink before chordvis_upload_scene or chordvis_destroy.  A
+ *     host that wants no stall gives its LARGEST list once, up front -- at upload, or in one chordvis_set_object_list -- and shorter ones after it.
+ *     On a sharded context the cull exchange buffer follows the list's count blocks (it is re-made, with a wait, whenever
+ *     ceil(count blocks / ranks) changes).
+ * tests/test_gpu_object_list.py holds every statement; DESIGN.md 4.15 has the kernel and the timings. */
+int chordvis_set_object_list(ChordCtx* ctx, const ChordObject* hostObjects, uint32_t count);
 
 /* OBJECT RECORDS BUILT ON THE DEVICE.  Every field of ChordObject::basicData is camera-relative, so a moving camera changes the record
  * of every object, static ones included.  Instead of filling the records on the host (chordvis_object_basic_data_batch) and copying
@@ -539,6 +584,9 @@ int chordvis_group_allocate_gbuffer(ChordGroup* group, uint32_t width, uint32_t 
 /* chordvis_rebalance on every rank (drains the frames in flight first) */
 int chordvis_group_rebalance(ChordGroup* group, uint32_t* imbalancePermille);
 int chordvis_group_update_objects(ChordGroup* group, const ChordObject* hostObjects, uint32_t count);
+/* chordvis_set_object_list on every rank (the list is replicated like the scene; a list one rank refuses every rank refuses, and
+ * each keeps the list it had).  On the sharded ranks the call re-makes the cull exchange buffer for the new count blocks. */
+int chordvis_group_set_object_list(ChordGroup* group, const ChordObject* hostObjects, uint32_t count);
 /* chordvis_upload_world_transforms / chordvis_build_objects on every rank (the transforms are replicated like the scene).  There is no
  * group scatter: the device arrays are per device, so a host that needs one goes through the ranks' contexts (chordvis_group_ctx). */
 int chordvis_group_upload_world_transforms(ChordGroup* group, const double* hostLocalToWorld, const double* hostPrevLocalToWorld, uint32_t count);
@@ -1155,7 +1203,10 @@ int chordvis_set_debug(ChordCtx* ctx, uint32_t flags);
 int chordvis_debug_fill_cull_exchange(ChordCtx* ctx);
 /* debugging aid: raw read of an internal buffer (0 tile counts, 1 fixed bins, 2 chunk table, 3 bin pool, 4 / 5 32- / 48-byte records,
  * 7 the alpha plane the masked buckets sample: one byte per texel, every level of every texture a masked material samples, in
- * texture order; CHORDVIS_E_INVALID when the scene has none) */
+ * texture order; CHORDVIS_E_INVALID when the scene has none; 8 the flattened (object, group) table, 24 bytes per group instance of
+ * the current object list: owner, group | meshlet count << 28, four global meshlet ids; 9 the per-object static table, 48 bytes per
+ * object: primitive, material flags | material << 8, first group instance, shading type, the primitive's bounds -- for 8 and 9 a
+ * range beyond the current list's table is CHORDVIS_E_INVALID) */
 int chordvis_debug_read(ChordCtx* ctx, int which, uint64_t offset, uint64_t bytes, void* host);
 /* debugging aid: non-zero words in the split-tile accumulation slabs (must be 0 between raster passes) */
 int chordvis_debug_slab_nonzero(ChordCtx* ctx, uint64_t* count);
