@@ -331,6 +331,22 @@ void free_retired(ChordCtx* c)      // (the caller has let the stream run empty)
     c->retiredChildren.clear();
 }
 
+// The ray scene (chordvis_build_ray_scene).  The TLAS belongs to an object list: chordvis_set_object_list parks its buffers without
+// waiting; the BLASes belong to a scene upload, which has let the stream run empty before it frees them.
+void drop_ray_tlas(ChordCtx* c, bool park)
+{
+    if (park) { retire(c, c->dRayTlas); retire(c, c->dRayLeafRef); retire(c, c->dRayCounters); retire(c, c->dRayLeafBox); retire(c, c->dRayRoot); }
+    else { dfree(c->dRayTlas); dfree(c->dRayLeafRef); dfree(c->dRayCounters); dfree(c->dRayLeafBox); dfree(c->dRayRoot); }
+    c->rayTlasBuilt = false; c->rayRefitDue = false; c->rayTlasNodes = c->rayTlasDepth = 0; c->rayTlasBytes = 0;
+}
+
+void drop_ray_scene(ChordCtx* c)          // (the caller has let the stream run empty)
+{
+    drop_ray_tlas(c, false);
+    dfree(c->dRayBlas); dfree(c->dRayTriangles); dfree(c->dRayBlasRoot); dfree(c->dRayCounts);
+    c->rayBlasBuilt = false; c->rayBlasNodes = c->rayBlasTriangles = c->rayBlasDepth = 0; c->rayBlasBytes = 0;
+}
+
 // The per-object static table and the totals every launch is sized by, from an object list and the resident scene's tables (hPrims,
 // hPrimMeshlets, hPrimTriangles, hMatFlags, hMatType), in O(count): what chordvis_upload_scene and chordvis_set_object_list share.
 // Nothing of the context is written but `out` (the caller's) and, on a refusal, the error text.
@@ -748,6 +764,7 @@ int chordvis_destroy(ChordCtx* c)
     dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dBoundsTilesScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     drop_world_transforms(c);
+    drop_ray_scene(c);
     for (int i = 0; i < 3; i++) dfree(c->lists[i].cmds);
     dfree(c->dRankCmds); dfree(c->dLeftCmds); dfree(c->dMineCmds);
     dfree(c->dCullLookback);
@@ -786,6 +803,7 @@ int chordvis_upload_scene(ChordCtx* c, const ChordSceneDesc* s)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         drop_world_transforms(c);
+        drop_ray_scene(c);
         free_retired(c);
     }
     const int rc = upload_scene_impl(c, s);
@@ -1005,6 +1023,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
     dfree(c->dCullExchange);                                               // (sized by the scene's count blocks: re-made on demand)
     c->objectCount = s->objectCount; c->primCount = s->primitiveCount; c->materialCount = s->materialCount;
     c->meshletCount = nM; c->groupCount = nG;
+    c->groupIndexWords = nI; c->meshletDataWords = nD; c->vertexTotal = nV;     // (what chordvis_build_ray_scene reads back)
     c->groupInstances = (uint32_t)groupInst; c->cmdCapacity = (uint32_t)std::max<uint64_t>(cmdCap, 1);
     c->cullBlocks = std::max(1u, (c->groupInstances + 255u) / 256u);
 
@@ -1510,6 +1529,7 @@ int chordvis_update_objects(ChordCtx* c, const ChordObject* hostObjects, uint32_
     CHORD_HIP(c, hipMemcpyAsync(c->dObjectsOwned, hostObjects, sizeof(ChordObject) * count, hipMemcpyHostToDevice, c->stream));
     c->dObjects = c->dObjectsOwned;
     c->resolveStale = true;
+    c->rayRefitDue = true;
     return CHORDVIS_OK;
 }
 
@@ -1518,6 +1538,7 @@ int chordvis_bind_objects(ChordCtx* c, const ChordObject* deviceObjects, uint32_
     if (!c || !c->sceneLoaded || !deviceObjects || count != c->objectCount) return fail(c, CHORDVIS_E_INVALID, "bind_objects: count must equal the uploaded scene's objectCount");
     c->dObjects = deviceObjects;
     c->resolveStale = true;                               // (like chordvis_update_objects: the array a resolve would read is no longer the frame's)
+    c->rayRefitDue = true;
     return CHORDVIS_OK;
 }
 
@@ -1598,6 +1619,7 @@ int chordvis_set_object_list(ChordCtx* c, const ChordObject* hostObjects, uint32
     c->mineValid = false; c->listMine[1] = c->listMine[2] = false; c->fullListStale = false;
     retire(c, c->dGeoFeedback); c->geoFeedbackCmds = nullptr;
     retire(c, c->dWorldCur); retire(c, c->dWorldPrev); retire(c, c->dBuildStatus); c->buildCount = 0;
+    drop_ray_tlas(c, true);                               // (the BLASes are the scene's and stay)
     if (c->depthCtx) { c->retiredChildren.push_back(c->depthCtx); c->depthCtx = nullptr; }
     c->shadowHistoryValid = false; c->fusedDepthView = -1;
     c->resolveFrame = false;
@@ -1664,6 +1686,7 @@ int chordvis_build_objects(ChordCtx* c, const double cameraPos[3], const double 
     c->buildCount++;
     c->dObjects = c->dObjectsOwned;
     c->resolveStale = true;                               // (like chordvis_update_objects)
+    c->rayRefitDue = true;
     return CHORDVIS_OK;
 }
 
@@ -1700,6 +1723,241 @@ int chordvis_readback_world_transforms(ChordCtx* c, double* hostCur, double* hos
     const size_t bytes = (size_t)count * 16u * sizeof(double);
     if (hostCur) CHORD_HIP(c, hipMemcpy(hostCur, c->dWorldCur, bytes, hipMemcpyDeviceToHost));
     if (hostPrev) CHORD_HIP(c, hipMemcpy(hostPrev, c->dWorldPrev, bytes, hipMemcpyDeviceToHost));
+    return CHORDVIS_OK;
+}
+
+// ---- ray queries on the resident scene (include/chordvis.h RAY QUERIES; ray_scene.cpp; kernels_rays.hip) ----
+
+extern "C++" {
+namespace {
+
+int ray_checks(ChordCtx* c, const char* fn, bool needTlas)
+{
+    char buf[160];
+    auto refuse = [&](const char* why) { std::snprintf(buf, sizeof(buf), "%s: %s", fn, why); return fail(c, CHORDVIS_E_INVALID, buf); };
+    if (c->sharedScene) return refuse("not on a depth-view context");
+    if (!c->sceneLoaded) return refuse("no scene (call chordvis_upload_scene first)");
+    if (needTlas && !(c->rayBlasBuilt && c->rayTlasBuilt))
+        return refuse("no ray scene, or it was dropped by chordvis_upload_scene / chordvis_set_object_list (call chordvis_build_ray_scene)");
+    return CHORDVIS_OK;
+}
+
+// the host's own copy of the object stage's box (kernels_rays.hip ray_refit_kernel): it shapes the TLAS, the device's boxes fill it
+ray::Box host_object_box(const ChordObject& ob, const float* posMin, const float* posMax)
+{
+    const float* m = ob.basicData.localToTranslatedWorld.m;
+    ray::Box b;
+    for (int k = 0; k < 8; k++) {
+        float q[3];
+        for (int a = 0; a < 3; a++) {
+            const float cen = (posMin[a] + posMax[a]) * 0.5f, ext = posMax[a] - cen;
+            q[a] = ((k >> a) & 1) ? cen + ext : cen - ext;
+        }
+        for (int a = 0; a < 3; a++) {
+            const float p = ((m[a] * q[0] + m[4 + a] * q[1]) + m[8 + a] * q[2]) + m[12 + a];
+            b.lo[a] = k == 0 ? p : ray::fmin_(b.lo[a], p);
+            b.hi[a] = k == 0 ? p : ray::fmax_(b.hi[a], p);
+        }
+    }
+    return b;
+}
+
+struct RayBlasBuild {
+    std::vector<ray::Node> nodes;
+    std::vector<ray::Triangle> triangles;
+    std::vector<uint32_t> roots;
+    uint32_t depth = 0;
+};
+
+// One BLAS per primitive from the resident scene's streams, read back (the stream has run empty).
+int ray_build_blases(ChordCtx* c, RayBlasBuild& out)
+{
+    std::vector<DMeshlet> meshlets(c->meshletCount);
+    std::vector<uint8_t> lod(c->meshletCount);
+    std::vector<DGroup> groups(c->groupCount);
+    std::vector<uint32_t> gidx(c->groupIndexWords), mdata(c->meshletDataWords);
+    std::vector<float> pos((size_t)c->vertexTotal * 3u);
+#define DOWN(vec, src) if (!vec.empty()) CHORD_HIP(c, hipMemcpy(vec.data(), src, vec.size() * sizeof(vec[0]), hipMemcpyDeviceToHost));
+    DOWN(meshlets, c->dMeshlets) DOWN(lod, c->dMeshletLod) DOWN(groups, c->dGroups) DOWN(gidx, c->dGroupIndices) DOWN(mdata, c->dMeshletData)
+    DOWN(pos, c->dPositions)
+#undef DOWN
+    out.roots.assign(c->hPrims.size(), ray::kNoChild);
+    std::vector<uint32_t> ids;
+    std::vector<ray::Triangle> tris;
+    std::vector<ray::Box> boxes;
+    for (size_t pi = 0; pi < c->hPrims.size(); pi++) {
+        const DPrim& pr = c->hPrims[pi];
+        // the primitive's LOD-0 meshlets, reached through its groups, each once, in ascending order (upload_scene checked every index)
+        ids.clear();
+        for (uint32_t gl = 0; gl < pr.groupCount; gl++) {
+            const DGroup& g = groups[pr.groupBase + gl];
+            for (uint32_t i = 0; i < g.meshletCount; i++) {
+                const uint32_t m = pr.meshletBase + gidx[pr.groupIndicesBase + g.meshletOffset + i];
+                if (lod[m] == 0u) ids.push_back(m);
+            }
+        }
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        tris.clear();
+        for (uint32_t m : ids) {
+            const DMeshlet& ml = meshlets[m];
+            const uint32_t V = ml.vertexTriangleCount & 0xFFu, T = (ml.vertexTriangleCount >> 8) & 0xFFu;
+            for (uint32_t t = 0; t < T; t++) {
+                const uint32_t w = mdata[ml.dataOffset + V + t];
+                ray::Triangle tr{};
+                for (int k = 0; k < 3; k++) {
+                    const uint32_t vid = ml.vertexBase + mdata[ml.dataOffset + ((w >> (8 * k)) & 0xFFu)];
+                    for (int a = 0; a < 3; a++) tr.v[3 * k + a] = pos[(size_t)vid * 3u + a];
+                }
+                for (int k = 0; k < 9; k++)
+                    if (!std::isfinite(tr.v[k])) return fail(c, CHORDVIS_E_INVALID, "build_ray_scene: a LOD-0 triangle has a non-finite position");
+                tr.meshlet = m - pr.assetMeshletBase; tr.triangle = t;
+                tris.push_back(tr);
+            }
+        }
+        if (tris.empty()) continue;
+        if (out.triangles.size() + tris.size() >= ray::kMaxTriangles || out.nodes.size() + tris.size() >= ray::kIndexMask)
+            return fail(c, CHORDVIS_E_CAPACITY, "build_ray_scene: 2^28 - 4 or more LOD-0 triangles in the scene");
+        boxes.resize(tris.size());
+        for (size_t i = 0; i < tris.size(); i++) boxes[i] = ray::triangle_box(tris[i]);
+        ray::Tree tree;
+        const int rc = ray::build_tree(boxes.data(), (uint32_t)tris.size(), ray::kLeafTriangles, ray::kBlasNode, ray::kBlasLeaf,
+                                       (uint32_t)out.nodes.size(), (uint32_t)out.triangles.size(), tree);
+        if (rc) return fail(c, CHORDVIS_E_CAPACITY, "build_ray_scene: a primitive's BLAS is deeper than CHORD_RAY_MAX_DEPTH levels (more than 4^12 leaves of four triangles)");
+        out.roots[pi] = (ray::kBlasNode << ray::kTagShift) | (uint32_t)out.nodes.size();
+        out.nodes.insert(out.nodes.end(), tree.nodes.begin(), tree.nodes.end());
+        for (uint32_t i : tree.order) out.triangles.push_back(tris[i]);
+        out.depth = std::max(out.depth, tree.depth);
+    }
+    return CHORDVIS_OK;
+}
+
+template <typename T>
+int ray_upload(ChordCtx* c, T*& fresh, const void* host, size_t count, uint64_t& bytes)
+{
+    const size_t n = std::max<size_t>(count, 1) * sizeof(T);
+    const hipError_t e = hipMalloc((void**)&fresh, n);
+    if (e != hipSuccess) { fresh = nullptr; return fail(c, CHORDVIS_E_HIP, "build_ray_scene: hipMalloc of a ray scene buffer", e); }
+    bytes += n;
+    if (host && count) CHORD_HIP(c, hipMemcpy(fresh, host, count * sizeof(T), hipMemcpyHostToDevice));
+    else if (!host) CHORD_HIP(c, hipMemsetAsync(fresh, 0, n, c->stream));
+    return CHORDVIS_OK;
+}
+
+} // namespace
+} // extern "C++"
+
+int chordvis_ray_scene_info(ChordCtx* c, ChordRaySceneInfo* out)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    if (!out) return fail(c, CHORDVIS_E_INVALID, "ray_scene_info: outInfo is NULL");
+    { const int rc = ray_checks(c, "ray_scene_info", true); if (rc) return rc; }
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    float root[8];
+    CHORD_HIP(c, hipMemcpy(root, c->dRayRoot, sizeof(root), hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof(*out));
+    out->blasCount = c->primCount; out->blasNodes = c->rayBlasNodes; out->blasTriangles = c->rayBlasTriangles;
+    out->blasMaxDepth = c->rayBlasDepth; out->tlasNodes = c->rayTlasNodes; out->tlasDepth = c->rayTlasDepth;
+    out->deviceBytes = c->rayBlasBytes + c->rayTlasBytes;
+    for (int a = 0; a < 3; a++) { out->rootMin[a] = root[a]; out->rootMax[a] = root[4 + a]; }
+    return CHORDVIS_OK;
+}
+
+// Everything is built on the host and every new device buffer made and filled before anything of the context's ray scene is touched.
+int chordvis_build_ray_scene(ChordCtx* c, ChordRaySceneInfo* outInfo)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    { const int rc = ray_checks(c, "build_ray_scene", false); if (rc) return rc; }
+    (void)hipSetDevice(c->device);
+    CHORD_HIP(c, hipStreamSynchronize(c->stream));
+    free_retired(c);                                      // (what chordvis_set_object_list parked, a TLAS before this one among it)
+#if CHORD_RAY_COUNTERS
+    if (!c->dRayCounts) {
+        CHORD_HIP(c, hipMalloc((void**)&c->dRayCounts, sizeof(unsigned long long) * CHORD_RAY_COUNTER_WORDS));
+        CHORD_HIP(c, hipMemset(c->dRayCounts, 0, sizeof(unsigned long long) * CHORD_RAY_COUNTER_WORDS));
+    }
+#endif
+
+    const bool buildBlas = !c->rayBlasBuilt;
+    RayBlasBuild blas;
+    if (buildBlas) { const int rc = ray_build_blases(c, blas); if (rc) return rc; }
+
+    // the TLAS over the boxes of the object array the frames read now
+    std::vector<ChordObject> objects(c->objectCount);
+    CHORD_HIP(c, hipMemcpy(objects.data(), c->dObjects, sizeof(ChordObject) * objects.size(), hipMemcpyDeviceToHost));
+    std::vector<ray::Box> boxes(c->objectCount);
+    for (uint32_t o = 0; o < c->objectCount; o++) boxes[o] = host_object_box(objects[o], c->hObjStatic[o].posMin, c->hObjStatic[o].posMax);
+    ray::Tree tlas;
+    if (ray::build_tree(boxes.data(), c->objectCount, 1u, ray::kTlasNode, ray::kTlasLeaf, 0u, 0u, tlas))
+        return fail(c, CHORDVIS_E_CAPACITY, "build_ray_scene: the TLAS is deeper than CHORD_RAY_MAX_DEPTH levels (more than 4^12 objects)");
+
+    ray::Node *fBlas = nullptr, *fTlas = nullptr;
+    ray::Triangle* fTris = nullptr;
+    uint32_t *fRoots = nullptr, *fLeafRef = nullptr, *fCounters = nullptr;
+    float *fLeafBox = nullptr, *fRoot = nullptr;
+    uint64_t blasBytes = 0, tlasBytes = 0;
+    int rc = CHORDVIS_OK;
+    if (buildBlas) {
+        if (!rc) rc = ray_upload(c, fBlas, blas.nodes.data(), blas.nodes.size(), blasBytes);
+        if (!rc) rc = ray_upload(c, fTris, blas.triangles.data(), blas.triangles.size(), blasBytes);
+        if (!rc) rc = ray_upload(c, fRoots, blas.roots.data(), blas.roots.size(), blasBytes);
+    }
+    if (!rc) rc = ray_upload(c, fTlas, tlas.nodes.data(), tlas.nodes.size(), tlasBytes);
+    if (!rc) rc = ray_upload(c, fLeafRef, tlas.leafRef.data(), tlas.leafRef.size(), tlasBytes);
+    if (!rc) rc = ray_upload(c, fCounters, nullptr, tlas.nodes.size(), tlasBytes);
+    if (!rc) rc = ray_upload(c, fLeafBox, nullptr, (size_t)c->objectCount * 8u, tlasBytes);
+    if (!rc) rc = ray_upload(c, fRoot, nullptr, 8u, tlasBytes);
+    if (rc) {
+        dfree(fBlas); dfree(fTris); dfree(fRoots); dfree(fTlas); dfree(fLeafRef); dfree(fCounters); dfree(fLeafBox); dfree(fRoot);
+        return rc;
+    }
+
+    // commit (the stream is empty: nothing reads the old buffers)
+    if (buildBlas) {
+        dfree(c->dRayBlas); dfree(c->dRayTriangles); dfree(c->dRayBlasRoot);
+        c->dRayBlas = fBlas; c->dRayTriangles = fTris; c->dRayBlasRoot = fRoots;
+        c->rayBlasNodes = (uint32_t)blas.nodes.size(); c->rayBlasTriangles = (uint32_t)blas.triangles.size(); c->rayBlasDepth = blas.depth;
+        c->rayBlasBytes = blasBytes; c->rayBlasBuilt = true;
+    }
+    drop_ray_tlas(c, false);
+    c->dRayTlas = fTlas; c->dRayLeafRef = fLeafRef; c->dRayCounters = fCounters; c->dRayLeafBox = fLeafBox; c->dRayRoot = fRoot;
+    c->rayTlasNodes = (uint32_t)tlas.nodes.size(); c->rayTlasDepth = tlas.depth; c->rayTlasBytes = tlasBytes; c->rayTlasBuilt = true;
+
+    rc = chordvis_refit_ray_scene(c);
+    if (rc) return rc;
+    if (outInfo) {
+        rc = chordvis_ray_scene_info(c, outInfo);
+        if (rc) return rc;
+        outInfo->blasBuilt = buildBlas ? c->primCount : 0u;
+    }
+    return CHORDVIS_OK;
+}
+
+int chordvis_refit_ray_scene(ChordCtx* c)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    { const int rc = ray_checks(c, "refit_ray_scene", true); if (rc) return rc; }
+    (void)hipSetDevice(c->device);
+    chord::launch_ray_refit(c);
+    CHORD_HIP(c, hipGetLastError());
+    c->rayRefitDue = false;
+    return CHORDVIS_OK;
+}
+
+int chordvis_trace_rays(ChordCtx* c, const ChordRay* deviceRays, uint32_t count, uint32_t flags, ChordRayHit* deviceHits)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    { const int rc = ray_checks(c, "trace_rays", true); if (rc) return rc; }
+    if (flags & ~CHORD_RAY_ANY_HIT) return fail(c, CHORDVIS_E_INVALID, "trace_rays: unknown flag bits (CHORD_RAY_ANY_HIT is the only flag)");
+    if (c->rayRefitDue)
+        return fail(c, CHORDVIS_E_INVALID, "trace_rays: the objects changed (chordvis_update_objects / chordvis_build_objects / chordvis_bind_objects): call chordvis_refit_ray_scene first");
+    if (count == 0) return CHORDVIS_OK;
+    if (!deviceRays || !deviceHits || ((uintptr_t)deviceRays & 15u) || ((uintptr_t)deviceHits & 15u))
+        return fail(c, CHORDVIS_E_INVALID, "trace_rays: deviceRays and deviceHits must be non-NULL and 16-byte aligned when count > 0");
+    (void)hipSetDevice(c->device);
+    chord::launch_ray_trace(c, deviceRays, count, (flags & CHORD_RAY_ANY_HIT) != 0u, deviceHits);
+    CHORD_HIP(c, hipGetLastError());
     return CHORDVIS_OK;
 }
 
@@ -2996,7 +3254,7 @@ int chordvis_debug_graph_frames(ChordCtx* c, uint32_t pairs, float* msPerFrameSt
 
 // Debugging aid: raw read of an internal buffer.  which: 0 tile counts (FrameState::tileCount), 1 fixed bins, 2 chunk table,
 // 3 bin pool, 4 compact records, 5 wide records, 6 the fused cull kernel's look-back words, 7 the alpha plane (dTexAlpha),
-// 8 the flattened (object, group) table (DGroupRef, 24 bytes per group instance), 9 the per-object static table (DObjStatic, 48
+// 10 the ray traversal sums of a measuring build; 8 the flattened (object, group) table (DGroupRef, 24 bytes per group instance), 9 the per-object static table (DObjStatic, 48
 // bytes per object) -- the two checked against the current list's size.  offset / bytes in bytes.
 int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes, void* host)
 {
@@ -3020,6 +3278,11 @@ int chordvis_debug_read(ChordCtx* c, int which, uint64_t offset, uint64_t bytes,
         base = which == 8 ? (const char*)c->dGroupRefs : (const char*)c->dObjStatic;
         break;
     }
+    case 10:                                                   // the traversal sums of a CHORD_RAY_COUNTERS build (device_layer.h)
+        if (!c->dRayCounts || offset > sizeof(unsigned long long) * CHORD_RAY_COUNTER_WORDS || bytes > sizeof(unsigned long long) * CHORD_RAY_COUNTER_WORDS - offset)
+            return fail(c, CHORDVIS_E_INVALID, "debug_read: no ray counters (a library built with -DCHORD_RAY_COUNTERS=1, after chordvis_build_ray_scene), or a range beyond them");
+        base = (const char*)c->dRayCounts;
+        break;
     default: return fail(c, CHORDVIS_E_INVALID, "debug_read: unknown buffer");
     }
     CHORD_HIP(c, hipMemcpy(host, base + offset, bytes, hipMemcpyDeviceToHost));

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "chordvis.h"
+#include "ray_scene.h"
 
 // Build switches of the measurement code in the raster kernels (kernels_raster.hip): per-phase clocks (chordvis_set_debug
 // bits 16 and 512) and ablation switches (bits 1, 2, 32, 64, 128, 256, 1024, 2048, 4096, 8192, 16384).  Off in the product
@@ -24,6 +25,14 @@
 #ifndef RASTER_ABLATION
 #define RASTER_ABLATION 0
 #endif
+// The measuring build of the ray traversal (kernels_rays.hip): python chord_amd/build.py --tag raycount -DCHORD_RAY_COUNTERS=1 makes a
+// library whose ray_trace_kernel adds, per ray, the TLAS nodes, TLAS leaves (objects entered), BLAS nodes and triangles it tested into
+// CHORD_RAY_COUNTER_WORDS 64-bit sums (chordvis_debug_read selector 10: rays, TLAS nodes, TLAS leaves, BLAS nodes, triangles, one per
+// 64-byte line).  Off in the product library, whose kernel carries none of it (tools/ray_query_time.py).
+#ifndef CHORD_RAY_COUNTERS
+#define CHORD_RAY_COUNTERS 0
+#endif
+#define CHORD_RAY_COUNTER_WORDS 40u
 #define CHORD_DEBUG_PROFILE_BITS (16u | 512u)
 #define CHORD_DEBUG_ABLATION_BITS (1u | 2u | 32u | 64u | 128u | 256u | 1024u | 2048u | 4096u | 8192u | 16384u | 1048576u | 2097152u)
 
@@ -506,6 +515,24 @@ struct ChordCtx {
     // device memory chordvis_set_object_list dropped without waiting for the device (hipFree waits): freed by whichever call waits next
     std::vector<void*> retired;
     std::vector<ChordCtx*> retiredChildren;
+    // the ray scene (chordvis_build_ray_scene; ray_scene.h; kernels_rays.hip).  BLASes: per scene upload; TLAS: per object list
+    chord::ray::Node* dRayBlas = nullptr;          // the nodes of every primitive's BLAS
+    chord::ray::Triangle* dRayTriangles = nullptr; // the LOD-0 triangles of every primitive in leaf order
+    uint32_t* dRayBlasRoot = nullptr;              // per primitive: the child word of its root, ray::kNoChild: no LOD-0 triangle
+    uint32_t rayBlasNodes = 0, rayBlasTriangles = 0, rayBlasDepth = 0;
+    bool rayBlasBuilt = false;
+    chord::ray::Node* dRayTlas = nullptr;
+    uint32_t* dRayLeafRef = nullptr;               // per object: node * 4 + slot of its leaf
+    uint32_t* dRayCounters = nullptr;              // per TLAS node: arrivals of the refit under way, zero between launches
+    float* dRayLeafBox = nullptr;                  // per object: two float4 (lo, hi), written by the refit
+    float* dRayRoot = nullptr;                     // two float4: the root's box
+    uint32_t rayTlasNodes = 0, rayTlasDepth = 0;
+    bool rayTlasBuilt = false;
+    bool rayRefitDue = false;                      // the objects changed since the latest refit was enqueued
+    uint64_t rayBlasBytes = 0, rayTlasBytes = 0;
+    unsigned long long* dRayCounts = nullptr;      // CHORD_RAY_COUNTERS builds only: the traversal sums, made with the BLASes, never cleared
+    // what chordvis_build_ray_scene reads back of the resident scene: the lengths of the three streams the context did not keep
+    uint32_t groupIndexWords = 0, meshletDataWords = 0, vertexTotal = 0;
 
     // frame
     chord::DView hView{};
@@ -765,6 +792,10 @@ void launch_build_objects(ChordCtx* c, const double cameraPos[3], const double c
 // chordvis_set_object_list's launch: dGroupRefs[0 .. groupInstances) from dObjStatic[0 .. objectCount), dPrims, dGroups and
 // dGroupIndices, byte for byte what chordvis_upload_scene fills on the host.  One launch on the context's stream; none for no instances.
 void launch_group_refs_build(ChordCtx* c);
+// kernels_rays.hip: chordvis_refit_ray_scene's and chordvis_trace_rays' launches (arguments checked by the entry points).  One launch
+// each on the context's stream.
+void launch_ray_refit(ChordCtx* c);
+void launch_ray_trace(ChordCtx* c, const ChordRay* rays, uint32_t count, bool anyHit, ChordRayHit* hits);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -145,6 +145,21 @@ class BoundsTiles(C.Structure):
     _fields_ = [("tileCounts", C.c_void_p), ("tileItems", C.c_void_p), ("tileDepth", C.c_void_p), ("totals", C.c_void_p)]
 
 
+class RaySceneInfo(C.Structure):
+    """ChordRaySceneInfo: what chordvis_build_ray_scene built and the TLAS root's box (numpy rays: records.RAY / records.RAY_HIT)."""
+    _fields_ = [("blasCount", C.c_uint32), ("blasNodes", C.c_uint32), ("blasTriangles", C.c_uint32), ("blasBuilt", C.c_uint32),
+                ("blasMaxDepth", C.c_uint32), ("tlasNodes", C.c_uint32), ("tlasDepth", C.c_uint32), ("pad", C.c_uint32),
+                ("deviceBytes", C.c_uint64), ("rootMin", C.c_float * 3), ("rootMax", C.c_float * 3)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("rootMin", "rootMax") else getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
+
+
+RAY_ANY_HIT = 1                                    # chordvis_trace_rays flags
+RAY_HIT, RAY_BACK_FACE = 1, 2                      # ChordRayHit::status bits
+RAY_MAX_DEPTH = 12
+
+
 class CameraDesc(C.Structure):
     _fields_ = [
         ("position", C.c_double * 3), ("front", C.c_double * 3), ("worldUp", C.c_double * 3),
@@ -235,6 +250,10 @@ def _load():
         "chordvis_build_objects_status": (i32, [vp, P(u32), P(u32)]),
         "chordvis_readback_objects": (i32, [vp, vp, u32]),
         "chordvis_readback_world_transforms": (i32, [vp, vp, vp, u32]),
+        "chordvis_build_ray_scene": (i32, [vp, P(RaySceneInfo)]),
+        "chordvis_refit_ray_scene": (i32, [vp]),
+        "chordvis_trace_rays": (i32, [vp, vp, u32, u32, vp]),
+        "chordvis_ray_scene_info": (i32, [vp, P(RaySceneInfo)]),
         "chordvis_set_view": (i32, [vp, vp, vp, u32]),
         "chordvis_allocate_gbuffer": (i32, [vp, u32, u32, vp]),
         "chordvis_set_shard": (i32, [vp, u32, u32]),

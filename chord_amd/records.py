@@ -106,6 +106,11 @@ BOUNDS_TILES = np.dtype([("tileCounts", np.uint64), ("tileItems", np.uint64), ("
 assert BOUNDS_TILES_DESC.itemsize == 16 and BOUNDS_TILES.itemsize == 32
 BOUNDS_TILES_NEAR, BOUNDS_TILES_FAR = 1, 2
 
+# chordvis_trace_rays (ChordRay / ChordRayHit)
+RAY = np.dtype([("origin", f32, 3), ("tMin", f32), ("direction", f32, 3), ("tMax", f32)])
+RAY_HIT = np.dtype([("t", f32), ("u", f32), ("v", f32), ("object", u32), ("meshlet", u32), ("triangle", u32), ("primitive", u32), ("status", u32)])
+assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32
+
 HZB_MAX_MIPS = 12
 
 

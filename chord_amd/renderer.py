@@ -402,6 +402,46 @@ class VisibilityRenderer:
         self._check(L.lib.chordvis_readback_world_transforms(self._ctx, cur.ctypes.data, prev.ctypes.data, n), "readback_world_transforms")
         return cur, prev
 
+    # -- ray queries on the resident scene (chordvis_build_ray_scene / chordvis_trace_rays) ---------
+    def build_ray_scene(self):
+        """chordvis_build_ray_scene: a BLAS per primitive (kept until the next upload_scene) and the TLAS of the current object list,
+        refitted.  May wait.  Returns an L.RaySceneInfo."""
+        info = L.RaySceneInfo()
+        self._check(L.lib.chordvis_build_ray_scene(self._ctx, C.byref(info)), "build_ray_scene")
+        return info
+
+    def refit_ray_scene(self):
+        """chordvis_refit_ray_scene, one launch that never waits: the TLAS boxes from the object array the frames read now."""
+        self._check(L.lib.chordvis_refit_ray_scene(self._ctx), "refit_ray_scene")
+
+    def ray_scene_info(self):
+        """chordvis_ray_scene_info: counts and the TLAS root's box, read from the device.  Synchronises."""
+        info = L.RaySceneInfo()
+        self._check(L.lib.chordvis_ray_scene_info(self._ctx, C.byref(info)), "ray_scene_info")
+        return info
+
+    def trace_rays(self, rays, any_hit=False, out=None):
+        """chordvis_trace_rays, one launch that never waits.  rays: a contiguous CUDA tensor of records.RAY records (32 bytes each, e.g.
+        float32 (n, 8)) on the context's device, or a numpy array of records.RAY, which is copied there.  Returns an int32 CUDA tensor
+        (n, 8) of records.RAY_HIT words (out: a tensor to write into); .cpu().numpy().view(records.RAY_HIT) reads them.  The call is
+        ordered behind the current torch stream and that one behind the call."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(rays, np.ndarray):
+            host = np.ascontiguousarray(rays, dtype=R.RAY).reshape(-1)
+            with torch.cuda.device(dev):
+                rays = torch.from_numpy(host.view(np.uint8).copy()).to(dev) if len(host) else torch.zeros(0, dtype=torch.uint8, device=dev)
+        nbytes = rays.numel() * rays.element_size()
+        assert rays.is_cuda and rays.is_contiguous() and nbytes % R.RAY.itemsize == 0, "trace_rays: a contiguous CUDA tensor of 32-byte records"
+        count = nbytes // R.RAY.itemsize
+        if out is None:
+            with torch.cuda.device(dev):
+                out = torch.empty((count, 8), dtype=torch.int32, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() == count * R.RAY_HIT.itemsize
+        self._on_my_stream([rays, out], lambda: self._check(L.lib.chordvis_trace_rays(
+            self._ctx, rays.data_ptr() if count else None, count, L.RAY_ANY_HIT if any_hit else 0, out.data_ptr() if count else None), "trace_rays"))
+        return out
+
     def allocate_gbuffer(self, width, height, device_visibility=None):
         self._check(L.lib.chordvis_allocate_gbuffer(self._ctx, width, height, device_visibility), "allocate_gbuffer")
         self.width, self.height = width, height

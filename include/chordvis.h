@@ -227,13 +227,13 @@ int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
  *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain);
  *     chordvis_scatter_world_transforms and chordvis_build_objects (one launch each, of any size: the way to new object records
  *     for a host that must not wait); chordvis_set_object_list while the new list fits what is allocated (it MAY WAIT when a buffer
- *     has to grow: OBJECTS COME AND GO below).
+ *     has to grow: OBJECTS COME AND GO below); chordvis_refit_ray_scene and chordvis_trace_rays (one launch each: RAY QUERIES below).
  *     The kernels a frame launches are chosen from reports the device leaves when a pass finishes; the host may hold a report any
  *     number of frames old, or none: the choice costs or saves time, never a pixel, a list entry or an HZB texel.
  *   MAY WAIT for everything enqueued before it: chordvis_upload_scene, chordvis_upload_material_textures,
  *     chordvis_allocate_gbuffer, chordvis_upload_history_hzb, chordvis_sync, every chordvis_readback_* call (chordvis_readback_objects and
  *     chordvis_readback_world_transforms among them), chordvis_upload_world_transforms (a build in flight keeps its inputs),
- *     chordvis_build_objects_status, chordvis_stats and
+ *     chordvis_build_objects_status, chordvis_build_ray_scene, chordvis_ray_scene_info, chordvis_stats and
  *     chordvis_destroy, which lets the stream run empty before it frees anything: frames in flight finish on memory that is still
  *     theirs.  (Read from the code, not among the tested calls: chordvis_set_shard, chordvis_set_tile_owners and
  *     chordvis_allocate_depth_views re-make buffers and wait likewise.)  chordvis_update_objects waits too when the array is
@@ -269,7 +269,8 @@ int chordvis_sync(ChordCtx* ctx);
  * A context may take scene after scene.  An upload drops what belonged to the scene before: the history HZB (the next frame is a
  * frame without history), the kept tile schedules, the depth views and the cascade cache, the material textures and the geometry
  * feedback, and objects bound with chordvis_bind_objects (the library's copy of the new scene's objects is read again), and the
- * resident world transforms of chordvis_upload_world_transforms (dropped by a refused upload too).  The
+ * resident world transforms of chordvis_upload_world_transforms and the ray scene of chordvis_build_ray_scene (both dropped by a
+ * refused upload too).  The
  * G-buffer, the view, the cull mode, the debug switches and the limits stay.
  * A REFUSED upload (any error code, the refusal of a scene without BVHs under chordvis_set_cull_mode(ctx, 1) included) leaves the
  * context with NO scene: the scene before is gone too, and every call that needs a scene returns CHORDVIS_E_INVALID until an upload
@@ -308,7 +309,8 @@ int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint3
  *     chordvis_render_shadow makes the views again and renders every cascade; the view-by-view depth calls are refused until
  *     chordvis_allocate_depth_views); the sharded lists and the cull exchange buffer
  *     (re-made on demand, as at upload); the resolve state -- chordvis_resolve_*, the feedback calls and everything else that needs a
- *     frame's image are refused until a frame has run.
+ *     frame's image are refused until a frame has run; the TLAS of the ray scene (chordvis_refit_ray_scene and chordvis_trace_rays are
+ *     refused until chordvis_build_ray_scene, which keeps the BLASes and builds none again).
  *   VALIDATE FIRST, COMMIT SECOND.  CHORDVIS_E_INVALID: count == 0 or hostObjects NULL; a primitive or material id out of range; no
  *     scene; a depth-view child context; a call between chordvis_frame_phase_cull and chordvis_frame_phase_a.  CHORDVIS_E_CAPACITY:
  *     2^24 - 2 or more cluster instances, or more than 2^31 - 1 group instances.  A refused call changes NOTHING -- unlike a refused
@@ -378,6 +380,57 @@ int chordvis_build_objects(ChordCtx* ctx, const double cameraPos[3], const doubl
 int chordvis_build_objects_status(ChordCtx* ctx, uint32_t* singularCount, uint32_t* firstSingular);
 int chordvis_readback_objects(ChordCtx* ctx, ChordObject* host, uint32_t count);
 int chordvis_readback_world_transforms(ChordCtx* ctx, double* hostCur, double* hostPrev, uint32_t count);
+
+/* RAY QUERIES.  The reference builds an acceleration structure over the scene it rasters -- one BLAS per primitive over its LOD-0
+ * triangles (asset_gltf.cpp:543-555), TLAS instances collected per frame (component_gltf_mesh.cpp:109-118), all FORCE_OPAQUE
+ * (asset_gltf.cpp:575-577) -- and traces inline ray queries against it (TraceRayInline on topLevelAS: gi_rt_ao.hlsl,
+ * ddgi_probe_trace.hlsl, gi_screen_probe_*.hlsl, gi_specular_trace.hlsl, accelerate_structure_visualize.hlsl, the editor's picking).
+ * This is that for the resident scene: an opt-in ray scene built from what chordvis_upload_scene left on the device, kept current by
+ * one launch and traced by one launch (the MI355X has no ray hardware: kernels_rays.hip walks the trees).  A host that calls none of
+ * these gets the launches and the bytes it got before; no frame state is read or written.
+ *   WHAT A RAY MEETS.  Every object of the current list, through the triangles of its primitive's meshlets with lod == 0 (reached through
+ *     the primitive's groups), solid whatever its material: masked, blended, two-sided or not.  A ChordRay lives in the translated-world
+ *     (camera-relative) space of the object records the frames read now.  The answer is DEFINED by a brute-force specification that
+ *     knows no tree (tests/spec_rays_np.py) and the result is that specification's word for word: binary32, no
+ *     contraction, correctly rounded divide, subnormals kept, min / max as the selects a < b ? a : b and a > b ? a : b.  In short: the
+ *     object's box is the min / max of the eight corners of the primitive's bounds through localToTranslatedWorld (the object stage's
+ *     arithmetic); the ray goes into local space through translatedWorldToLocal; a triangle is tested by Moller-Trumbore against the
+ *     local ray, its t clamped into the slab interval of the triangle's own box and then into that of the object's box, and kept when
+ *     the clamped t lies in [tMin, tMax]; the smallest t wins, ties go to the smallest (object, meshlet, triangle).  A ray with a
+ *     non-finite word, with no finite reciprocal direction component, or with tMin > tMax is a miss; no ray faults.  The triangle test
+ *     is NOT watertight: a ray through an edge or a vertex two triangles share may miss both (a watertight test is a later change).
+ *     Object records must be finite, and so must the positions of the LOD-0 triangles: chordvis_build_ray_scene refuses a scene with a
+ *     non-finite one (CHORDVIS_E_INVALID; a box that is a union with a NaN bounds nothing).
+ *   chordvis_build_ray_scene MAY WAIT (it reads device memory back).  It builds one BLAS per primitive of the uploaded scene, named by
+ *     an object or not (a primitive without LOD-0 triangles gets an empty BLAS and is never hit); BLASes are kept until the next
+ *     chordvis_upload_scene, so a second call builds none (outInfo->blasBuilt == 0).  It builds the TLAS topology for the current
+ *     object list from the object array the frames read now, and ends with a refit: tracing is valid straight after it.  outInfo may
+ *     be NULL.  Trees are 4-wide with at most four triangles (one object) per leaf and at most CHORD_RAY_MAX_DEPTH interior levels each:
+ *     the traversal stack holds 76 entries per ray, 3 x (12 + 12) + 2.  The builder bounds the depth by equal-count splits, so
+ *     CHORDVIS_E_CAPACITY means more items than 4^12 leaves hold (67 M triangles in one primitive, 16 M objects), or 2^28 - 4 or more
+ *     LOD-0 triangles in the scene.  VALIDATE FIRST, COMMIT SECOND: every new buffer is made before an old one is let go; a refused
+ *     call leaves the ray scene it found.
+ *   DROPPED: the whole ray scene by chordvis_upload_scene (refused ones included); the TLAS by chordvis_set_object_list, whether its
+ *     buffers fit or grow.  Until the next chordvis_build_ray_scene the refit and the trace are refused.
+ *   chordvis_refit_ray_scene is ONE launch on the context's stream and never waits: every TLAS leaf box again from the object array the
+ *     frames read now (the bound one after chordvis_bind_objects), every interior box bottom-up.  After chordvis_update_objects,
+ *     chordvis_build_objects or chordvis_bind_objects a trace is refused until a refit has been enqueued.  A bound array the caller
+ *     rewrites itself is the caller's to follow with a refit.
+ *   chordvis_trace_rays is ONE launch and never waits; count == 0 succeeds without one.  deviceRays / deviceHits: caller-owned device
+ *     memory, 16-byte aligned, read and written when the launch runs -- behind the refit and behind whatever wrote the rays on the
+ *     context's stream.  flags: CHORD_RAY_ANY_HIT asks only whether a candidate exists (which triangle is found first is not part of
+ *     the contract).  Valid with or without a view or a G-buffer.
+ *   chordvis_ray_scene_info SYNCHRONISES and fills the counts and the root's box from the device.
+ *   CHORDVIS_E_INVALID, chordvis_last_error naming the rule: no scene; no ray scene, or one dropped since; a depth-view child context;
+ *     count > 0 with a NULL or misaligned pointer; unknown flag bits; a trace before the refit an object change requires; a non-finite
+ *     LOD-0 position at the build.
+ *   Sharded and group contexts: every rank holds the whole scene, so a rank's own context may build and trace.
+ * tests/test_gpu_rays.py holds every statement but one: the refusal on a depth-view child context, which no entry point hands out (read
+ * from the code, like the same refusal of chordvis_set_object_list). */
+int chordvis_build_ray_scene(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
+int chordvis_refit_ray_scene(ChordCtx* ctx);
+int chordvis_trace_rays(ChordCtx* ctx, const ChordRay* deviceRays, uint32_t count, uint32_t flags, ChordRayHit* deviceHits);
+int chordvis_ray_scene_info(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
 
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
  * and the r.instanceculling.* cvars -> switchFlags (instance_culling.cpp:22-68). */

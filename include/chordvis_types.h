@@ -323,8 +323,43 @@ typedef struct ChordBoundsTiles {               /* caller-owned DEVICE memory, N
     uint32_t* totals;      /* [4] */
 } ChordBoundsTiles;
 
+/* chordvis_trace_rays (chordvis.h RAY QUERIES): caller-owned DEVICE records, 16-byte aligned, moved as 16-byte vectors. */
+typedef struct ChordRay {                       /* 32 bytes */
+    float origin[3];    float tMin;             /* translated-world (camera-relative) space of the object records the frames read now */
+    float direction[3]; float tMax;             /* need not be normalised; t is the parameter along it (base.h:439-440: 1e-2 .. 1e9 by default) */
+} ChordRay;
+
+#define CHORD_RAY_HIT        1u    /* ChordRayHit::status bit 0                                                   */
+#define CHORD_RAY_BACK_FACE  2u    /* bit 1: det < 0 in the triangle test (the ray meets the clockwise side)      */
+typedef struct ChordRayHit {                    /* 32 bytes; a miss is eight zero words */
+    float    t, u, v;          /* v0 + u (v1 - v0) + v (v2 - v0) is the point; t along the ray's own direction      */
+    uint32_t object;           /* index in the current object list                                                  */
+    uint32_t meshlet;          /* index into the asset's meshlets (ChordDrawCmd::meshletId's numbering)              */
+    uint32_t triangle;         /* index within the meshlet                                                          */
+    uint32_t primitive;        /* the object's GLTFPrimitiveDetail                                                  */
+    uint32_t status;           /* CHORD_RAY_HIT | CHORD_RAY_BACK_FACE                                               */
+} ChordRayHit;
+
+#define CHORD_RAY_ANY_HIT    1u    /* chordvis_trace_rays flags: only status bit 0 is written, the other seven words are zero */
+#define CHORD_RAY_MAX_DEPTH  12u   /* interior levels of one tree (BLAS or TLAS) the traversal stack is sized for */
+
+typedef struct ChordRaySceneInfo {              /* 64 bytes */
+    uint32_t blasCount;        /* primitives of the uploaded scene (an empty BLAS counts)                           */
+    uint32_t blasNodes;        /* 128-byte nodes of all BLASes                                                       */
+    uint32_t blasTriangles;    /* 48-byte triangle records of all BLASes = the scene's LOD-0 triangles               */
+    uint32_t blasBuilt;        /* BLASes the chordvis_build_ray_scene call that filled this built (0: they were kept) */
+    uint32_t blasMaxDepth;     /* interior levels of the deepest BLAS                                                */
+    uint32_t tlasNodes;
+    uint32_t tlasDepth;
+    uint32_t pad;
+    uint64_t deviceBytes;      /* of the whole ray scene                                                             */
+    float    rootMin[3];       /* the TLAS root's box after the latest refit the device has finished                 */
+    float    rootMax[3];
+} ChordRaySceneInfo;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(ChordRay) == 32 && sizeof(ChordRayHit) == 32 && sizeof(ChordRaySceneInfo) == 64, "ray records");
 static_assert(sizeof(ChordBoundsTilesDesc) == 16, "ChordBoundsTilesDesc");
 static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
 static_assert(sizeof(ChordBoundsResult) == 16, "ChordBoundsResult");

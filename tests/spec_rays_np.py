@@ -1,0 +1,251 @@
+"""The specification of chordvis_trace_rays in numpy: brute force over every (ray, object, LOD-0 triangle), no tree anywhere.
+
+Arithmetic: binary32 throughout, round to nearest, one rounding per operation (numpy float32 arrays never contract), `/` correctly
+rounded, subnormals kept, sums and products left to right.  min and max are the selects rmin(a, b) = a if a < b else b and
+rmax(a, b) = a if a > b else b -- NOT np.minimum / np.maximum -- so that a NaN takes the same way here and in the kernel.
+
+    slab interval of a ray (o, d) and a box [lo, hi], per axis: r = 1 / d; r not finite (d is +-0 or subnormal): (-inf, +inf) when
+        lo <= o <= hi, else empty; otherwise a = (lo - o) * r, b = (hi - o) * r and the axis interval is [rmin(a, b), rmax(a, b)].
+        near = rmax(rmax(n0, n1), n2), far = rmin(rmin(f0, f1), f2); empty when near > far.
+    object box: c = (posMin + posMax) * 0.5, e = posMax - c, the eight corners c +- e (extent_corner) through localToTranslatedWorld
+        as ((m00 x + m01 y) + m02 z) + m03 (mul_mv with w = 1: the object stage of kernels_cull.hip), componentwise rmin / rmax.
+    local ray: o_l = ((w00 ox + w01 oy) + w02 oz) + w03 per row of translatedWorldToLocal, d_l = (w00 dx + w01 dy) + w02 dz.
+    triangle: e1 = v1 - v0, e2 = v2 - v0, p = cross(d_l, e2), det = dot(e1, p); miss when det == 0 or not finite; inv = 1 / det,
+        s = o_l - v0, u = dot(s, p) * inv in [0, 1], q = cross(s, e1), v = dot(d_l, q) * inv >= 0, u + v <= 1, tMT = dot(e2, q) * inv.
+    candidate: object interval [nO, fO] non-empty, triangle-box interval [nT, fT] (local ray, box = rmin / rmax of the three
+        vertices) non-empty, the triangle test passes, and t = rmin(rmax(rmin(rmax(tMT, nT), fT), nO), fO) lies in [tMin, tMax].
+    result: the candidate of smallest t, ties to the smallest (object, meshlet, triangle); any-hit: whether one exists.
+    a ray with a non-finite word, with three non-finite reciprocals, or with tMin > tMax is a miss (eight zero words).
+"""
+import numpy as np
+
+from chord_amd import records as R
+
+F = np.float32
+INF = F(np.inf)
+
+
+def rmin(a, b):
+    return np.where(a < b, a, b)
+
+
+def rmax(a, b):
+    return np.where(a > b, a, b)
+
+
+def slab(o, d, lo, hi):
+    """(near, far) of rays (o, d) against boxes [lo, hi]; the last axis of every argument is xyz, the others broadcast."""
+    o, d, lo, hi = (np.asarray(x, dtype=F) for x in (o, d, lo, hi))
+    with np.errstate(all="ignore"):
+        r = F(1.0) / d
+        fin = np.isfinite(r)
+        a, b = (lo - o) * r, (hi - o) * r
+        inside = (lo <= o) & (o <= hi)
+        n = np.where(fin, rmin(a, b), np.where(inside, -INF, INF)).astype(F)
+        f = np.where(fin, rmax(a, b), np.where(inside, INF, -INF)).astype(F)
+        near = rmax(rmax(n[..., 0], n[..., 1]), n[..., 2])
+        far = rmin(rmin(f[..., 0], f[..., 1]), f[..., 2])
+    return near, far
+
+
+# kExtentApplyFactor (device_math.h extent_corner)
+_CORNER_SIGNS = np.array([[(-1.0 if k in (1, 4, 6, 7) else 1.0), (-1.0 if k in (1, 3, 5, 6) else 1.0), (-1.0 if k in (1, 2, 5, 7) else 1.0)]
+                          for k in range(8)], dtype=F)
+
+
+def object_boxes(objects, primitives):
+    """(lo, hi) float32 (n, 3): the boxes of records.OBJECT records over records.PRIMITIVE bounds."""
+    prim = primitives[objects["GLTFPrimitiveDetail"]]
+    mn, mx = prim["posMin"].astype(F), prim["posMax"].astype(F)
+    with np.errstate(all="ignore"):
+        c = (mn + mx) * F(0.5)
+        e = mx - c
+        m = objects["localToTranslatedWorld"].astype(F).reshape(-1, 4, 4)      # [n][col][row]
+        lo = hi = None
+        for k in range(8):
+            q = c + e * _CORNER_SIGNS[k]
+            p = np.stack([((m[:, 0, r] * q[:, 0] + m[:, 1, r] * q[:, 1]) + m[:, 2, r] * q[:, 2]) + m[:, 3, r] * F(1.0) for r in range(3)], axis=1)
+            lo = p if lo is None else rmin(lo, p)
+            hi = p if hi is None else rmax(hi, p)
+    return lo.astype(F), hi.astype(F)
+
+
+def lod0_triangles(scene):
+    """Per primitive: (vertices float32 (T, 3, 3), meshlet uint32 (T,), triangle uint32 (T,)) of the triangles of its meshlets with
+    lod == 0 reached through its groups, in ascending (meshlet, triangle) order.  meshlet: index into the asset's meshlets -- a
+    records.Scene is ONE asset, so that is the index into scene.meshlets (the library subtracts the asset's first meshlet; a scene of
+    several assets would have to do the same here)."""
+    out = []
+    for p in scene.primitives:
+        ids = set()
+        for g in scene.groups[p["meshletGroupOffset"]: p["meshletGroupOffset"] + p["meshletGroupCount"]]:
+            for i in range(int(g["meshletCount"])):
+                ids.add(int(p["meshletOffset"]) + int(scene.group_indices[int(p["meshletGroupIndicesOffset"]) + int(g["meshletOffset"]) + i]))
+        verts, mids, tids = [], [], []
+        for m in sorted(ids):
+            ml = scene.meshlets[m]
+            if int(ml["lod"]) != 0:
+                continue
+            V, T = int(ml["vertexTriangleCount"]) & 0xFF, (int(ml["vertexTriangleCount"]) >> 8) & 0xFF
+            off = int(ml["dataOffset"])
+            vid = scene.meshlet_data[off: off + V].astype(np.int64) + int(p["vertexOffset"])
+            words = scene.meshlet_data[off + V: off + V + T]
+            local = np.stack([words & 0xFF, (words >> 8) & 0xFF, (words >> 16) & 0xFF], axis=1).astype(np.int64)
+            if T:
+                verts.append(scene.positions[vid[local]])
+                mids.append(np.full(T, m, dtype=np.uint32))
+                tids.append(np.arange(T, dtype=np.uint32))
+        if verts:
+            out.append((np.concatenate(verts).astype(F), np.concatenate(mids), np.concatenate(tids)))
+        else:
+            out.append((np.zeros((0, 3, 3), dtype=F), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32)))
+    return out
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def live_rays(rays):
+    words = np.concatenate([rays["origin"], rays["tMin"][:, None], rays["direction"], rays["tMax"][:, None]], axis=1).astype(F)
+    with np.errstate(all="ignore"):
+        recip_ok = np.isfinite(F(1.0) / rays["direction"].astype(F)).any(axis=1)
+    return np.isfinite(words).all(axis=1) & recip_ok & ~(rays["tMin"] > rays["tMax"])
+
+
+def pair_candidates(o, d, v0, v1, v2, nO, fO, tMin, tMax):
+    """The candidate test, elementwise over broadcastable leading axes: o, d local rays (..., 3); v0, v1, v2 (..., 3); the rest (...).
+    Returns (candidate mask, t, u, v, det)."""
+    with np.errstate(all="ignore"):
+        shape = np.broadcast_shapes(o.shape, v0.shape)
+        o, d, v0, v1, v2 = (np.broadcast_to(x, shape) for x in (o, d, v0, v1, v2))
+        blo, bhi = rmin(rmin(v0, v1), v2), rmax(rmax(v0, v1), v2)
+        nT, fT = slab(o, d, blo, bhi)
+        e1, e2 = v1 - v0, v2 - v0
+        p = _cross(d, e2)
+        det = _dot(e1, p)
+        ok = ~(nT > fT) & (det != 0) & np.isfinite(det)
+        inv = F(1.0) / det
+        s = o - v0
+        u = _dot(s, p) * inv
+        ok &= (F(0.0) <= u) & (u <= F(1.0))
+        q = _cross(s, e1)
+        v = _dot(d, q) * inv
+        ok &= (v >= F(0.0)) & (u + v <= F(1.0))
+        tMT = _dot(e2, q) * inv
+        t = rmin(rmax(rmin(rmax(tMT, nT), fT), nO), fO).astype(F)
+        ok &= (t >= tMin) & (t <= tMax)
+    return ok, t, u.astype(F), v.astype(F), det
+
+
+def _object_best(ol, dl, verts, mids, nO, fO, tMin, tMax, meshlet_cull, pair_budget):
+    """Per ray of one object: (has, t, u, v, det, triangle index into verts) of its best candidate -- smallest t, ties to the
+    smallest index (verts are in ascending (meshlet, triangle) order)."""
+    r, T = len(ol), len(verts)
+    has = np.zeros(r, dtype=bool)
+    bt, bu, bv, bd = (np.zeros(r, dtype=F) for _ in range(4))
+    bk = np.zeros(r, dtype=np.int64)
+    if not meshlet_cull:
+        step = max(1, pair_budget // T)
+        for b in range(0, r, step):
+            e = min(r, b + step)
+            ok, t, u, v, det = pair_candidates(ol[b:e, None, :], dl[b:e, None, :], verts[None, :, 0], verts[None, :, 1], verts[None, :, 2],
+                                               nO[b:e, None], fO[b:e, None], tMin[b:e, None], tMax[b:e, None])
+            tm = np.where(ok, t, INF)
+            k = tm.argmin(axis=1)                        # (the first of equal minima: the smallest (meshlet, triangle))
+            rows = np.arange(e - b)
+            has[b:e] = ok[rows, k]
+            bt[b:e], bu[b:e], bv[b:e], bd[b:e], bk[b:e] = t[rows, k], u[rows, k], v[rows, k], det[rows, k], k
+        return has, bt, bu, bv, bd, bk
+    # The same answer with fewer pairs formed: a triangle whose meshlet's box -- the exact rmin / rmax union of the meshlet's triangle
+    # boxes -- has an empty interval has an empty interval itself (the monotonicity of the slab interval, tests/test_rays_spec.py),
+    # so it is no candidate.  tests/test_rays_spec.py also holds this path to the plain one above.
+    starts = np.concatenate([[0], np.nonzero(np.diff(mids))[0] + 1, [T]])
+    mlo = np.stack([rmin(rmin(verts[a:b, 0], verts[a:b, 1]), verts[a:b, 2]).min(axis=0) for a, b in zip(starts[:-1], starts[1:])])
+    mhi = np.stack([rmax(rmax(verts[a:b, 0], verts[a:b, 1]), verts[a:b, 2]).max(axis=0) for a, b in zip(starts[:-1], starts[1:])])
+    nM, fM = slab(ol[:, None, :], dl[:, None, :], mlo[None], mhi[None])
+    ri, mi = np.nonzero(~(nM > fM))
+    if len(ri) == 0:
+        return has, bt, bu, bv, bd, bk
+    cnt = (starts[1:] - starts[:-1])[mi]
+    pr = np.repeat(ri, cnt)
+    pk = np.repeat(starts[:-1][mi], cnt) + (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    ok, t, u, v, det = pair_candidates(ol[pr], dl[pr], verts[pk, 0], verts[pk, 1], verts[pk, 2], nO[pr], fO[pr], tMin[pr], tMax[pr])
+    pr, pk, t, u, v, det = pr[ok], pk[ok], t[ok], u[ok], v[ok], det[ok]
+    order = np.lexsort((pk, t, pr))                      # by ray, then t, then index
+    pr, pk, t, u, v, det = pr[order], pk[order], t[order], u[order], v[order], det[order]
+    first = np.concatenate([[True], pr[1:] != pr[:-1]]) if len(pr) else np.zeros(0, dtype=bool)
+    g = pr[first]
+    has[g] = True
+    bt[g], bu[g], bv[g], bd[g], bk[g] = t[first], u[first], v[first], det[first], pk[first]
+    return has, bt, bu, bv, bd, bk
+
+
+def trace(scene, objects, rays, any_hit=False, triangles=None, meshlet_cull=False, pair_budget=1 << 21):
+    """records.RAY_HIT for records.RAY rays against `objects` (records.OBJECT: the current list's records) over scene's geometry.
+    triangles: lod0_triangles(scene), when the caller has it.  meshlet_cull: the quicker evaluation of the same definition."""
+    rays = np.ascontiguousarray(rays, dtype=R.RAY).reshape(-1)
+    objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
+    tris = lod0_triangles(scene) if triangles is None else triangles
+    n = len(rays)
+    hits = np.zeros(n, dtype=R.RAY_HIT)
+    if n == 0:
+        return hits
+    live = live_rays(rays)
+    o, d = rays["origin"].astype(F), rays["direction"].astype(F)
+    tMin, tMax = rays["tMin"].astype(F), rays["tMax"].astype(F)
+    lo, hi = object_boxes(objects, scene.primitives)
+    best_t = np.full(n, np.inf, dtype=F)
+    found = np.zeros(n, dtype=bool)
+    for i in range(len(objects)):
+        prim = int(objects["GLTFPrimitiveDetail"][i])
+        verts, mids, tids = tris[prim]
+        if len(verts) == 0:
+            continue
+        nO, fO = slab(o, d, lo[i], hi[i])
+        sel = np.nonzero(live & ~(nO > fO))[0]
+        if len(sel) == 0:
+            continue
+        w = objects["translatedWorldToLocal"][i].astype(F).reshape(4, 4)        # [col][row]
+        with np.errstate(all="ignore"):
+            ol = np.stack([((w[0, r] * o[sel, 0] + w[1, r] * o[sel, 1]) + w[2, r] * o[sel, 2]) + w[3, r] * F(1.0) for r in range(3)], axis=1)
+            dl = np.stack([(w[0, r] * d[sel, 0] + w[1, r] * d[sel, 1]) + w[2, r] * d[sel, 2] for r in range(3)], axis=1)
+        has, t, u, v, det, k = _object_best(ol, dl, verts, mids, nO[sel], fO[sel], tMin[sel], tMax[sel], meshlet_cull, pair_budget)
+        better = has & (~found[sel] | (t < best_t[sel]))     # (strict: an equal t of a later object loses)
+        g, kk = sel[better], k[better]
+        found[g] = True
+        best_t[g] = t[better]
+        hits["t"][g], hits["u"][g], hits["v"][g] = t[better], u[better], v[better]
+        hits["object"][g], hits["meshlet"][g], hits["triangle"][g], hits["primitive"][g] = i, mids[kk], tids[kk], prim
+        hits["status"][g] = 1 | np.where(det[better] < 0, 2, 0)
+    if any_hit:
+        out = np.zeros(n, dtype=R.RAY_HIT)
+        out["status"] = found.astype(np.uint32)
+        return out
+    return hits
+
+
+def make_rays(origins, directions, t_min=1e-2, t_max=1e9):
+    origins = np.asarray(origins, dtype=F).reshape(-1, 3)
+    rays = np.zeros(len(origins), dtype=R.RAY)
+    rays["origin"], rays["direction"] = origins, np.broadcast_to(np.asarray(directions, dtype=F), origins.shape)
+    rays["tMin"], rays["tMax"] = t_min, t_max
+    return rays
+
+
+def pixel_rays(view, width, height, t_min=1e-2, t_max=1e9):
+    """One ray per pixel centre of a records.CAMERA_VIEW, formed in binary64: from the camera (the translated-world origin) through
+    the point the inverse of translatedWorldToClip gives for the pixel centre at reverse-Z depth 0.5.  Row-major pixel order."""
+    m = view["translatedWorldToClip"][0].astype(np.float64).reshape(4, 4).T        # row-major clip = m @ world
+    inv = np.linalg.inv(m)
+    ys, xs = np.mgrid[0:height, 0:width]
+    ndc = np.stack([(xs + 0.5) / width * 2.0 - 1.0, 1.0 - (ys + 0.5) / height * 2.0, np.full(xs.shape, 0.5), np.ones(xs.shape)], axis=-1).reshape(-1, 4)
+    p = ndc @ inv.T
+    p = p[:, :3] / p[:, 3:4]
+    d = p / np.linalg.norm(p, axis=1, keepdims=True)
+    return make_rays(np.zeros_like(d), d, t_min, t_max)
