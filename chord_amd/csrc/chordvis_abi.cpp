@@ -760,7 +760,7 @@ int chordvis_destroy(ChordCtx* c)
         c->dMatRecords = nullptr; c->dMatTexels = nullptr; c->dMatBlocks = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
-    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod);
+    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod); dfree(c->dPrimVertexBase);
     dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dBoundsTilesScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     drop_world_transforms(c);
@@ -888,6 +888,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
     c->hPrims.assign(s->primitiveCount, DPrim{});
     std::vector<uint32_t> primMeshlets(s->primitiveCount, 0);
     std::vector<uint64_t> primTriangles(s->primitiveCount, 0);
+    std::vector<uint32_t> primVertexBase(s->primitiveCount, 0);   // asset vertex base + primitive.vertexOffset (chordvis_shade_ray_hits)
     for (uint32_t pi = 0; pi < s->primitiveCount; pi++) {
         const ChordPrimitive& p = s->primitives[pi];
         if (p.primitiveDatasBufferId >= s->assetCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: primitiveDatasBufferId out of range");
@@ -901,6 +902,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
         d.groupIndicesBase = iB[a] + p.meshletGroupIndicesOffset;
         d.groupCount = p.meshletGroupCount;
         d.assetMeshletBase = mB[a];
+        primVertexBase[pi] = vB[a] + p.vertexOffset;
         d.bvhBase = 0xFFFFFFFFu;
         if (as.bvhNodes && as.bvhNodeCount && p.bvhNodeOffset < as.bvhNodeCount) {
             // GPUBVHNode tree of the primitive (gltf.h:16-24): copied, and checked for what the hierarchical cull relies on --
@@ -1150,7 +1152,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
     if (!vec.empty()) CHORD_HIP(c, hipMemcpy(dst, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice));
     UP(c->dMeshlets, meshlets) UP(c->dGroups, groups) UP(c->dGroupIndices, gidx) UP(c->dMeshletData, mdata)
     UP(c->dPositions, pos) UP(c->dPrims, c->hPrims) UP(c->dObjStatic, c->hObjStatic) UP(c->dGroupRefs, refs)
-    UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod)
+    UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod) UP(c->dPrimVertexBase, primVertexBase)
     if (!bvh.empty()) { UP(c->dBvhNodes, bvh) } else dfree(c->dBvhNodes);
     c->bvhComplete = bvhComplete;
     if (alphaTexels) {
@@ -1314,6 +1316,7 @@ int chordvis_upload_material_textures(ChordCtx* c, const ChordSceneDesc* s)
         d.roughnessFactor = mat.roughnessFactor; d.metallicFactor = mat.metallicFactor; d.normalFactorScale = mat.normalFactorScale;
         d.occlusionTextureStrength = mat.occlusionTextureStrength; d.bExistOcclusion = mat.bExistOcclusion != 0u;
         d.pbr = mat.materialType == 1u;                                    // kLightingType_GLTF_MetallicRoughnessPBR, base.h:423
+        d.twoSided = mat.bTwoSided != 0u;
         slot_ids(mat, tex, smp);
         for (int k = 0; k < 4; k++) {
             chord::DMatSlot& S = d.slot[k];
@@ -1957,6 +1960,25 @@ int chordvis_trace_rays(ChordCtx* c, const ChordRay* deviceRays, uint32_t count,
         return fail(c, CHORDVIS_E_INVALID, "trace_rays: deviceRays and deviceHits must be non-NULL and 16-byte aligned when count > 0");
     (void)hipSetDevice(c->device);
     chord::launch_ray_trace(c, deviceRays, count, (flags & CHORD_RAY_ANY_HIT) != 0u, deviceHits);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
+// Everything is checked before the device is touched; no device pointer is dereferenced here.  Needs no ray scene: the hits may be a host's.
+int chordvis_shade_ray_hits(ChordCtx* c, const ChordRayHit* deviceHits, uint32_t count, float lod, const float* deviceLods, ChordRayHitSurface* deviceSurfaces)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    { const int rc = ray_checks(c, "shade_ray_hits", false); if (rc) return rc; }
+    if (c->cullPhaseDone) return fail(c, CHORDVIS_E_INVALID, "shade_ray_hits: not between chordvis_frame_phase_cull and chordvis_frame_phase_a");
+    if (!c->matTexturesLoaded || !c->dMatRecords)
+        return fail(c, CHORDVIS_E_INVALID, "shade_ray_hits: no material textures since the last chordvis_upload_scene (call chordvis_upload_material_textures first)");
+    if (count == 0) return CHORDVIS_OK;
+    if (!deviceHits || !deviceSurfaces || ((uintptr_t)deviceHits & 15u) || ((uintptr_t)deviceSurfaces & 15u))
+        return fail(c, CHORDVIS_E_INVALID, "shade_ray_hits: deviceHits and deviceSurfaces must be non-NULL and 16-byte aligned when count > 0");
+    if ((uintptr_t)deviceLods & 3u)
+        return fail(c, CHORDVIS_E_INVALID, "shade_ray_hits: deviceLods must be NULL (one lod for every hit) or 4-byte aligned");
+    (void)hipSetDevice(c->device);
+    chord::launch_ray_shade(c, deviceHits, count, lod, deviceLods, deviceSurfaces);
     CHORD_HIP(c, hipGetLastError());
     return CHORDVIS_OK;
 }

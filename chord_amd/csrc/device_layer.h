@@ -145,7 +145,8 @@ struct DMatRecord {            // 64 + 4 x 392 B
     float    occlusionTextureStrength;
     uint32_t bExistOcclusion;
     uint32_t pbr;              // materialType == kLightingType_GLTF_MetallicRoughnessPBR
-    uint32_t pad[3];
+    uint32_t twoSided;         // bTwoSided != 0 (a former pad word; the shading of ray hits alone reads it: ray_shade.h)
+    uint32_t pad[2];
     DMatSlot slot[4];
 };
 static_assert(sizeof(DMatSlot) == 392 && sizeof(DMatRecord) == 64 + 4 * 392, "DMatRecord");
@@ -445,6 +446,7 @@ struct ChordCtx {
     float* dNormals = nullptr;                // float3 per vertex (normalBuffer), or null: no asset has normals (chordvis_resolve_surface only)
     float* dTangents = nullptr;               // float4 per vertex (tangentBuffer), or null: no asset has tangents (likewise)
     uint8_t* dMeshletLod = nullptr;           // per device meshlet: ChordMeshlet::lod (DMeshlet carries vertexBase instead; the resolve's debug view reads it)
+    uint32_t* dPrimVertexBase = nullptr;      // per primitive: asset vertex base + primitive.vertexOffset (the shading of ray hits: ray_shade.h); a depth-view child has none
     bool anyMasked = false;
     // chordvis_upload_material_textures (read by chordvis_resolve_material alone; dropped by the next chordvis_upload_scene)
     chord::DMatRecord* dMatRecords = nullptr; // per material
@@ -796,6 +798,9 @@ void launch_group_refs_build(ChordCtx* c);
 // each on the context's stream.
 void launch_ray_refit(ChordCtx* c);
 void launch_ray_trace(ChordCtx* c, const ChordRay* rays, uint32_t count, bool anyHit, ChordRayHit* hits);
+// kernels_rayshade.hip: chordvis_shade_ray_hits' launch (arguments checked by the entry point; count > 0).  One launch on the context's
+// stream, of the kernel for the texel store or -- some chain kept as blocks -- the one that reads both stores.
+void launch_ray_shade(ChordCtx* c, const ChordRayHit* hits, uint32_t count, float lod, const float* lods, ChordRayHitSurface* surfaces);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -158,6 +158,7 @@ class RaySceneInfo(C.Structure):
 RAY_ANY_HIT = 1                                    # chordvis_trace_rays flags
 RAY_HIT, RAY_BACK_FACE = 1, 2                      # ChordRayHit::status bits
 RAY_MAX_DEPTH = 12
+RAYSURF_VALID, RAYSURF_BACK_FACE, RAYSURF_TWO_SIDED, RAYSURF_PBR = 1, 2, 4, 8      # ChordRayHitSurface::flags (chordvis_shade_ray_hits)
 
 
 class CameraDesc(C.Structure):
@@ -254,6 +255,8 @@ def _load():
         "chordvis_refit_ray_scene": (i32, [vp]),
         "chordvis_trace_rays": (i32, [vp, vp, u32, u32, vp]),
         "chordvis_ray_scene_info": (i32, [vp, P(RaySceneInfo)]),
+        # (ctx, deviceHits, count, lod, deviceLods, deviceSurfaces): the float travels as a float, every pointer as a void pointer
+        "chordvis_shade_ray_hits": (i32, [vp, vp, u32, C.c_float, vp, vp]),
         "chordvis_set_view": (i32, [vp, vp, vp, u32]),
         "chordvis_allocate_gbuffer": (i32, [vp, u32, u32, vp]),
         "chordvis_set_shard": (i32, [vp, u32, u32]),

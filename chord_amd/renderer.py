@@ -442,6 +442,44 @@ class VisibilityRenderer:
             self._ctx, rays.data_ptr() if count else None, count, L.RAY_ANY_HIT if any_hit else 0, out.data_ptr() if count else None), "trace_rays"))
         return out
 
+    def shade_ray_hits(self, hits, lod=0.0, lods=None, out=None):
+        """chordvis_shade_ray_hits, one launch that never waits: material, normal and uv at every hit.  hits: a contiguous CUDA tensor
+        of records.RAY_HIT records (32 bytes each, e.g. what trace_rays returns) on the context's device, or a numpy array of
+        records.RAY_HIT, which is copied there.  lod: the texture level of every hit; lods: a level per hit instead, a float32 CUDA
+        tensor or a numpy array of n values.  Needs upload_material_textures and no ray scene.  Returns an int32 CUDA tensor (n, 16)
+        of records.RAY_HIT_SURFACE words (out: a tensor to write into); .cpu().numpy().view(records.RAY_HIT_SURFACE) reads them.
+
+        Ordering and lifetime: the context's stream waits for the current torch stream before the call and the current torch stream
+        waits for the context's stream after it, so every later use of hits, lods and the result on the current stream -- the
+        allocator's reuse of their memory after a free included, which is ordered on that stream -- is behind the kernel.  No tensor
+        is recorded on the context's stream.  A caller who frees or reuses these tensors on a third stream orders that stream itself."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(hits, np.ndarray):
+            host = np.ascontiguousarray(hits, dtype=R.RAY_HIT).reshape(-1)
+            with torch.cuda.device(dev):
+                hits = torch.from_numpy(host.view(np.uint8).copy()).to(dev) if len(host) else torch.zeros(0, dtype=torch.uint8, device=dev)
+        nbytes = hits.numel() * hits.element_size()
+        assert hits.is_cuda and hits.is_contiguous() and nbytes % R.RAY_HIT.itemsize == 0, "shade_ray_hits: a contiguous CUDA tensor of 32-byte records"
+        assert hits.device.index == self.device, "shade_ray_hits: hits is on cuda:%s, the context on cuda:%d" % (hits.device.index, self.device)
+        count = nbytes // R.RAY_HIT.itemsize
+        if lods is not None:
+            if isinstance(lods, np.ndarray):
+                host = np.ascontiguousarray(lods, dtype=np.float32).reshape(-1)
+                with torch.cuda.device(dev):
+                    lods = torch.from_numpy(host.copy()).to(dev) if len(host) else torch.zeros(0, dtype=torch.float32, device=dev)
+            assert lods.is_cuda and lods.is_contiguous() and lods.dtype == torch.float32 and lods.numel() == count, "shade_ray_hits: lods is n float32 values"
+            assert lods.device.index == self.device, "shade_ray_hits: lods is on cuda:%s, the context on cuda:%d" % (lods.device.index, self.device)
+        if out is None:
+            with torch.cuda.device(dev):
+                out = torch.empty((count, 16), dtype=torch.int32, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() == count * R.RAY_HIT_SURFACE.itemsize
+        assert out.device.index == self.device, "shade_ray_hits: out is on cuda:%s, the context on cuda:%d" % (out.device.index, self.device)
+        self._on_my_stream([], lambda: self._check(L.lib.chordvis_shade_ray_hits(
+            self._ctx, hits.data_ptr() if count else None, count, float(lod), lods.data_ptr() if (lods is not None and count) else None,
+            out.data_ptr() if count else None), "shade_ray_hits"))
+        return out
+
     def allocate_gbuffer(self, width, height, device_visibility=None):
         self._check(L.lib.chordvis_allocate_gbuffer(self._ctx, width, height, device_visibility), "allocate_gbuffer")
         self.width, self.height = width, height

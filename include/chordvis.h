@@ -432,6 +432,49 @@ int chordvis_refit_ray_scene(ChordCtx* ctx);
 int chordvis_trace_rays(ChordCtx* ctx, const ChordRay* deviceRays, uint32_t count, uint32_t flags, ChordRayHit* deviceHits);
 int chordvis_ray_scene_info(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
 
+/* SHADING A HIT (RayHitMaterialInfo::init, raytrace_shared.hlsli: what ddgi_probe_trace.hlsl, gi_screen_probe_*.hlsl and
+ * gi_specular_trace.hlsl do with a hit).  chordvis_shade_ray_hits writes one ChordRayHitSurface per ChordRayHit --
+ * material, normal and uv at the hit point -- in ONE launch on the context's stream that never waits; count == 0 succeeds without
+ * one.  deviceHits / deviceSurfaces: caller-owned device memory, 16-byte aligned; deviceLods: NULL (`lod` for every hit) or count
+ * floats, 4-byte aligned; all read and written when the launch runs.  It needs chordvis_upload_scene and
+ * chordvis_upload_material_textures and NO ray scene: the hits may be chordvis_trace_rays' or a host's own.  It reads the object array
+ * the frames read now (the bound one after chordvis_bind_objects): a host that changes the objects between trace and shade gets the
+ * new matrices and the new materials, and no refit is involved; after chordvis_set_object_list the valid object indices are the new
+ * list's.  Valid with or without a view or a G-buffer; frames are untouched.
+ *   The answer is DEFINED by tests/spec_ray_shade_np.py (shade) and is that specification's word for word: binary32, one rounding
+ *   per operation, no contraction, correctly rounded divide and square root.  Per hit:
+ *     valid     status bit 0 set; u and v finite; object < the object count; meshlet < the scene's meshlet count; the object's
+ *               GLTFPrimitiveDetail and GLTFMaterialData below their counts; triangle < the meshlet's triangle count; the triangle
+ *               word, the three vertex-id words and the three vertex ids inside their arrays.  An INVALID hit gives sixteen zero words;
+ *               no hit faults.  The vertex ids are offset by the vertexOffset of the OBJECT's primitive, also where a host's own hit
+ *               pairs the object with a meshlet of another primitive.
+ *     b         ((1 - u) - v, u, v)
+ *     uv        (uv0 * b.x + uv1 * b.y) + uv2 * b.z per component; (0, 0) for a scene uploaded without texture coordinates, and the
+ *               material fields are then sampled at (0, 0)
+ *     normal    per vertex normalize(mul(float4(nLS, 0), translatedWorldToLocal).xyz) -- chordvis_resolve_surface's vertex normal --
+ *               interpolated like uv and THEN normalised (raytrace_shared.hlsli:92); normalize gives 0 where the squared length is not
+ *               above 0; negated when the material is two-sided and the hit a back face; zero for a scene uploaded without normals
+ *     level     lodq = (int32) floor(min(max(lod, 0), 15) * 256), a NaN lod counting as 0, from deviceLods[i] or `lod`; from lodq the
+ *               level rule of chordvis_resolve_material's sampler unchanged: minified iff lodq > 0; *_MIPMAP_NEAREST takes level
+ *               min((lodq + 128) >> 8, last); *_MIPMAP_LINEAR blends levels l0 = min(lodq >> 8, last) and min(l0 + 1, last) by
+ *               (lodq & 255) / 256; otherwise level 0; the min / mag filter inside a level.  Levels count from the first level STORED
+ *               (chordvis_set_texture_first_level).  There are no gradients, so chordvis_set_material_anisotropy has no effect.
+ *     fields    baseColor = sample * baseColorFactor, rgb through sRGB -> AP1, white without a texture; emissive = sample.rgb *
+ *               emissiveFactor, zero without one, NOT through sRGB -> AP1 (chordvis_resolve_material's row; a departure from the
+ *               reference's hit shading); roughness, metallic = .g, .b of the metallic-roughness texture, or roughnessFactor and
+ *               (metallicFactor >= 1 ? 0 : metallicFactor); the normal texture is not read.  A material of another materialType than 1
+ *               leaves these fields zero and CHORD_RAYSURF_PBR clear; material, normal, uv and the other flags are filled all the same.
+ *   Both texture stores (chordvis_set_material_texture_store) give the same words.
+ *   CHORDVIS_E_INVALID, chordvis_last_error naming the remedy, and nothing is changed or launched: a NULL context (no message); a
+ *   depth-view child context; no scene; no chordvis_upload_material_textures since the last chordvis_upload_scene; between
+ *   chordvis_frame_phase_cull and chordvis_frame_phase_a; count > 0 with deviceHits or deviceSurfaces NULL or not 16-byte aligned; a
+ *   deviceLods that is not 4-byte aligned.
+ * tests/test_ray_shade_host.py runs the per-hit code on the host under the address and undefined-behaviour sanitizers;
+ * tests/test_gpu_ray_shade.py holds the statements above on the GPU, but the refusal on a depth-view child context, which no entry
+ * point hands out (read from the code). */
+int chordvis_shade_ray_hits(ChordCtx* ctx, const ChordRayHit* deviceHits, uint32_t count, float lod, const float* deviceLods,
+                            ChordRayHitSurface* deviceSurfaces);
+
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
  * and the r.instanceculling.* cvars -> switchFlags (instance_culling.cpp:22-68). */
 int chordvis_set_view(ChordCtx* ctx, const ChordCameraView* view, const ChordInstanceCullingView* instanceView,

@@ -343,6 +343,22 @@ typedef struct ChordRayHit {                    /* 32 bytes; a miss is eight zer
 #define CHORD_RAY_ANY_HIT    1u    /* chordvis_trace_rays flags: only status bit 0 is written, the other seven words are zero */
 #define CHORD_RAY_MAX_DEPTH  12u   /* interior levels of one tree (BLAS or TLAS) the traversal stack is sized for */
 
+/* chordvis_shade_ray_hits (chordvis.h RAY QUERIES, "shading a hit"): one record per ChordRayHit. */
+#define CHORD_RAYSURF_VALID      1u   /* ChordRayHitSurface::flags bit 0: the record is filled (an invalid hit: sixteen zero words)  */
+#define CHORD_RAYSURF_BACK_FACE  2u   /* copied from the hit's CHORD_RAY_BACK_FACE                                                */
+#define CHORD_RAYSURF_TWO_SIDED  4u   /* the material's bTwoSided                                                                 */
+#define CHORD_RAYSURF_PBR        8u   /* materialType == 1: the material fields are filled                                        */
+typedef struct ChordRayHitSurface {             /* 64 bytes, 16-byte aligned, moved as four 16-byte vectors; an invalid hit is sixteen zero words */
+    float    baseColor[4];     /* rgb through sRGB -> AP1, alpha                                                     */
+    float    emissive[3];      /* NOT through sRGB -> AP1                                                            */
+    float    roughness;
+    float    normal[3];        /* translated-world space, unit length or zero; flipped on a back face of a two-sided material */
+    float    metallic;
+    float    uv[2];
+    uint32_t material;         /* the object's GLTFMaterialData                                                      */
+    uint32_t flags;            /* CHORD_RAYSURF_*                                                                    */
+} ChordRayHitSurface;
+
 typedef struct ChordRaySceneInfo {              /* 64 bytes */
     uint32_t blasCount;        /* primitives of the uploaded scene (an empty BLAS counts)                           */
     uint32_t blasNodes;        /* 128-byte nodes of all BLASes                                                       */
@@ -360,6 +376,7 @@ typedef struct ChordRaySceneInfo {              /* 64 bytes */
 #ifdef __cplusplus
 }
 static_assert(sizeof(ChordRay) == 32 && sizeof(ChordRayHit) == 32 && sizeof(ChordRaySceneInfo) == 64, "ray records");
+static_assert(sizeof(ChordRayHitSurface) == 64, "ChordRayHitSurface");
 static_assert(sizeof(ChordBoundsTilesDesc) == 16, "ChordBoundsTilesDesc");
 static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
 static_assert(sizeof(ChordBoundsResult) == 16, "ChordBoundsResult");
