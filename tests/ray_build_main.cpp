@@ -11,6 +11,7 @@
 
 #include "ray_scene.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -162,6 +163,24 @@ int main()
         float x = 1.0f;
         for (int t = 0; t < 120; t++) { Box b{{x, 0.0f, 0.0f}, {x * 1.01f, 1.0f, 1.0f}}; boxes.push_back(b); x *= 2.0f; }
         check_tree("exponential", boxes, kLeafTriangles, 0u, 0u);
+    }
+    {   // the deep scene of tests/ray_deep_cases.py: its primitive's 128 triangles, x = 2^(j - 125), and its 120 instance boxes, moved
+        // along x by 0, 8, 16, ... 2^121 (formed from centre and extent, as an object's box is).  Both must use the depth bound fully.
+        std::vector<Box> boxes;
+        for (int j = 0; j < 128; j++) {
+            const float x = std::ldexp(1.0f, j - 125), x2 = x * (1.0f + 0.0078125f);
+            const float v[9] = {x, 0.0f, 0.0f, x, 1.0f, 0.0f, x2, 0.0f, 1.0f};
+            boxes.push_back(tri_box(v));
+        }
+        check_tree("deep_blas", boxes, kLeafTriangles, 0u, 0u);
+        const float mn = std::ldexp(1.0f, -125), mx = 4.0f * (1.0f + 0.0078125f), c = (mn + mx) * 0.5f, e = mx - c;
+        boxes.clear();
+        for (int k = 0; k < 120; k++) {
+            const float t = k == 0 ? 0.0f : std::ldexp(1.0f, k + 2);
+            Box b{{(c - e) + t, 0.0f, 0.0f}, {(c + e) + t, 1.0f, 1.0f}};
+            boxes.push_back(b);
+        }
+        check_tree("deep_tlas", boxes, 1u, 0u, 0u);
     }
     {   // NaN and infinite boxes among ordinary ones (an upload does not refuse them; the library's own build does, before it gets
         // here): the equal-count sort's key is total, so the builder still ends, with every item in one leaf

@@ -15,6 +15,7 @@ import helpers as H
 import inflight as IF
 import meshlet_shapes as MS
 import spec_rays_np as S
+from ray_deep_cases import meshlet_primitive as _meshlet_primitive
 from chord_amd import lib as L, records as R, scenes
 
 pytestmark = pytest.mark.gpu
@@ -23,32 +24,6 @@ PW, PH = 64, 40
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------------
-
-def _meshlet_primitive(positions, tris_per_meshlet, group_sizes):
-    """A finished-primitive dictionary (scenes.PrimitiveBuilder.finish) of LOD-0 meshlets written directly: positions (n, 3), and per
-    meshlet an int array (T, 3) of indices into them."""
-    positions = np.asarray(positions, dtype=np.float32)
-    meshlets, data, nd = np.zeros(len(tris_per_meshlet), dtype=R.MESHLET), [], 0
-    for k, tris in enumerate(tris_per_meshlet):
-        tris = np.asarray(tris, dtype=np.int64).reshape(-1, 3)
-        gid = np.unique(tris)
-        local = np.searchsorted(gid, tris)
-        m = meshlets[k]
-        m["posMin"], m["posMax"] = positions[gid].min(axis=0), positions[gid].max(axis=0)
-        m["coneCutOff"] = 1.0                                              # (a cone that never culls)
-        m["vertexTriangleCount"] = len(gid) | (len(tris) << 8)
-        m["dataOffset"] = nd
-        data.append(np.concatenate([gid, local[:, 0] | (local[:, 1] << 8) | (local[:, 2] << 16)]).astype(np.uint32))
-        nd += len(gid) + len(tris)
-    groups = np.zeros(len(group_sizes), dtype=R.MESHLET_GROUP)
-    groups["error"], groups["parentError"] = -1.0, scenes.FLT_MAX
-    groups["meshletCount"] = group_sizes
-    groups["meshletOffset"] = np.concatenate([[0], np.cumsum(group_sizes)[:-1]])
-    groups, nodes = scenes.build_bvh(groups)
-    return dict(bvh_nodes=nodes, positions=positions, texcoords=np.zeros((len(positions), 2), np.float32), normals=None, tangents=None,
-                meshlets=meshlets, meshlet_data=np.concatenate(data), groups=groups,
-                group_indices=np.arange(len(tris_per_meshlet), dtype=np.uint32))
-
 
 def _quads(quads):
     """positions and triangles of axis-aligned quads given by four corners each, corners shared exactly between neighbours."""
