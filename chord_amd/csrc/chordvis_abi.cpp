@@ -1964,6 +1964,53 @@ int chordvis_trace_rays(ChordCtx* c, const ChordRay* deviceRays, uint32_t count,
     return CHORDVIS_OK;
 }
 
+// Everything is checked before the device is touched; no device pointer is dereferenced here.  The refusals of chordvis_trace_rays
+// first, in its order; then the desc; then -- behind the empty image, which launches nothing -- the pointers the desc asks for.
+int chordvis_pixel_rays(ChordCtx* c, const ChordPixelRaysDesc* desc, const float* devicePosition, const float* deviceNormal, const float* deviceZ,
+                        const float* deviceTable, float* deviceOut, ChordRayHit* deviceHits)
+{
+    if (!c) return CHORDVIS_E_INVALID;
+    { const int rc = ray_checks(c, "pixel_rays", true); if (rc) return rc; }
+    if (c->rayRefitDue)
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: the objects changed (chordvis_update_objects / chordvis_build_objects / chordvis_bind_objects): call chordvis_refit_ray_scene first");
+    if (!desc) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: desc is NULL");
+    const uint32_t kFlags = CHORD_PIXEL_RAYS_ANY_HIT | CHORD_PIXEL_RAYS_FRONT_ONLY | CHORD_PIXEL_RAYS_START_FROM_DEPTH;
+    if (desc->mode != CHORD_PIXEL_RAYS_HEMISPHERE && desc->mode != CHORD_PIXEL_RAYS_DIRECTION)
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: unknown mode (CHORD_PIXEL_RAYS_HEMISPHERE or CHORD_PIXEL_RAYS_DIRECTION)");
+    if (desc->flags & ~kFlags)
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: unknown flag bits (CHORD_PIXEL_RAYS_ANY_HIT, _FRONT_ONLY and _START_FROM_DEPTH are the flags)");
+    const bool hemisphere = desc->mode == CHORD_PIXEL_RAYS_HEMISPHERE;
+    const bool anyHit = (desc->flags & CHORD_PIXEL_RAYS_ANY_HIT) != 0u, frontOnly = (desc->flags & CHORD_PIXEL_RAYS_FRONT_ONLY) != 0u;
+    if (hemisphere) {
+        const uint32_t tw = desc->tableW, th = desc->tableH;
+        if (!deviceTable) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: CHORD_PIXEL_RAYS_HEMISPHERE needs deviceTable");
+        if (tw == 0u || th == 0u || (tw & (tw - 1u)) || (th & (th - 1u)))
+            return fail(c, CHORDVIS_E_INVALID, "pixel_rays: tableW and tableH must be powers of two");
+    }
+    if ((desc->flags & CHORD_PIXEL_RAYS_START_FROM_DEPTH) && !deviceZ)
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: CHORD_PIXEL_RAYS_START_FROM_DEPTH needs deviceZ");
+    if (deviceZ && desc->deviceZStride == 0u) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceZStride must not be 0 with a deviceZ");
+    if (anyHit && deviceHits) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: CHORD_PIXEL_RAYS_ANY_HIT writes no hit records (deviceHits must be NULL)");
+    if (frontOnly && hemisphere) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: CHORD_PIXEL_RAYS_FRONT_ONLY goes with CHORD_PIXEL_RAYS_DIRECTION only");
+    const uint64_t pixels = (uint64_t)desc->width * desc->height;
+    if (pixels > 0xFFFFFFFFull) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: width * height must not exceed 2^32 - 1");
+    if (pixels == 0u) return CHORDVIS_OK;
+    if (!devicePosition || ((uintptr_t)devicePosition & 15u))
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: devicePosition must be non-NULL and 16-byte aligned");
+    const bool needNormal = hemisphere || frontOnly;
+    if (needNormal && (!deviceNormal || ((uintptr_t)deviceNormal & 15u)))
+        return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceNormal must be non-NULL and 16-byte aligned (HEMISPHERE, FRONT_ONLY)");
+    if (hemisphere && ((uintptr_t)deviceTable & 15u)) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceTable must be 16-byte aligned");
+    if ((uintptr_t)deviceZ & 3u) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceZ must be NULL or 4-byte aligned");
+    if (!deviceOut || ((uintptr_t)deviceOut & 3u)) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceOut must be non-NULL and 4-byte aligned");
+    if ((uintptr_t)deviceHits & 15u) return fail(c, CHORDVIS_E_INVALID, "pixel_rays: deviceHits must be NULL or 16-byte aligned");
+    (void)hipSetDevice(c->device);
+    // (a normal or a table no statement reads is not handed to the kernel)
+    chord::launch_pixel_rays(c, *desc, devicePosition, needNormal ? deviceNormal : nullptr, deviceZ, hemisphere ? deviceTable : nullptr, deviceOut, deviceHits);
+    CHORD_HIP(c, hipGetLastError());
+    return CHORDVIS_OK;
+}
+
 // Everything is checked before the device is touched; no device pointer is dereferenced here.  Needs no ray scene: the hits may be a host's.
 int chordvis_shade_ray_hits(ChordCtx* c, const ChordRayHit* deviceHits, uint32_t count, float lod, const float* deviceLods, ChordRayHitSurface* deviceSurfaces)
 {

@@ -801,6 +801,10 @@ void launch_ray_trace(ChordCtx* c, const ChordRay* rays, uint32_t count, bool an
 // kernels_rayshade.hip: chordvis_shade_ray_hits' launch (arguments checked by the entry point; count > 0).  One launch on the context's
 // stream, of the kernel for the texel store or -- some chain kept as blocks -- the one that reads both stores.
 void launch_ray_shade(ChordCtx* c, const ChordRayHit* hits, uint32_t count, float lod, const float* lods, ChordRayHitSurface* surfaces);
+// kernels_pixelrays.hip: chordvis_pixel_rays' launch (arguments checked by the entry point; width * height > 0).  One launch on the
+// context's stream, of the closest-hit or the any-hit kernel.
+void launch_pixel_rays(ChordCtx* c, const ChordPixelRaysDesc& desc, const float* position, const float* normal, const float* z, const float* table,
+                       float* out, ChordRayHit* hits);
 void stamp(ChordCtx* c, int tag);               // no-op when timers are off
 int comm_render_frame(ChordCtx* c);             // multi_gpu.cpp: phase a -> ncclAllGather -> phase b -> ncclAllGather -> phase c
 

@@ -161,6 +161,17 @@ RAY_MAX_DEPTH = 12
 RAYSURF_VALID, RAYSURF_BACK_FACE, RAYSURF_TWO_SIDED, RAYSURF_PBR = 1, 2, 4, 8      # ChordRayHitSurface::flags (chordvis_shade_ray_hits)
 
 
+class PixelRaysDesc(C.Structure):
+    """ChordPixelRaysDesc: image and table sizes, mode, flags and the ray interval of chordvis_pixel_rays."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32),
+                ("tableW", C.c_uint32), ("tableH", C.c_uint32), ("deviceZStride", C.c_uint32), ("pad", C.c_uint32),
+                ("direction", C.c_float * 3), ("rayLength", C.c_float), ("tMin", C.c_float), ("zNear", C.c_float), ("pad2", C.c_float * 2)]
+
+
+PIXEL_RAYS_HEMISPHERE, PIXEL_RAYS_DIRECTION = 0, 1                                   # ChordPixelRaysDesc::mode
+PIXEL_RAYS_ANY_HIT, PIXEL_RAYS_FRONT_ONLY, PIXEL_RAYS_START_FROM_DEPTH = 1, 2, 4     # ChordPixelRaysDesc::flags
+
+
 class CameraDesc(C.Structure):
     _fields_ = [
         ("position", C.c_double * 3), ("front", C.c_double * 3), ("worldUp", C.c_double * 3),
@@ -257,6 +268,8 @@ def _load():
         "chordvis_ray_scene_info": (i32, [vp, P(RaySceneInfo)]),
         # (ctx, deviceHits, count, lod, deviceLods, deviceSurfaces): the float travels as a float, every pointer as a void pointer
         "chordvis_shade_ray_hits": (i32, [vp, vp, u32, C.c_float, vp, vp]),
+        # (ctx, desc, devicePosition, deviceNormal, deviceZ, deviceTable, deviceOut, deviceHits)
+        "chordvis_pixel_rays": (i32, [vp, P(PixelRaysDesc), vp, vp, vp, vp, vp, vp]),
         "chordvis_set_view": (i32, [vp, vp, vp, u32]),
         "chordvis_allocate_gbuffer": (i32, [vp, u32, u32, vp]),
         "chordvis_set_shard": (i32, [vp, u32, u32]),

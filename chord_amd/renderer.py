@@ -480,6 +480,67 @@ class VisibilityRenderer:
             out.data_ptr() if count else None), "shade_ray_hits"))
         return out
 
+    def pixel_rays(self, position, normal=None, mode=L.PIXEL_RAYS_HEMISPHERE, table=None, direction=(0.0, 0.0, 0.0), ray_length=1.0, t_min=0.0,
+                   z_near=0.0, depth=None, depth_stride=1, any_hit=False, front_only=False, start_from_depth=False, hits=False, out=None,
+                   out_hits=None):
+        """chordvis_pixel_rays, one launch that never waits: a ray per pixel of the position and normal images, traced and reduced to
+        one float per pixel.  position, normal: contiguous float32 CUDA tensors (height, width, 4) on the context's device (what
+        resolve_attributes returns as positionRS and vertexNormal / pixelNormal); normal may be None for L.PIXEL_RAYS_DIRECTION without
+        front_only.  table: (tableH, tableW, 4) float32, the tangent-space directions of L.PIXEL_RAYS_HEMISPHERE.  depth: None, a
+        float32 CUDA tensor of height * width * depth_stride values, or a device address (an int: visibility_ptr() + 4 with
+        depth_stride=2 reads the depth halves of the visibility image in place).  hits=True (or out_hits) also writes the closest
+        hits.  Returns the (height, width) float32 image, or (image, (height * width, 8) int32 records.RAY_HIT words) with hits.
+
+        Ordering and lifetime as in shade_ray_hits: the context's stream waits for the current torch stream before the call and the
+        current torch stream waits for the context's stream after it; no tensor is recorded on the context's stream."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def image(t, what, channels=4):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.device.index == self.device, \
+                "pixel_rays: %s is a contiguous float32 tensor on cuda:%d" % (what, self.device)
+            assert t.dim() == 3 and t.shape[2] == channels, "pixel_rays: %s is (height, width, %d)" % (what, channels)
+            return t
+        image(position, "position")
+        height, width = int(position.shape[0]), int(position.shape[1])
+        if normal is not None:
+            assert tuple(image(normal, "normal").shape) == tuple(position.shape), "pixel_rays: normal is of position's size"
+        d = L.PixelRaysDesc()
+        d.width, d.height, d.mode = width, height, int(mode)
+        d.flags = (L.PIXEL_RAYS_ANY_HIT if any_hit else 0) | (L.PIXEL_RAYS_FRONT_ONLY if front_only else 0) | \
+                  (L.PIXEL_RAYS_START_FROM_DEPTH if start_from_depth else 0)
+        if table is not None:
+            image(table, "table")
+            d.tableH, d.tableW = int(table.shape[0]), int(table.shape[1])
+        d.direction[:] = [float(v) for v in direction]
+        d.rayLength, d.tMin, d.zNear = float(ray_length), float(t_min), float(z_near)
+        zp = None
+        if depth is not None:
+            d.deviceZStride = int(depth_stride)
+            if isinstance(depth, int):
+                zp = depth
+            else:
+                assert depth.is_cuda and depth.is_contiguous() and depth.dtype == torch.float32 and depth.device.index == self.device
+                assert depth.numel() >= width * height * int(depth_stride), "pixel_rays: depth holds height * width * depth_stride values"
+                zp = depth.data_ptr()
+        want_hits = bool(hits) or out_hits is not None
+        if out is None:
+            with torch.cuda.device(dev):
+                out = torch.empty((height, width), dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == width * height and out.device.index == self.device
+        if want_hits and out_hits is None:
+            with torch.cuda.device(dev):
+                out_hits = torch.empty((width * height, 8), dtype=torch.int32, device=dev)
+        if want_hits:
+            assert out_hits.is_cuda and out_hits.is_contiguous() and out_hits.numel() * out_hits.element_size() == width * height * R.RAY_HIT.itemsize
+            assert out_hits.device.index == self.device
+        n = width * height
+        self._on_my_stream([], lambda: self._check(L.lib.chordvis_pixel_rays(
+            self._ctx, C.byref(d), position.data_ptr() if n else None, normal.data_ptr() if (normal is not None and n) else None, zp,
+            table.data_ptr() if table is not None else None, out.data_ptr() if n else None,
+            out_hits.data_ptr() if (want_hits and n) else None), "pixel_rays"))
+        return (out, out_hits) if want_hits else out
+
     def allocate_gbuffer(self, width, height, device_visibility=None):
         self._check(L.lib.chordvis_allocate_gbuffer(self._ctx, width, height, device_visibility), "allocate_gbuffer")
         self.width, self.height = width, height

@@ -227,7 +227,7 @@ int chordvis_create(int deviceOrdinal, void* hipStream, ChordCtx** outCtx);
  *     have yet to write: read them ordered behind the context's stream; chordvis_history_hzb may launch the tail of the chain);
  *     chordvis_scatter_world_transforms and chordvis_build_objects (one launch each, of any size: the way to new object records
  *     for a host that must not wait); chordvis_set_object_list while the new list fits what is allocated (it MAY WAIT when a buffer
- *     has to grow: OBJECTS COME AND GO below); chordvis_refit_ray_scene and chordvis_trace_rays (one launch each: RAY QUERIES below).
+ *     has to grow: OBJECTS COME AND GO below); chordvis_refit_ray_scene, chordvis_trace_rays and chordvis_pixel_rays (one launch each: RAY QUERIES below).
  *     The kernels a frame launches are chosen from reports the device leaves when a pass finishes; the host may hold a report any
  *     number of frames old, or none: the choice costs or saves time, never a pixel, a list entry or an HZB texel.
  *   MAY WAIT for everything enqueued before it: chordvis_upload_scene, chordvis_upload_material_textures,
@@ -309,8 +309,8 @@ int chordvis_bind_objects(ChordCtx* ctx, const ChordObject* deviceObjects, uint3
  *     chordvis_render_shadow makes the views again and renders every cascade; the view-by-view depth calls are refused until
  *     chordvis_allocate_depth_views); the sharded lists and the cull exchange buffer
  *     (re-made on demand, as at upload); the resolve state -- chordvis_resolve_*, the feedback calls and everything else that needs a
- *     frame's image are refused until a frame has run; the TLAS of the ray scene (chordvis_refit_ray_scene and chordvis_trace_rays are
- *     refused until chordvis_build_ray_scene, which keeps the BLASes and builds none again).
+ *     frame's image are refused until a frame has run; the TLAS of the ray scene (chordvis_refit_ray_scene, chordvis_trace_rays and
+ *     chordvis_pixel_rays are refused until chordvis_build_ray_scene, which keeps the BLASes and builds none again).
  *   VALIDATE FIRST, COMMIT SECOND.  CHORDVIS_E_INVALID: count == 0 or hostObjects NULL; a primitive or material id out of range; no
  *     scene; a depth-view child context; a call between chordvis_frame_phase_cull and chordvis_frame_phase_a.  CHORDVIS_E_CAPACITY:
  *     2^24 - 2 or more cluster instances, or more than 2^31 - 1 group instances.  A refused call changes NOTHING -- unlike a refused
@@ -474,6 +474,54 @@ int chordvis_ray_scene_info(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
  * point hands out (read from the code). */
 int chordvis_shade_ray_hits(ChordCtx* ctx, const ChordRayHit* deviceHits, uint32_t count, float lod, const float* deviceLods,
                             ChordRayHitSurface* deviceSurfaces);
+
+/* PIXEL RAYS (gi_rt_ao.hlsl, the first of the reference's ray consumers and the one a frame of this library feeds by itself; a sun-
+ * shadow mask likewise).  chordvis_pixel_rays generates one ray per pixel from caller-owned position and normal images
+ * (ChordResolveTargets::positionRS; ChordSurfaceTargets::vertexNormal or the material resolve's pixel normal; or a host's own), traces
+ * it against the ray scene and reduces the result to one float per pixel, in ONE launch on the context's stream that never waits;
+ * width * height == 0 succeeds without one.  The rays never reach memory.  All pointers are caller-owned device memory, read and
+ * written when the launch runs, in stream order: behind the refit and behind whatever wrote the images on the context's stream.  The
+ * images need not come from this context's frame: valid with or without a view or a G-buffer, like chordvis_trace_rays; frames are
+ * untouched.
+ *   The answer is DEFINED by tests/spec_pixel_rays_np.py (pixel_rays), which builds a ChordRay per pixel and hands it to the brute
+ *   force of tests/spec_rays_np.py, and is that specification's word for word: binary32, one rounding per operation, no contraction,
+ *   correctly rounded divide and square root, no transcendental.  Per pixel (x, y), i = y * width + x:
+ *     valid      with deviceZ: z = deviceZ[i * deviceZStride] > 0 (deviceZStride in floats: 1 reads a D32 image, 2 the depth halves of
+ *                the library's 64-bit visibility words in place, the pointer at the first word's high half); without: position.w != 0
+ *                (the resolve writes xyz, 1 and all-zero for an empty pixel).  An INVALID pixel traces nothing: out = 1, a zero hit record.
+ *     origin     position.xyz, translated-world space: the space of a ChordRay
+ *     n          normalize(normal.xyz) with chordvis_resolve_surface's normalize: 0 where the squared length is not above 0
+ *     direction  CHORD_PIXEL_RAYS_HEMISPHERE (gi_rt_ao.hlsl:59-61): dT = deviceTable[(y & (tableH - 1)) * tableW + (x & (tableW - 1))].xyz,
+ *                a tangent-space direction, z up, float4 per texel, tableW and tableH powers of two.  The host bakes
+ *                uniformSampleHemisphere(STBN_float2(...)) into the table once per slice and passes the slice of the frame: the library
+ *                owns no blue noise and evaluates no sin or cos.  createTBN (base.hlsli:1001-1025): |n.z| > 0: k = sqrt(n.y n.y +
+ *                n.z n.z), u = (0, -n.z / k, n.y / k); otherwise k = sqrt(n.x n.x + n.y n.y), u = (n.y / k, -n.x / k, 0); b = cross(n, u);
+ *                d = (dT.x u + dT.y b) + dT.z n per component.
+ *                CHORD_PIXEL_RAYS_DIRECTION: d = desc->direction for every pixel (a sun shadow ray).  With CHORD_PIXEL_RAYS_FRONT_ONLY a
+ *                pixel whose (n.x d.x + n.y d.y) + n.z d.z is not above 0 faces away: it traces nothing, out = 0, a zero hit record.
+ *     interval   tMax = rayLength; tMin = desc->tMin, or with CHORD_PIXEL_RAYS_START_FROM_DEPTH (getRayTraceStartOffset,
+ *                raytrace_shared.hlsli:10-17) lin = zNear / z, s = lin * 0.01f, w = s / (s + 1.0f), tMin = 5e-3f + w * (1e-1f - 5e-3f)
+ *     out        closest hit (default): min(max(t / rayLength, 0), 1) with the selects of RAY QUERIES, 1 on a miss; deviceHits, when
+ *                given, gets the ChordRayHit of chordvis_trace_rays for that ray.  CHORD_PIXEL_RAYS_ANY_HIT: 0 when a candidate exists,
+ *                1 otherwise; no hit records.
+ *     A ray with a non-finite word -- from a zero normal through 0 / 0, a non-finite table texel or position -- is a miss, as in RAY
+ *     QUERIES: out = 1.  So is tMin > tMax.  No pixel faults.
+ *   NOT HERE: the reference writes pow(out, power).  No pow is pinned on the device, so the exponent stays with the consumer, whose
+ *   denoiser reads this image next.  Several rays per pixel: call once per table slice and accumulate.
+ *   CHORDVIS_E_INVALID, chordvis_last_error naming the rule, everything checked before the device is touched and no device pointer
+ *   dereferenced on the host: every refusal of chordvis_trace_rays, in its order (a depth-view child context; no scene; no ray scene, or
+ *   one dropped since; a call before the refit an object change requires); a NULL desc; an unknown mode or flag bit; HEMISPHERE with a
+ *   NULL table or a table dimension that is zero or no power of two; START_FROM_DEPTH without deviceZ; a deviceZStride of 0 with a
+ *   deviceZ; ANY_HIT with deviceHits; FRONT_ONLY outside DIRECTION; width * height beyond 2^32 - 1; and, for an image that is not empty,
+ *   a NULL or 16-byte-misaligned position, normal (HEMISPHERE, FRONT_ONLY), table (HEMISPHERE) or hits pointer where it is needed, a
+ *   NULL or 4-byte-misaligned deviceOut, a 4-byte-misaligned deviceZ.
+ * tests/test_pixel_rays_host.py runs the per-pixel code on the host under the address and undefined-behaviour sanitizers;
+ * tests/test_gpu_pixel_rays.py holds the statements above on the GPU, but the refusal on a depth-view child context, which no entry
+ * point hands out (read from the code). */
+int chordvis_pixel_rays(ChordCtx* ctx, const ChordPixelRaysDesc* desc, const float* devicePosition /* float4 */,
+                        const float* deviceNormal /* float4 */, const float* deviceZ /* or NULL */,
+                        const float* deviceTable /* float4, HEMISPHERE only */, float* deviceOut /* float */,
+                        ChordRayHit* deviceHits /* or NULL */);
 
 /* uploadBufferToGPU("PerViewCamera") + ("MainViewInstanceCullingInfo") renderer.cpp:246,262
  * and the r.instanceculling.* cvars -> switchFlags (instance_culling.cpp:22-68). */

@@ -359,6 +359,22 @@ typedef struct ChordRayHitSurface {             /* 64 bytes, 16-byte aligned, mo
     uint32_t flags;            /* CHORD_RAYSURF_*                                                                    */
 } ChordRayHitSurface;
 
+/* chordvis_pixel_rays (chordvis.h RAY QUERIES, "pixel rays"): one ray per pixel of caller-owned position and normal images. */
+#define CHORD_PIXEL_RAYS_HEMISPHERE        0u   /* ChordPixelRaysDesc::mode: a tangent-space direction per pixel from the table (gi_rt_ao.hlsl) */
+#define CHORD_PIXEL_RAYS_DIRECTION         1u   /* one direction for every pixel (a sun shadow ray)                                             */
+#define CHORD_PIXEL_RAYS_ANY_HIT           1u   /* ChordPixelRaysDesc::flags: out = 0 when a candidate exists, 1 otherwise; no hit records       */
+#define CHORD_PIXEL_RAYS_FRONT_ONLY        2u   /* DIRECTION only: a pixel whose normal does not face the direction traces nothing, out = 0      */
+#define CHORD_PIXEL_RAYS_START_FROM_DEPTH  4u   /* tMin from the pixel's device depth and zNear (getRayTraceStartOffset); needs deviceZ          */
+typedef struct ChordPixelRaysDesc {             /* 64 bytes */
+    uint32_t width, height;    /* of the position, normal, depth and output images, row-major, no padding between rows */
+    uint32_t mode, flags;      /* CHORD_PIXEL_RAYS_*                                                                   */
+    uint32_t tableW, tableH;   /* HEMISPHERE: the direction table's size, powers of two                                */
+    uint32_t deviceZStride;    /* in floats: 1 a D32 image, 2 the depth halves of 64-bit visibility words              */
+    uint32_t pad;
+    float    direction[3];     /* DIRECTION: translated-world space, need not be normalised                            */
+    float    rayLength, tMin, zNear, pad2[2];
+} ChordPixelRaysDesc;
+
 typedef struct ChordRaySceneInfo {              /* 64 bytes */
     uint32_t blasCount;        /* primitives of the uploaded scene (an empty BLAS counts)                           */
     uint32_t blasNodes;        /* 128-byte nodes of all BLASes                                                       */
@@ -377,6 +393,7 @@ typedef struct ChordRaySceneInfo {              /* 64 bytes */
 }
 static_assert(sizeof(ChordRay) == 32 && sizeof(ChordRayHit) == 32 && sizeof(ChordRaySceneInfo) == 64, "ray records");
 static_assert(sizeof(ChordRayHitSurface) == 64, "ChordRayHitSurface");
+static_assert(sizeof(ChordPixelRaysDesc) == 64, "ChordPixelRaysDesc");
 static_assert(sizeof(ChordBoundsTilesDesc) == 16, "ChordBoundsTilesDesc");
 static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
 static_assert(sizeof(ChordBoundsResult) == 16, "ChordBoundsResult");

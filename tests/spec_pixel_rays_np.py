@@ -1,0 +1,125 @@
+"""The specification of chordvis_pixel_rays in numpy (include/chordvis.h RAY QUERIES, "pixel rays"): a records.RAY per pixel from
+position and normal images, handed to spec_rays_np.trace -- the brute force that knows no tree -- unchanged, and the hit reduced to
+one float.  TEST INFRASTRUCTURE: never imported by chord_amd/.
+
+Arithmetic: binary32 throughout, one rounding per operation in source order (numpy float32 arrays never contract), `/` and sqrt
+correctly rounded, no transcendental anywhere; min and max are spec_rays_np's selects.  Per pixel (x, y) of a width x height image:
+
+    valid      with a depth image: z = deviceZ[y, x] > 0; without: position.w != 0.  An invalid pixel traces nothing: out = 1, a
+               zero hit record.
+    origin     position.xyz
+    n          normalize(normal.xyz) = v / sqrt((x x + y y) + z z) per component, 0 where the squared length is not above 0
+    direction  HEMISPHERE: dT = table[y & (tableH - 1), x & (tableW - 1)].xyz; createTBN: |n.z| > 0: k = sqrt(n.y n.y + n.z n.z),
+               u = (0, -n.z / k, n.y / k); otherwise k = sqrt(n.x n.x + n.y n.y), u = (n.y / k, -n.x / k, 0); b = cross(n, u), each
+               component a b - c d; d = (dT.x u + dT.y b) + dT.z n.
+               DIRECTION: d = desc.direction; with FRONT_ONLY a pixel whose (n.x d.x + n.y d.y) + n.z d.z is not above 0 traces
+               nothing: out = 0, a zero hit record.
+    interval   tMax = rayLength; tMin = desc.tMin, or with START_FROM_DEPTH lin = zNear / z, s = lin * 0.01, w = s / (s + 1),
+               tMin = 5e-3 + w * (1e-1 - 5e-3)
+    out        closest: rmin(rmax(t / rayLength, 0), 1), 1 on a miss; ANY_HIT: 0 when a candidate exists, else 1, no hit records.
+A ray with a non-finite word, or with tMin > tMax, is a miss by spec_rays_np's own rule."""
+import numpy as np
+
+from chord_amd import records as R
+
+import spec_rays_np as S
+
+F = np.float32
+HEMISPHERE, DIRECTION = 0, 1
+ANY_HIT, FRONT_ONLY, START_FROM_DEPTH = 1, 2, 4
+TRACE, FIXED_ONE, FIXED_ZERO = 0, 1, 2              # a pixel's disposition
+
+
+class Desc:
+    """The fields of ChordPixelRaysDesc the answer depends on (deviceZStride is a matter of memory layout: deviceZ here is (h, w))."""
+
+    def __init__(self, width, height, mode, flags=0, tableW=0, tableH=0, direction=(0.0, 0.0, 0.0), rayLength=1.0, tMin=0.0, zNear=0.0):
+        self.width, self.height, self.mode, self.flags, self.tableW, self.tableH = int(width), int(height), int(mode), int(flags), int(tableW), int(tableH)
+        self.direction = tuple(float(F(v)) for v in direction)
+        self.rayLength, self.tMin, self.zNear = F(rayLength), F(tMin), F(zNear)
+
+    def __repr__(self):
+        return "Desc(%dx%d mode %d flags %d table %dx%d dir %r L %r tMin %r zNear %r)" % (
+            self.width, self.height, self.mode, self.flags, self.tableW, self.tableH, self.direction, self.rayLength, self.tMin, self.zNear)
+
+
+def normalize(v):
+    l2 = (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
+    s = np.sqrt(l2)[..., None]
+    return np.where((l2 > F(0.0))[..., None], v / s, F(0.0)).astype(F)
+
+
+def tangent_frame(n):
+    """createTBN: (u, b) of unit (or zero, or non-finite) normals n (..., 3)"""
+    nx, ny, nz = n[..., 0], n[..., 1], n[..., 2]
+    zero = np.zeros_like(nx)
+    kz = np.sqrt(ny * ny + nz * nz)
+    kx = np.sqrt(nx * nx + ny * ny)
+    uz = np.stack([zero, -nz / kz, ny / kz], axis=-1)
+    ux = np.stack([ny / kx, -nx / kx, zero], axis=-1)
+    z_branch = np.abs(nz) > F(0.0)
+    u = np.where(z_branch[..., None], uz, ux).astype(F)
+    b = np.stack([n[..., 1] * u[..., 2] - n[..., 2] * u[..., 1], n[..., 2] * u[..., 0] - n[..., 0] * u[..., 2],
+                  n[..., 0] * u[..., 1] - n[..., 1] * u[..., 0]], axis=-1).astype(F)
+    return u, b, z_branch
+
+
+def make_rays(position, normal, deviceZ, table, desc):
+    """(records.RAY (h * w,), disposition uint8 (h * w,), createTBN's branch bool (h * w,)) in row-major pixel order; the ray of a
+    pixel that is not traced is eight zero words."""
+    h, w = desc.height, desc.width
+    pos = np.asarray(position, dtype=F).reshape(h * w, 4)
+    nrm = np.zeros((h * w, 4), dtype=F) if normal is None else np.asarray(normal, dtype=F).reshape(h * w, 4)
+    z = None if deviceZ is None else np.asarray(deviceZ, dtype=F).reshape(h * w)
+    assert not (desc.flags & START_FROM_DEPTH) or z is not None, "START_FROM_DEPTH needs a depth image"
+    assert not (desc.flags & FRONT_ONLY) or desc.mode == DIRECTION, "FRONT_ONLY goes with DIRECTION"
+    ys, xs = np.divmod(np.arange(h * w), max(w, 1))
+    with np.errstate(all="ignore"):
+        valid = (z > F(0.0)) if z is not None else (pos[:, 3] != F(0.0))
+        disp = np.where(valid, TRACE, FIXED_ONE).astype(np.uint8)
+        n = normalize(nrm[:, :3])
+        z_branch = np.zeros(h * w, dtype=bool)
+        if desc.mode == HEMISPHERE:
+            assert desc.tableW > 0 and desc.tableH > 0 and not (desc.tableW & (desc.tableW - 1)) and not (desc.tableH & (desc.tableH - 1))
+            tab = np.asarray(table, dtype=F).reshape(desc.tableH * desc.tableW, 4)
+            dT = tab[(ys & (desc.tableH - 1)) * desc.tableW + (xs & (desc.tableW - 1)), :3]
+            u, b, z_branch = tangent_frame(n)
+            d = ((dT[:, 0:1] * u + dT[:, 1:2] * b) + dT[:, 2:3] * n).astype(F)
+        else:
+            d = np.broadcast_to(np.array(desc.direction, dtype=F), (h * w, 3)).copy()
+            if desc.flags & FRONT_ONLY:
+                facing = (n[:, 0] * d[:, 0] + n[:, 1] * d[:, 1]) + n[:, 2] * d[:, 2]
+                disp = np.where(valid & ~(facing > F(0.0)), FIXED_ZERO, disp).astype(np.uint8)
+        t_min = np.full(h * w, desc.tMin, dtype=F)
+        if desc.flags & START_FROM_DEPTH:
+            lin = desc.zNear / z
+            s = lin * F(0.01)
+            wgt = s / (s + F(1.0))
+            t_min = (F(5e-3) + wgt * (F(1e-1) - F(5e-3))).astype(F)
+    rays = np.zeros(h * w, dtype=R.RAY)
+    go = disp == TRACE
+    rays["origin"][go], rays["tMin"][go] = pos[go, :3], t_min[go]
+    rays["direction"][go], rays["tMax"][go] = d[go], desc.rayLength
+    return rays, disp, z_branch
+
+
+def pixel_rays(scene, objects, position, normal, deviceZ, table, desc, triangles=None, meshlet_cull=False, info=None):
+    """(out float32 (h, w), hits records.RAY_HIT (h * w,) or None under ANY_HIT) of chordvis_pixel_rays.  triangles, meshlet_cull: as
+    spec_rays_np.trace takes them.  info: a dictionary that receives the rays, the dispositions and createTBN's branches."""
+    h, w = desc.height, desc.width
+    rays, disp, z_branch = make_rays(position, normal, deviceZ, table, desc)
+    any_hit = bool(desc.flags & ANY_HIT)
+    go = np.flatnonzero(disp == TRACE)
+    hits = np.zeros(h * w, dtype=R.RAY_HIT)
+    if len(go):
+        hits[go] = S.trace(scene, objects, rays[go], any_hit=any_hit, triangles=triangles, meshlet_cull=meshlet_cull)
+    hit = (hits["status"] & 1) != 0
+    out = np.where(disp == FIXED_ZERO, F(0.0), F(1.0)).astype(F)
+    with np.errstate(all="ignore"):
+        if any_hit:
+            out[hit] = F(0.0)
+        else:
+            out[hit] = S.rmin(S.rmax(hits["t"][hit] / desc.rayLength, F(0.0)), F(1.0))
+    if info is not None:
+        info.update(rays=rays, disposition=disp, z_branch=z_branch)
+    return out.reshape(h, w), (None if any_hit else hits)
