@@ -760,7 +760,7 @@ int chordvis_destroy(ChordCtx* c)
         c->dMatRecords = nullptr; c->dMatTexels = nullptr; c->dMatBlocks = nullptr;
     }
     dfree(c->dPrims); dfree(c->dGroups); dfree(c->dMeshlets); dfree(c->dGroupIndices); dfree(c->dMeshletData);
-    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod); dfree(c->dPrimVertexBase);
+    dfree(c->dPositions); dfree(c->dObjStatic); dfree(c->dMaterials); dfree(c->dTexAlpha); dfree(c->dTexcoords); dfree(c->dBvhNodes); dfree(c->dGroupRefs); dfree(c->dObjectsOwned); dfree(c->dMeshletLod); dfree(c->dPrimVertexBase); dfree(c->dPrimAssetMeshlets);
     dfree(c->dNormals); dfree(c->dTangents); dfree(c->dMatRecords); dfree(c->dMatTexels); dfree(c->dMatBlocks); dfree(c->dMatFeedback); dfree(c->dGeoFeedback); dfree(c->dBoundsScratch); dfree(c->dBoundsTilesScratch); dfree(c->dTexEncTables);
     dfree(c->dView); dfree(c->dObjFrame); dfree(c->dGroupMask); dfree(c->dBlockCounts);
     drop_world_transforms(c);
@@ -889,12 +889,15 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
     std::vector<uint32_t> primMeshlets(s->primitiveCount, 0);
     std::vector<uint64_t> primTriangles(s->primitiveCount, 0);
     std::vector<uint32_t> primVertexBase(s->primitiveCount, 0);   // asset vertex base + primitive.vertexOffset (chordvis_shade_ray_hits)
+    std::vector<uint2> primAssetMeshlets(s->primitiveCount, make_uint2(0u, 0u));   // (first meshlet, meshlet count) of the primitive's asset (the same call)
     for (uint32_t pi = 0; pi < s->primitiveCount; pi++) {
         const ChordPrimitive& p = s->primitives[pi];
         if (p.primitiveDatasBufferId >= s->assetCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: primitiveDatasBufferId out of range");
         const uint32_t a = p.primitiveDatasBufferId;
         const ChordAssetDesc& as = s->assets[a];
-        if (p.meshletGroupOffset + p.meshletGroupCount > as.meshletGroupCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: primitive group range out of bounds");
+        // (every range of a primitive is held to its OWN asset's counts, in 64 bits: one past an asset's stream is still inside the
+        // concatenation, and an offset near 2^32 must not wrap back into range)
+        if ((uint64_t)p.meshletGroupOffset + p.meshletGroupCount > as.meshletGroupCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: primitive group range out of bounds");
         DPrim& d = c->hPrims[pi];
         std::memcpy(d.posMin, p.posMin, 12); std::memcpy(d.posMax, p.posMax, 12);
         d.meshletBase = mB[a] + p.meshletOffset;
@@ -903,6 +906,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
         d.groupCount = p.meshletGroupCount;
         d.assetMeshletBase = mB[a];
         primVertexBase[pi] = vB[a] + p.vertexOffset;
+        primAssetMeshlets[pi] = make_uint2(mB[a], as.meshletCount);
         d.bvhBase = 0xFFFFFFFFu;
         if (as.bvhNodes && as.bvhNodeCount && p.bvhNodeOffset < as.bvhNodeCount) {
             // GPUBVHNode tree of the primitive (gltf.h:16-24): copied, and checked for what the hierarchical cull relies on --
@@ -969,9 +973,9 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
         for (uint32_t gi = 0; gi < p.meshletGroupCount; gi++) {
             const ChordMeshletGroup& g = as.meshletGroups[p.meshletGroupOffset + gi];
             for (uint32_t i = 0; i < g.meshletCount; i++) {
-                const uint32_t ii = p.meshletGroupIndicesOffset + g.meshletOffset + i;
+                const uint64_t ii = (uint64_t)p.meshletGroupIndicesOffset + g.meshletOffset + i;
                 if (ii >= as.meshletGroupIndexCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: group index out of bounds");
-                const uint32_t mi = p.meshletOffset + as.meshletGroupIndices[ii];
+                const uint64_t mi = (uint64_t)p.meshletOffset + as.meshletGroupIndices[ii];
                 if (mi >= as.meshletCount) return fail(c, CHORDVIS_E_INVALID, "upload_scene: meshlet index out of bounds");
                 DMeshlet& dm = meshlets[mB[a] + mi];
                 if (dm.vertexBase == 0xFFFFFFFFu) {                  // first reference: check the vertex ids against the asset
@@ -1152,7 +1156,7 @@ static int upload_scene_impl(ChordCtx* c, const ChordSceneDesc* s)
     if (!vec.empty()) CHORD_HIP(c, hipMemcpy(dst, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice));
     UP(c->dMeshlets, meshlets) UP(c->dGroups, groups) UP(c->dGroupIndices, gidx) UP(c->dMeshletData, mdata)
     UP(c->dPositions, pos) UP(c->dPrims, c->hPrims) UP(c->dObjStatic, c->hObjStatic) UP(c->dGroupRefs, refs)
-    UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod) UP(c->dPrimVertexBase, primVertexBase)
+    UP(c->dMaterials, dmats) UP(c->dMeshletLod, meshletLod) UP(c->dPrimVertexBase, primVertexBase) UP(c->dPrimAssetMeshlets, primAssetMeshlets)
     if (!bvh.empty()) { UP(c->dBvhNodes, bvh) } else dfree(c->dBvhNodes);
     c->bvhComplete = bvhComplete;
     if (alphaTexels) {

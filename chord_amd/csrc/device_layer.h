@@ -446,6 +446,7 @@ struct ChordCtx {
     float* dNormals = nullptr;                // float3 per vertex (normalBuffer), or null: no asset has normals (chordvis_resolve_surface only)
     float* dTangents = nullptr;               // float4 per vertex (tangentBuffer), or null: no asset has tangents (likewise)
     uint8_t* dMeshletLod = nullptr;           // per device meshlet: ChordMeshlet::lod (DMeshlet carries vertexBase instead; the resolve's debug view reads it)
+    uint2* dPrimAssetMeshlets = nullptr;      // per primitive: (first meshlet, meshlet count) of its asset in dMeshlets: a ray hit's meshlet is asset-relative (ray_shade.h); a depth-view child has none
     uint32_t* dPrimVertexBase = nullptr;      // per primitive: asset vertex base + primitive.vertexOffset (the shading of ray hits: ray_shade.h); a depth-view child has none
     bool anyMasked = false;
     // chordvis_upload_material_textures (read by chordvis_resolve_material alone; dropped by the next chordvis_upload_scene)

@@ -4,7 +4,7 @@
 //
 //   ray_shade_kernel    wave64, a hit per lane, four waves per workgroup.  The per-hit code is ray_shade.h's shade_ray_hit (which the
 //                       host compiler builds too and tests/ray_shade_main.cpp runs under the sanitizers): two 16-byte loads of the hit,
-//                       the walk object -> meshlet -> triangle word -> three vertex ids with every index checked against its count,
+//                       the walk object -> primitive -> asset-relative meshlet -> triangle word -> three vertex ids with every index checked against its count,
 //                       uv and the normal at the barycentrics, and the three material slots at an explicit level through the pinned
 //                       sampler.  The sRGB table is in LDS, as in the resolve kernels.  Four plain 16-byte stores per lane.
 //
@@ -57,7 +57,8 @@ void launch_ray_shade(ChordCtx* c, const ChordRayHit* hits, uint32_t count, floa
 {
     RayShadeArgs a;
     RayShadeScene& s = a.scene;
-    s.objects = c->dObjects; s.meshlets = c->dMeshlets; s.materials = c->dMatRecords; s.primVertexBase = c->dPrimVertexBase; s.meshletData = c->dMeshletData;
+    s.objects = c->dObjects; s.meshlets = c->dMeshlets; s.materials = c->dMatRecords; s.primVertexBase = c->dPrimVertexBase;
+    s.primAssetMeshlets = c->dPrimAssetMeshlets; s.meshletData = c->dMeshletData;
     s.texcoords = c->dTexcoords; s.normals = c->dNormals;
     s.texels = c->dMatTexels; s.blocks = reinterpret_cast<const uint2*>(c->dMatBlocks);
     s.objectCount = c->objectCount; s.meshletCount = c->meshletCount; s.primCount = c->primCount; s.materialCount = c->materialCount;

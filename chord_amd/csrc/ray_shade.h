@@ -5,8 +5,13 @@
 // of exactly their size, and kernels_rayshade.hip runs the same statements a hit per lane.
 //
 // Every index is compared with the COUNT of its array before it is used, in the order of the specification's validate: status bit 0 and
-// finite u, v; object and meshlet; the object's primitive and material ids; the triangle against the meshlet's count; the triangle
-// word; the three vertex-id words and the three vertex ids.  An invalid hit gives sixteen zero words and reads nothing further.
+// finite u, v; the object; the object's primitive and material ids; the meshlet against the meshlet count of the primitive's ASSET; the
+// triangle against the meshlet's count; the triangle word; the three vertex-id words and the three vertex ids.  An invalid hit gives
+// sixteen zero words and reads nothing further.
+//
+// The hit's meshlet is ASSET-RELATIVE, as chordvis_trace_rays and chordvis_pixel_rays write it (ChordRayHit::meshlet): it is read at
+// primAssetMeshlets[primitive].x + meshlet of the concatenated meshlet array, and is valid below primAssetMeshlets[primitive].y, the
+// asset's own count.  With one asset the pair is (0, the scene's meshlet count).
 #pragma once
 
 #include "device_layer.h"
@@ -19,6 +24,7 @@ struct RayShadeScene {             // pointers and the counts of what they point
     const DMeshlet* meshlets;
     const DMatRecord* materials;
     const uint32_t* primVertexBase; // per primitive: its vertexOffset, made global over the assets
+    const uint2* primAssetMeshlets; // per primitive: (first meshlet, meshlet count) of its asset in `meshlets`, or null: ONE asset, (0, meshletCount)
     const uint32_t* meshletData;
     const float* texcoords;        // float2 per vertex, or null: uv (0, 0)
     const float* normals;          // float3 per vertex, or null: a zero normal
@@ -64,11 +70,14 @@ __device__ __forceinline__ void ray_shade_geometry(const RayShadeScene& s, uint4
     o.valid = false; o.material = 0u; o.flags = 0u; o.u = 0.0f; o.v = 0.0f; o.n[0] = 0.0f; o.n[1] = 0.0f; o.n[2] = 0.0f; o.lodq = 0;
     const uint32_t status = h1.w, object = h0.w, meshlet = h1.x, triangle = h1.y;
     if (!(status & CHORD_RAY_HIT) || !rs_finite(h0.y) || !rs_finite(h0.z)) return;
-    if (object >= s.objectCount || meshlet >= s.meshletCount) return;
+    if (object >= s.objectCount) return;
     const ChordObject& ob = s.objects[object];
     const uint32_t prim = ob.GLTFPrimitiveDetail, mat = ob.GLTFMaterialData;
     if (prim >= s.primCount || mat >= s.materialCount) return;
-    const DMeshlet& m = s.meshlets[meshlet];
+    // (first meshlet, count) of the primitive's asset; a scene handed over without the table is one asset
+    const uint2 asset = s.primAssetMeshlets ? s.primAssetMeshlets[prim] : make_uint2(0u, s.meshletCount);
+    if (meshlet >= asset.y || (uint64_t)asset.x + meshlet >= s.meshletCount) return;
+    const DMeshlet& m = s.meshlets[asset.x + meshlet];
     const uint32_t vtc = m.vertexTriangleCount, V = vtc & 0xFFu, T = (vtc >> 8) & 0xFFu;
     if (triangle >= T) return;
     const uint64_t base = m.dataOffset, vertexBase = s.primVertexBase[prim];   // (the OBJECT's primitive's vertexOffset, as the specification's)

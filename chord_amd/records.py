@@ -308,6 +308,12 @@ class Scene:
     """Host-side scene: the reference's per-frame collected arrays, one asset.
 
     Holds numpy arrays alive and exposes a ctypes SceneDesc over them.
+
+    With ONE asset the two numberings of a meshlet are one number: the index into `meshlets` is both the asset-relative id of
+    ChordDrawCmd::meshletId / ChordRayHit::meshlet (what chordvis_readback_cmds, chordvis_trace_rays and chordvis_pixel_rays return
+    and chordvis_shade_ray_hits reads) and the device's concatenated id.  A ChordSceneDesc of several assets tells them apart: the
+    library concatenates the assets' streams and subtracts the asset's first meshlet wherever a record leaves it as asset-relative
+    ("Two numberings of a meshlet"; tests/multi_asset.py builds such scenes out of several Scene).
     """
 
     def __init__(self, objects, primitives, materials, meshlets, groups, group_indices, meshlet_data, positions,

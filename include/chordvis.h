@@ -443,11 +443,15 @@ int chordvis_ray_scene_info(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
  * list's.  Valid with or without a view or a G-buffer; frames are untouched.
  *   The answer is DEFINED by tests/spec_ray_shade_np.py (shade) and is that specification's word for word: binary32, one rounding
  *   per operation, no contraction, correctly rounded divide and square root.  Per hit:
- *     valid     status bit 0 set; u and v finite; object < the object count; meshlet < the scene's meshlet count; the object's
- *               GLTFPrimitiveDetail and GLTFMaterialData below their counts; triangle < the meshlet's triangle count; the triangle
+ *     meshlet   ChordRayHit::meshlet is ASSET-RELATIVE, as chordvis_trace_rays and chordvis_pixel_rays write it: an index into the
+ *               meshlets of the asset (ChordPrimitive::primitiveDatasBufferId) of the OBJECT's primitive.  It is read at that asset's
+ *               first meshlet + meshlet.  With one asset that is the index into the scene's meshlets.
+ *     valid     status bit 0 set; u and v finite; object < the object count; the object's GLTFPrimitiveDetail and GLTFMaterialData
+ *               below their counts; meshlet < the meshlet count of THAT ASSET (not the scene's: the id one past an asset's last
+ *               meshlet is invalid although the concatenated array goes on); triangle < the meshlet's triangle count; the triangle
  *               word, the three vertex-id words and the three vertex ids inside their arrays.  An INVALID hit gives sixteen zero words;
  *               no hit faults.  The vertex ids are offset by the vertexOffset of the OBJECT's primitive, also where a host's own hit
- *               pairs the object with a meshlet of another primitive.
+ *               pairs the object with a meshlet of another primitive OF THE SAME ASSET (a meshlet of another asset cannot be named).
  *     b         ((1 - u) - v, u, v)
  *     uv        (uv0 * b.x + uv1 * b.y) + uv2 * b.z per component; (0, 0) for a scene uploaded without texture coordinates, and the
  *               material fields are then sampled at (0, 0)
@@ -1124,7 +1128,9 @@ int chordvis_material_texture_levels(ChordCtx* ctx, uint32_t textureId, uint32_t
  *   chordvis_readback_geometry_feedback  synchronises and copies the arrays whose pointer is not NULL.
  *   chordvis_visible_clusters            writes the seen commands of the latest chordvis_geometry_feedback call into caller-owned DEVICE
  *                                        memory, IN LIST ORDER, records verbatim (`slot` keeps the original slot, so visibility ids still
- *                                        resolve through the full list).  *deviceCount receives the number of seen commands even when
+ *                                        resolve through the full list; `meshletId` stays in the device lists' concatenated numbering
+ *                                        -- the output is a device list for the calls that take one -- and is NOT the asset-relative
+ *                                        id chordvis_readback_cmds returns: in a scene of several assets the two differ).  *deviceCount receives the number of seen commands even when
  *                                        it exceeds `capacity`; nothing is written at or beyond `capacity` (deviceOut may be NULL when
  *                                        capacity is 0).  The order is part of the contract and does not depend on scheduling.  Two
  *                                        launches.  CHORDVIS_E_INVALID when no feedback call has run since the last reset or scene

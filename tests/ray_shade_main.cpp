@@ -5,7 +5,8 @@
 // sixteen words of every record:
 //   request   uint32 words.  Sixteen of header: objects, meshlets, primitives, materials, samplers, textures, meshlet-data words,
 //             vertices, has texcoords, has normals, hits, has per-hit levels, the uniform level (float bits), three zero words.  Then
-//             the object records (ChordObject, 56 words each); per primitive its vertexOffset; per meshlet dataOffset and
+//             the object records (ChordObject, 56 words each); per primitive its vertexOffset; per primitive the first meshlet and the
+//             meshlet count of its asset (a hit's meshlet is asset-relative; one asset: 0 and the meshlet count); per meshlet dataOffset and
 //             vertexTriangleCount; the meshlet data; the texture coordinates (2 floats a vertex) and the normals (3 floats a vertex) where the header says so; the
 //             materials (ChordMaterial, 24 words each); the samplers (4 words each); per texture width, height, mips and its RGBA8
 //             chain, a word a texel; the hits (ChordRayHit, 8 words each); the per-hit levels.
@@ -83,6 +84,7 @@ int main(int argc, char** argv)
     std::memset(&s, 0, sizeof(s));
     ChordObject* objects = exact<ChordObject>(take((size_t)nObjects * 56u), nObjects);
     uint32_t* primVertexBase = exact<uint32_t>(take(nPrims), nPrims);
+    uint2* primAssetMeshlets = exact<uint2>(take((size_t)nPrims * 2u), nPrims);
     const uint32_t* mw = take((size_t)nMeshlets * 2u);
     DMeshlet* meshlets = static_cast<DMeshlet*>(std::malloc(nMeshlets ? nMeshlets * sizeof(DMeshlet) : 1u));
     for (uint32_t i = 0; i < nMeshlets; i++) {
@@ -148,7 +150,7 @@ int main(int argc, char** argv)
     float* lods = hasLods ? exact<float>(take(nHits), nHits) : nullptr;
     if (at != req.size()) return 2;
 
-    s.objects = objects; s.meshlets = meshlets; s.materials = recs; s.primVertexBase = primVertexBase; s.meshletData = data; s.texcoords = texcoords; s.normals = normals;
+    s.objects = objects; s.meshlets = meshlets; s.materials = recs; s.primVertexBase = primVertexBase; s.primAssetMeshlets = primAssetMeshlets; s.meshletData = data; s.texcoords = texcoords; s.normals = normals;
     s.texels = texels; s.blocks = nullptr;
     s.objectCount = nObjects; s.meshletCount = nMeshlets; s.primCount = nPrims; s.materialCount = nMaterials; s.dataWords = nData; s.vertexCount = nVertices;
     float table[256], ap1[9];
@@ -159,7 +161,7 @@ int main(int argc, char** argv)
     for (uint32_t i = 0; i < nHits; i++)
         shade_ray_hit<false>(s, hits[2u * i], hits[2u * i + 1u], lods ? lods[i] : lod, table, ap1, &out[4u * i]);
 
-    std::free(objects); std::free(primVertexBase); std::free(meshlets); std::free(data); std::free(texcoords); std::free(normals); std::free(texels); std::free(recs);
+    std::free(objects); std::free(primVertexBase); std::free(primAssetMeshlets); std::free(meshlets); std::free(data); std::free(texcoords); std::free(normals); std::free(texels); std::free(recs);
     std::free(hits); std::free(lods);
     FILE* o = std::fopen(argv[2], "wb");
     if (!o) return 2;

@@ -17,7 +17,8 @@ correctly rounded, no transcendental anywhere; min and max are spec_rays_np's se
     interval   tMax = rayLength; tMin = desc.tMin, or with START_FROM_DEPTH lin = zNear / z, s = lin * 0.01, w = s / (s + 1),
                tMin = 5e-3 + w * (1e-1 - 5e-3)
     out        closest: rmin(rmax(t / rayLength, 0), 1), 1 on a miss; ANY_HIT: 0 when a candidate exists, else 1, no hit records.
-A ray with a non-finite word, or with tMin > tMax, is a miss by spec_rays_np's own rule."""
+A ray with a non-finite word, or with tMin > tMax, is a miss by spec_rays_np's own rule.  A hit record's meshlet is asset-relative
+like spec_rays_np's: for a scene of several assets pass triangles = spec_rays_np.lod0_triangles(scene, asset_meshlet_base)."""
 import numpy as np
 
 from chord_amd import records as R

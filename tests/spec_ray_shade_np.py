@@ -5,9 +5,14 @@ spec_material_np (sample_level, levels_of, slot_texture, tables) and spec_surfac
 TEST INFRASTRUCTURE: never imported by chord_amd/.
 
 Per hit (records.RAY_HIT), against the object records `objects` (the array the frames read now) over `scene`:
-  valid     status bit 0 set; u and v finite; object < len(objects); meshlet < len(scene.meshlets); the object's primitive and material
-            ids below their counts; triangle < the meshlet's triangle count; the triangle word, the three vertex-id words and the three
-            vertex ids inside their arrays.  An invalid hit gives sixteen zero words.
+  meshlet   the hit's meshlet is ASSET-RELATIVE (ChordRayHit::meshlet, as chordvis_trace_rays and chordvis_pixel_rays write it): an index
+            into the meshlets of the asset of the OBJECT's primitive.  In a scene of several assets -- `scene` is then the one-asset twin
+            of tests/multi_asset.py, the assets' arrays concatenated in the upload's order -- asset_meshlet_base[primitive] and
+            asset_meshlet_count[primitive] give that asset's first meshlet in scene.meshlets and its meshlet count: the meshlet is read
+            at base + meshlet.  A records.Scene as it stands is one asset: base 0, count len(scene.meshlets), the defaults.
+  valid     status bit 0 set; u and v finite; object < len(objects); the object's primitive and material ids below their counts;
+            meshlet < the meshlet count of the primitive's asset; triangle < the meshlet's triangle count; the triangle word, the three
+            vertex-id words and the three vertex ids inside their arrays.  An invalid hit gives sixteen zero words.
   vertices  spec_surface_np.vertex_ids' walk from (object, meshlet, triangle): meshlet data at dataOffset, V vertex-id words, the
             triangle word at dataOffset + V + triangle, ids + the primitive's vertexOffset.  lod0IndicesOffset stays unread.
   b         ((1 - u) - v, u, v)
@@ -91,19 +96,28 @@ def sample_lod(levels, sampler, u, v, lodq, srgb, stats=None):
     return out
 
 
-def validate(scene, objects, hits):
-    """(valid (N,) bool, vertex ids (N, 3) int64 -- zeros where invalid, material (N,) int64)"""
+def validate(scene, objects, hits, asset_meshlet_base=None, asset_meshlet_count=None):
+    """(valid (N,) bool, vertex ids (N, 3) int64 -- zeros where invalid, material (N,) int64).  asset_meshlet_base /
+    asset_meshlet_count: per primitive, the first meshlet and the meshlet count of its asset in scene.meshlets (None: one asset)."""
     hits = np.ascontiguousarray(hits, dtype=R.RAY_HIT).reshape(-1)
     n = len(hits)
     with np.errstate(all="ignore"):
         ok = ((hits["status"] & u32(1)) != 0) & np.isfinite(hits["u"]) & np.isfinite(hits["v"])
     o, mid, tri = hits["object"].astype(np.int64), hits["meshlet"].astype(np.int64), hits["triangle"].astype(np.int64)
-    ok &= (o < len(objects)) & (mid < len(scene.meshlets))
-    o, mid = np.where(ok, o, 0), np.where(ok, mid, 0)
+    ok &= o < len(objects)
+    o = np.where(ok, o, 0)
     prim = objects["GLTFPrimitiveDetail"][o].astype(np.int64)
     mat = objects["GLTFMaterialData"][o].astype(np.int64)
     ok &= (prim < len(scene.primitives)) & (mat < len(scene.materials))
     prim, mat = np.where(ok, prim, 0), np.where(ok, mat, 0)
+    mbase = np.zeros(len(scene.primitives), dtype=np.int64) if asset_meshlet_base is None else np.asarray(asset_meshlet_base, dtype=np.int64)
+    mcount = np.full(len(scene.primitives), len(scene.meshlets), dtype=np.int64) if asset_meshlet_count is None else \
+        np.asarray(asset_meshlet_count, dtype=np.int64)
+    assert len(mbase) == len(mcount) == len(scene.primitives)
+    ok &= mid < mcount[prim]                               # asset-relative: below THAT asset's count
+    mid = np.where(ok, mid + mbase[prim], 0)               # ... and read at base + meshlet
+    ok &= mid < len(scene.meshlets)
+    mid = np.where(ok, mid, 0)
     m = scene.meshlets[mid]
     V = (m["vertexTriangleCount"] & u32(0xFF)).astype(np.int64)
     T = ((m["vertexTriangleCount"] >> u32(8)) & u32(0xFF)).astype(np.int64)
@@ -126,9 +140,9 @@ def validate(scene, objects, hits):
     return ok, vi, np.where(ok, mat, 0)
 
 
-def shade(scene, objects, hits, lod=0.0, lods=None, normals="scene", stats=None):
+def shade(scene, objects, hits, lod=0.0, lods=None, normals="scene", stats=None, asset_meshlet_base=None, asset_meshlet_count=None):
     """RAY_HIT_SURFACE per hit.  objects: the records.OBJECT array the hits are shaded against; normals: the stream the device
-    holds (default: the scene's; None: a scene uploaded without).  stats: a dict that receives "slots": per sampled (material, slot) a
+    holds (default: the scene's; None: a scene uploaded without).  asset_meshlet_base / asset_meshlet_count: validate's.  stats: a dict that receives "slots": per sampled (material, slot) a
     dict of sample_lod's statistics with "hits" (the indices that sampled it) and "material"."""
     hits = np.ascontiguousarray(hits, dtype=R.RAY_HIT).reshape(-1)
     objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
@@ -139,7 +153,7 @@ def shade(scene, objects, hits, lod=0.0, lods=None, normals="scene", stats=None)
     if n == 0:
         return out
     srgb, ap1 = SM.tables()
-    valid, vi, mat = validate(scene, objects, hits)
+    valid, vi, mat = validate(scene, objects, hits, asset_meshlet_base, asset_meshlet_count)
     idx = np.nonzero(valid)[0]
     if not len(idx):
         return out

@@ -70,13 +70,16 @@ def object_boxes(objects, primitives):
     return lo.astype(F), hi.astype(F)
 
 
-def lod0_triangles(scene):
+def lod0_triangles(scene, asset_meshlet_base=None):
     """Per primitive: (vertices float32 (T, 3, 3), meshlet uint32 (T,), triangle uint32 (T,)) of the triangles of its meshlets with
-    lod == 0 reached through its groups, in ascending (meshlet, triangle) order.  meshlet: index into the asset's meshlets -- a
-    records.Scene is ONE asset, so that is the index into scene.meshlets (the library subtracts the asset's first meshlet; a scene of
-    several assets would have to do the same here)."""
+    lod == 0 reached through its groups, in ascending (meshlet, triangle) order.  meshlet: index into the ASSET's meshlets
+    (ChordRayHit::meshlet: the library subtracts the asset's first meshlet).  A records.Scene is ONE asset, so that is the index into
+    scene.meshlets; for the one-asset twin of a scene of several assets (tests/multi_asset.py) asset_meshlet_base[primitive] is the
+    first meshlet of the primitive's asset in scene.meshlets and is subtracted here (None: 0)."""
     out = []
-    for p in scene.primitives:
+    bases = np.zeros(len(scene.primitives), dtype=np.int64) if asset_meshlet_base is None else np.asarray(asset_meshlet_base, dtype=np.int64)
+    assert len(bases) == len(scene.primitives)
+    for p, mbase in zip(scene.primitives, bases):
         ids = set()
         for g in scene.groups[p["meshletGroupOffset"]: p["meshletGroupOffset"] + p["meshletGroupCount"]]:
             for i in range(int(g["meshletCount"])):
@@ -93,7 +96,7 @@ def lod0_triangles(scene):
             local = np.stack([words & 0xFF, (words >> 8) & 0xFF, (words >> 16) & 0xFF], axis=1).astype(np.int64)
             if T:
                 verts.append(scene.positions[vid[local]])
-                mids.append(np.full(T, m, dtype=np.uint32))
+                mids.append(np.full(T, m - int(mbase), dtype=np.uint32))
                 tids.append(np.arange(T, dtype=np.uint32))
         if verts:
             out.append((np.concatenate(verts).astype(F), np.concatenate(mids), np.concatenate(tids)))
@@ -186,12 +189,13 @@ def _object_best(ol, dl, verts, mids, nO, fO, tMin, tMax, meshlet_cull, pair_bud
     return has, bt, bu, bv, bd, bk
 
 
-def trace(scene, objects, rays, any_hit=False, triangles=None, meshlet_cull=False, pair_budget=1 << 21):
+def trace(scene, objects, rays, any_hit=False, triangles=None, meshlet_cull=False, pair_budget=1 << 21, asset_meshlet_base=None):
     """records.RAY_HIT for records.RAY rays against `objects` (records.OBJECT: the current list's records) over scene's geometry.
-    triangles: lod0_triangles(scene), when the caller has it.  meshlet_cull: the quicker evaluation of the same definition."""
+    triangles: lod0_triangles(scene[, asset_meshlet_base]), when the caller has it.  meshlet_cull: the quicker evaluation of the same
+    definition.  asset_meshlet_base: lod0_triangles' (a hit's meshlet is asset-relative); unused when triangles is given."""
     rays = np.ascontiguousarray(rays, dtype=R.RAY).reshape(-1)
     objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
-    tris = lod0_triangles(scene) if triangles is None else triangles
+    tris = lod0_triangles(scene, asset_meshlet_base) if triangles is None else triangles
     n = len(rays)
     hits = np.zeros(n, dtype=R.RAY_HIT)
     if n == 0:

@@ -5,7 +5,13 @@ INFRASTRUCTURE: never imported by chord_amd/.
 
 The triangle set-up is done once per distinct low word (slot | triangle) and gathered per pixel; every + - * / is a float32
 array operation in the order the HLSL writes it (numpy rounds each one separately, no contraction), so the result is the
-kernel's bit for bit.  Scenes are records.Scene (one asset): a command's meshletId indexes scene.meshlets directly."""
+kernel's bit for bit.  Scenes are records.Scene (one asset): a command's meshletId indexes scene.meshlets directly.
+
+Two numberings of a meshlet: `cmds` here are always in the CONCATENATED one (an index into scene.meshlets), which for one asset is
+also the asset-relative one of ChordDrawCmd::meshletId.  For a scene of several assets -- `scene` is then the one-asset twin of
+tests/multi_asset.py and the caller has put the read-back list through to_concatenated -- asset_meshlet_base[primitive] is the first
+meshlet of the primitive's asset: the meshlet debug views hash meshletId - base, the reference's asset-relative cmd.y
+(kernels_resolve.hip); nothing else reads the base."""
 import numpy as np
 
 from spec_np import mat, mul_mm, mul_mv
@@ -50,8 +56,9 @@ def _interp(a, b):
     return (a[..., 0, :] * b[..., 0:1] + a[..., 1, :] * b[..., 1:2]) + a[..., 2, :] * b[..., 2:3]
 
 
-def triangle_setup(scene, cmds, view, iv, lows, use_no_jitter=False, vp_nj=None, vp_last_nj=None):
-    """Per distinct low word: validity, the vertices' clip / translated-world / motion positions, uvs and the debug ids."""
+def triangle_setup(scene, cmds, view, iv, lows, use_no_jitter=False, vp_nj=None, vp_last_nj=None, asset_meshlet_base=None):
+    """Per distinct low word: validity, the vertices' clip / translated-world / motion positions, uvs and the debug ids.
+    asset_meshlet_base: per primitive, what the meshlet debug id subtracts (None: 0, one asset)."""
     lows = np.asarray(lows, dtype=u32)
     slot = ((lows >> u32(8)) & u32(MAX_INSTANCE_ID)).astype(np.int64) - 1
     tri = (lows & u32(0xFF)).astype(np.int64)
@@ -84,8 +91,11 @@ def triangle_setup(scene, cmds, view, iv, lows, use_no_jitter=False, vp_nj=None,
     px, py, pz = pos[..., 0], pos[..., 1], pos[..., 2]
     per_vertex = lambda Mx: mul_mv(Mx[:, None], px, py, pz)                    # (N, 3, 4)
     cur, last = per_vertex(m_cur), per_vertex(m_last)
+    hash_id = mid
+    if asset_meshlet_base is not None:
+        hash_id = mid - np.asarray(asset_meshlet_base, dtype=np.int64)[scene.objects["GLTFPrimitiveDetail"][o].astype(np.int64)]
     return dict(ok=ok, phs=per_vertex(mvp), prs=per_vertex(M)[..., :3], cur=cur[..., [0, 1, 3]], last=last[..., [0, 1, 3]], uv=uv,
-                meshlet=mid.astype(u32), tri_word=tri_word.astype(u32), lod=np.minimum(m["lod"], 11).astype(np.int64))
+                meshlet=(hash_id & 0xFFFFFFFF).astype(u32), tri_word=tri_word.astype(u32), lod=np.minimum(m["lod"], 11).astype(np.int64))
 
 
 def barycentrics(phs, pcx, pcy, inv_w, inv_h):
@@ -111,7 +121,7 @@ def barycentrics(phs, pcx, pcy, inv_w, inv_h):
 
 
 def resolve(scene, vis, cmds, view, iv, w, h, names=NAMES, use_no_jitter=False, vp_nj=None, vp_last_nj=None, debug_mode=0,
-            chunk=1 << 20, extras=False):
+            chunk=1 << 20, extras=False, asset_meshlet_base=None):
     """{name: array} as chordvis_resolve_attributes writes it: (h, w, channels) float32, (h, w) uint32 for debugRGBA8.
     extras=True adds "hit" (h, w) bool and "phs" (h, w, 3, 4): the clip position interpolated with the barycentrics, with ddx and
     with ddy (what the tests check the raster against)."""
@@ -129,7 +139,7 @@ def resolve(scene, vis, cmds, view, iv, w, h, names=NAMES, use_no_jitter=False, 
     if len(idx):
         keys, inv = np.unique(low[idx], return_inverse=True)
         with np.errstate(all="ignore"):
-            S = triangle_setup(scene, cmds, view, iv, keys, use_no_jitter, vp_nj, vp_last_nj)
+            S = triangle_setup(scene, cmds, view, iv, keys, use_no_jitter, vp_nj, vp_last_nj, asset_meshlet_base)
         inv_w, inv_h = f32(view["renderDimension"][2]), f32(view["renderDimension"][3])
         for c0 in range(0, len(idx), chunk):
             pix, t = idx[c0:c0 + chunk], inv[c0:c0 + chunk]

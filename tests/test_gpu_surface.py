@@ -8,6 +8,7 @@ import pytest
 from chord_amd import records as R, scenes
 
 import helpers as H
+import multi_asset as MA
 import spec_resolve_np as SR
 import spec_surface_np as SS
 
@@ -30,9 +31,9 @@ def _gpu(r, names):
     return {n: t.cpu().numpy().view(np.uint32) for n, t in out.items()}
 
 
-def _check(r, scene, view, iv, what, names=SS.NAMES, spec_scene=None, **kw):
+def _check(r, scene, view, iv, what, names=SS.NAMES, spec_scene=None, cmds=None, **kw):
     got = _gpu(r, list(names))
-    want = SS.resolve(spec_scene or scene, r.read_visibility(), r.read_cmds(r.last_frame_cmds()), view, iv, r.width, r.height,
+    want = SS.resolve(spec_scene or scene, r.read_visibility(), r.read_cmds(r.last_frame_cmds()) if cmds is None else cmds, view, iv, r.width, r.height,
                       names=names, **kw)
     for n in names:
         wv = np.ascontiguousarray(want[n]).view(np.uint32)
@@ -99,46 +100,15 @@ def test_config3_4k(gpu):
     r.close()
 
 
-class _TwoAssetScene:
-    """Two records.Scene as the two assets of one ChordSceneDesc (the second without normals and tangents), and the one-asset
-    scene the spec reads: the same arrays concatenated the way chordvis_upload_scene lays them out on the device."""
-
-    def __init__(self, a, b):
-        objs = np.concatenate([a.objects, b.objects])
-        objs["GLTFPrimitiveDetail"][len(a.objects):] += len(a.primitives)
-        objs["GLTFMaterialData"][len(a.objects):] += len(a.materials)
-        prims = np.concatenate([a.primitives, b.primitives])
-        prims["primitiveDatasBufferId"][len(a.primitives):] = 1
-        mats = np.concatenate([a.materials, b.materials])
-        self._keep = (objs, prims, mats, a, b)
-        self._assets = (R.AssetDesc * 2)(a._asset, b._asset)
-        self.desc = R.SceneDesc(objs.ctypes.data, len(objs), prims.ctypes.data, len(prims), mats.ctypes.data, len(mats),
-                                self._assets, 2, None, 0, None, 0)
-        self.objects = objs
-        # the spec's view: one asset, offsets shifted by the first asset's sizes
-        sp = prims.copy()
-        sp["primitiveDatasBufferId"] = 0
-        k = len(a.primitives)
-        sp["vertexOffset"][k:] += len(a.positions); sp["meshletOffset"][k:] += len(a.meshlets)
-        sp["meshletGroupOffset"][k:] += len(a.groups); sp["meshletGroupIndicesOffset"][k:] += len(a.group_indices)
-        ml = b.meshlets.copy(); ml["dataOffset"] += len(a.meshlet_data)
-        self.spec = R.Scene(objs, sp, mats, np.concatenate([a.meshlets, ml]), np.concatenate([a.groups, b.groups]),
-                            np.concatenate([a.group_indices, b.group_indices]),
-                            np.concatenate([a.meshlet_data, b.meshlet_data]), np.concatenate([a.positions, b.positions]),
-                            normals=np.concatenate([a.normals, np.zeros((len(b.positions), 3), np.float32)]),
-                            tangents=np.concatenate([a.tangents, np.zeros((len(b.positions), 4), np.float32)]))
-
-
 def test_an_asset_without_normals_beside_one_with_them(gpu):
     from chord_amd import lib as L
     a, cam = scenes.small_test_scene(200, 120, attributes=True)
     b, _ = scenes.small_test_scene(200, 120, seed=9)
     b.local_to_world = b.local_to_world.copy()
     b.local_to_world[:, 12] += 1.5                     # (the second asset's objects beside the first's)
-    two = _TwoAssetScene(a, b)
-    two.local_to_world = np.concatenate([a.local_to_world, b.local_to_world])
+    two = MA.MultiAssetScene([a, b])                    # (tests/multi_asset.py: what _TwoAssetScene of this file grew into)
     L.fill_objects(two, cam)
-    two.spec.objects = two.objects
+    assert two.spec.objects is two.objects
     view, iv = L.make_views(cam)
     r = _renderer(two, view, iv, cam.width, cam.height)
     r.render_frame()
@@ -149,7 +119,9 @@ def test_an_asset_without_normals_beside_one_with_them(gpu):
     on = slot[(slot >= 0) & (slot < len(cmds))]
     objs = cmds["objectId"][on]
     assert np.any(objs < len(a.objects)) and np.any(objs >= len(a.objects)), "both assets on screen"
-    got = _check(r, two, view, iv, "two assets", spec_scene=two.spec)
+    assert np.any(two.asset_of_object[objs] == 0) and np.any(two.asset_of_object[objs] == 1), "both assets on screen (objects are interleaved)"
+    cmds = two.to_concatenated(cmds)                   # (the list reads back asset-relative; the twin's meshlets are concatenated)
+    got = _check(r, two, view, iv, "two assets", spec_scene=two.spec, cmds=cmds)
     assert np.any(got["vertexNormal"].view(np.float32)[..., :3] != 0.0)
     r.close()
 

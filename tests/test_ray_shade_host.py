@@ -33,8 +33,12 @@ def program(tmp_path_factory):
     return exe, cc      # (a build that fails is every test's failure, asserted where the program is run)
 
 
-def _run(program, tmp_path, scene, objects, hits, lod=0.0, lods=None, texcoords="scene", normals="scene"):
-    """The program's records for `hits` against `objects` over `scene` (texcoords / normals None: a scene uploaded without)."""
+def _run(program, tmp_path, scene, objects, hits, lod=0.0, lods=None, texcoords="scene", normals="scene", asset_meshlet_base=None,
+         asset_meshlet_count=None):
+    """The program's records for `hits` against `objects` over `scene` (texcoords / normals None: a scene uploaded without).
+    asset_meshlet_base / asset_meshlet_count: per primitive, its asset's first meshlet and meshlet count (None: one asset)."""
+    mbase = np.zeros(len(scene.primitives), dtype=u32) if asset_meshlet_base is None else np.asarray(asset_meshlet_base, dtype=u32)
+    mcount = np.full(len(scene.primitives), len(scene.meshlets), dtype=u32) if asset_meshlet_count is None else np.asarray(asset_meshlet_count, dtype=u32)
     hits = np.ascontiguousarray(hits, dtype=R.RAY_HIT).reshape(-1)
     objects = np.ascontiguousarray(objects, dtype=R.OBJECT)
     uv = scene.texcoord0 if isinstance(texcoords, str) else texcoords
@@ -44,7 +48,8 @@ def _run(program, tmp_path, scene, objects, hits, lod=0.0, lods=None, texcoords=
                  len(scene.meshlet_data), len(scene.positions), uv is not None, nrm is not None, len(hits), lods is not None]
     head[12] = np.array([lod], dtype=f32).view(u32)[0]
     m = np.stack([scene.meshlets["dataOffset"], scene.meshlets["vertexTriangleCount"]], axis=1).astype(u32)
-    parts = [head, objects.view(u32).reshape(-1), scene.primitives["vertexOffset"].astype(u32), m.reshape(-1), scene.meshlet_data]
+    parts = [head, objects.view(u32).reshape(-1), scene.primitives["vertexOffset"].astype(u32),
+             np.stack([mbase, mcount], axis=1).reshape(-1), m.reshape(-1), scene.meshlet_data]
     if uv is not None:
         parts.append(np.ascontiguousarray(uv, dtype=f32).view(u32).reshape(-1))
     if nrm is not None:
@@ -183,3 +188,25 @@ def test_scene_without_normals_or_texcoords(program, tmp_path):
     want = RS.shade(bare, bare.objects, hits, lods=lods)
     assert not want["uv"].view(u32).any() and want["normal"].any() and want["baseColor"].any()
     _same(_run(program, tmp_path, bare, bare.objects, hits, 0.0, lods), want, hits, "no texture coordinates")
+
+
+def test_several_assets_the_hits_meshlet_is_asset_relative(program, tmp_path):
+    """tests/multi_asset.py's three assets as one table (per primitive the first meshlet and the meshlet count of its asset): the traced
+    hits, whose meshlet is asset-relative, and the edges of that numbering -- the last meshlet of an asset, its count (invalid, though a
+    valid index of the concatenated array), a meshlet of another primitive of the same asset."""
+    import multi_asset as MA
+    ms, cam = MA.three_assets()
+    MA.filled(ms, cam)
+    rays, _ = MA.ray_set(ms)
+    hits = S.trace(ms.spec, ms.objects, rays, meshlet_cull=True, asset_meshlet_base=ms.asset_meshlet_base)
+    edges = ms.edge_hits()
+    hits = np.concatenate([hits] + [h for _, h, _ in edges])
+    kw = dict(asset_meshlet_base=ms.asset_meshlet_base, asset_meshlet_count=ms.asset_meshlet_count)
+    lods = RC.per_hit_lods(hits)
+    want = RS.shade(ms.spec, ms.objects, hits, lods=lods, **kw)
+    valid = (want["flags"] & RS.RAYSURF_VALID) != 0
+    on = ms.asset_of_object[np.where(valid, hits["object"], 0)]
+    assert all((valid & (on == a)).sum() >= 50 for a in range(3))
+    assert [bool(v) for v in valid[-len(edges):]] == [v for _, _, v in edges]
+    assert (want.view(u32).reshape(-1, 16) != RS.shade(ms.spec, ms.objects, hits, lods=lods).view(u32).reshape(-1, 16)).any(axis=1).sum() >= 50
+    _same(_run(program, tmp_path, ms.spec, ms.objects, hits, 0.0, lods, **kw), want, hits, "three assets")
