@@ -706,7 +706,7 @@ void launch_full_list(ChordCtx* c);             // the full post-cull list of a 
 void launch_cull_masks(ChordCtx* c, bool wholeRange = false);   // sharded cull: objects + this rank's range of group instances -> rank-mask words (its chunk of dCullExchange)
 bool cull_shardable_config(const ChordCtx* c);  // the sharded cull applies to this configuration: 2..8 ranks, flat cull mode, a scene and a sharded G-buffer (debug bit 524288 -- set alike on every rank -- turns it off)
 bool cull_shardable(const ChordCtx* c);         // ... and its exchange buffer stands (made at set-up): what a frame decides its first collective by -- state every rank shares
-int ensure_cull_exchange(ChordCtx* c);          // chordvis_abi.cpp: (re)allocates dCullExchange for the current scene / rank count
+int ensure_cull_exchange(ChordCtx* c);          // abi_shard.cpp: (re)allocates dCullExchange for the current scene / rank count
 int prepare_cull_exchange(ChordCtx* c);         // ... at set-up time (upload_scene, set_shard / allocate_gbuffer), wherever the sharded cull can apply
 void launch_hzb_cull(ChordCtx* c, const HzbBuffers& hzb, int phase, const CmdList& in, const CmdList& outVisible,
                      const CmdList* outRejected);
@@ -721,7 +721,7 @@ void launch_detile(ChordCtx* c, hipStream_t stream = nullptr);
 void launch_hzb_untile(ChordCtx* c, HzbBuffers& out, bool finalChain);   // exchanged tile slots -> mips 0..5 of the chain (final: min + max + per-tile ranges and loads)
 void launch_rank_filter(ChordCtx* c, const CmdList& in, const CmdList& out);
 int tile_layout(uint32_t tilesX, uint32_t tilesY, uint32_t ranks, const uint32_t* loads, uint32_t cap, uint8_t* owners);   // tile_layout.cpp
-int install_tile_owners(ChordCtx* c);                                     // chordvis_abi.cpp: c->tileOwners -> device tables
+int install_tile_owners(ChordCtx* c);                                     // abi_shard.cpp: c->tileOwners -> device tables
 void launch_visibility_mark(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount, uint32_t* marker);
 void launch_shading_tiles(ChordCtx* c, const uint32_t* marker, uint32_t shadingType, uint32_t* tiles, uint32_t* count, uint32_t* args);
 void launch_resolve_attributes(ChordCtx* c, const unsigned long long* vis, const ChordDrawCmd* cmds, const uint32_t* cmdCount,

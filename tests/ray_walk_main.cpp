@@ -79,7 +79,7 @@ int main(int argc, char** argv)
     };
     ChordObject* objects = exact<ChordObject>(take((size_t)nObjects * 56u), nObjects);
 
-    // one BLAS per primitive, all in one node array and one triangle array (chordvis_abi.cpp ray_build_blases)
+    // one BLAS per primitive, all in one node array and one triangle array (abi_rays.cpp ray_build_blases)
     std::vector<float> bounds((size_t)nPrims * 6u);
     std::vector<ray::Node> blasNodes;
     std::vector<ray::Triangle> blasTris;

@@ -6,8 +6,8 @@ carries from call to call, and which call has to drop, re-make or keep it.  A fr
 orc.frame (or the oracle call of its entry point: orc.visibility_mark, orc.shading_tiles, orc.raster_depth, the renderShadow
 replay of test_depth_views.py, spec_bounds_tiles_np), never only with a second HIP context.
 
-Carried state, read from the source before anything was run.  abi = chord_amd/csrc/chordvis_abi.cpp, dv = csrc/depth_views.cpp,
-lr = launch_raster in csrc/kernels_raster.hip, ct = configure_targets (abi), the shared tail of allocate_gbuffer and set_shard.
+Carried state, read from the source before anything was run.  abi = the host layer, chord_amd/csrc/abi_*.cpp and chordvis_abi.cpp (the scene), dv = csrc/depth_views.cpp,
+lr = launch_raster in csrc/kernels_raster.hip, ct = configure_targets (abi_context.cpp), the shared tail of allocate_gbuffer and set_shard.
 Tests: T1 resizing, T2a templates_and_forms, T2b block_kernel_leftovers, T2c refused_upload, T2d hot_tiles, T3 mode_switches,
 T4 bind_objects, T5 sharded_and_unsharded, T6 cascade_cache.
 

@@ -28,7 +28,7 @@ FUSED_CULL_GROUPS = 64              # :947  FUSED_CULL_THREADS / 4: group instan
 FUSED_CULL_MAX_BLOCKS = 1024        # :948  look-back words
 QUAD_CULL_MAX_BLOCKS = 512          # :1620, :1631  past it, object_cull_kernel opens the frame (count + self-summing scatter)
 CULL_SELFSUM_MAX_BLOCKS = 4096      # :1187 past it, group_cull_prefix_kernel as well (BASELINE config 5 sits there)
-COUNT_BLOCK_GROUPS = 256            # chordvis_abi.cpp:659  cullBlocks = max(1, ceil(groupInstances / 256))
+COUNT_BLOCK_GROUPS = 256            # chordvis_abi.cpp upload_scene_impl  cullBlocks = max(1, ceil(groupInstances / 256))
 # (the fused path's last condition, the HZB tail in HZB_TAIL_FLOATS (:706), holds for every target of this module)
 
 

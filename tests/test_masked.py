@@ -174,8 +174,8 @@ def test_masked_frame_properties():
 
 
 def test_wrap_remainder_by_multiply_high_is_exact():
-    """The tile kernel wraps a texel index of a non-power-of-two level with constants resolved at upload (chordvis_abi.cpp
-    wrap_consts; kernels_raster.hip period_mod): magic = floor(2^32 / period), bias = the first multiple of the period >= 2^30;
+    """The tile kernel wraps a texel index of a non-power-of-two level with constants resolved at upload (host_layer.h
+    tex_wrap_constants; texel_wrap.h period_mod): magic = floor(2^32 / period), bias = the first multiple of the period >= 2^30;
     r = (i + bias) - mulhi(i + bias, magic) * period, minus the period once if r >= period.  Restated here in numpy over every
     period a level can have (sizes 1..16384, doubled for MIRRORED_REPEAT) at the index range texel_floor produces (|i| <= 1e9,
     and the +1 neighbour of the bilinear fetch), against the mathematical remainder."""
