@@ -16,6 +16,7 @@ import helpers as H
 import orc
 from chord_amd import records as R
 from chord_amd import scenes
+from helpers import _unproject
 
 W, HGT = 200, 136
 W_WIDE = 328
@@ -51,31 +52,6 @@ GUARD_328 = [
     ((-150000.5, 30.5), (150.5, 20.5), (140000.5, 60000.5)),
     ((100.5, -65000.5), (300.5, 60.5), (-160000.5, 130.5)),
 ]
-
-
-def _unproject(view, iv, tris, w, h, dist0=5.0):
-    """World positions (float32) whose projections are the given pixel positions, triangle k on the plane of view depth
-    dist0 + k / 64 (no two triangles tie in depth)."""
-    m = view["translatedWorldToClip"][0].reshape(4, 4).T.astype(np.float64)
-    inv = np.linalg.inv(m)
-    campos = np.frombuffer(iv["cameraWorldPos"][0].tobytes(), dtype=np.float64)[:3]
-    out = []
-    for k, tri in enumerate(tris):
-        for (x, y) in tri:
-            ndc = np.array([x / w * 2.0 - 1.0, 1.0 - y / h * 2.0])
-            a = inv @ np.array([ndc[0], ndc[1], 0.5, 1.0]); a = a[:3] / a[3]
-            b = inv @ np.array([ndc[0], ndc[1], 0.25, 1.0]); b = b[:3] / b[3]
-            wa, wb = m[3] @ np.append(a, 1.0), m[3] @ np.append(b, 1.0)
-            t = (dist0 + k / 64.0 - wa) / (wb - wa)
-            out.append(campos + a + t * (b - a))
-    pos = np.asarray(out, dtype=np.float32)
-    # back through the matrix: the float32 positions land on the intended sub-pixels
-    clip = m @ np.concatenate([pos.astype(np.float64) - campos, np.ones((len(pos), 1))], axis=1).T
-    px, py = (clip[0] / clip[3] * 0.5 + 0.5) * w, (0.5 - clip[1] / clip[3] * 0.5) * h
-    want = np.asarray([v for tri in tris for v in tri], dtype=np.float64)
-    near = (np.abs(want) < 1000.0).all(axis=1)          # (the far vertices of GUARD only have to be far)
-    assert np.abs(px - want[:, 0])[near].max() * 256 < 0.25 and np.abs(py - want[:, 1])[near].max() * 256 < 0.25, "a vertex misses its sub-pixel"
-    return pos
 
 
 def _scene(tris, mode, w=W, h=HGT):
