@@ -11,6 +11,8 @@ namespace chord {
 // waiting; the BLASes belong to a scene upload, which has let the stream run empty before it frees them.
 void drop_ray_tlas(ChordCtx* c, bool park)
 {
+    // (a rebuilt TLAS lives in the rebuild's own buffers, which stay for the next rebuild: abi_raytlas.cpp)
+    if (c->rayTlasRebuilt) { c->dRayTlas = nullptr; c->dRayLeafRef = nullptr; c->dRayCounters = nullptr; c->dRayLeafBox = nullptr; c->dRayRoot = nullptr; c->rayTlasRebuilt = false; }
     if (park) { retire(c, c->dRayTlas); retire(c, c->dRayLeafRef); retire(c, c->dRayCounters); retire(c, c->dRayLeafBox); retire(c, c->dRayRoot); }
     else { dfree(c->dRayTlas); dfree(c->dRayLeafRef); dfree(c->dRayCounters); dfree(c->dRayLeafBox); dfree(c->dRayRoot); }
     c->rayTlasBuilt = false; c->rayRefitDue = false; c->rayTlasNodes = c->rayTlasDepth = 0; c->rayTlasBytes = 0;
@@ -19,6 +21,7 @@ void drop_ray_tlas(ChordCtx* c, bool park)
 void drop_ray_scene(ChordCtx* c)          // (the caller has let the stream run empty)
 {
     drop_ray_tlas(c, false);
+    drop_ray_rebuild_buffers(c);
     dfree(c->dRayBlas); dfree(c->dRayTriangles); dfree(c->dRayBlasRoot); dfree(c->dRayCounts);
     c->rayBlasBuilt = false; c->rayBlasNodes = c->rayBlasTriangles = c->rayBlasDepth = 0; c->rayBlasBytes = 0;
 }
@@ -32,7 +35,7 @@ int ray_checks(ChordCtx* c, const char* fn, bool needTlas)
     if (c->sharedScene) return refuse(c, CHORDVIS_E_INVALID, fn, "not on a depth-view context");
     if (!c->sceneLoaded) return refuse(c, CHORDVIS_E_INVALID, fn, "no scene (call chordvis_upload_scene first)");
     if (needTlas && !(c->rayBlasBuilt && c->rayTlasBuilt))
-        return refuse(c, CHORDVIS_E_INVALID, fn, "no ray scene, or it was dropped by chordvis_upload_scene / chordvis_set_object_list (call chordvis_build_ray_scene)");
+        return refuse(c, CHORDVIS_E_INVALID, fn, "no ray scene, or it was dropped by chordvis_upload_scene / chordvis_set_object_list (call chordvis_build_ray_scene, or chordvis_rebuild_ray_tlas)");
     return CHORDVIS_OK;
 }
 

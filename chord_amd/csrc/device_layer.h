@@ -533,6 +533,16 @@ struct ChordCtx {
     bool rayTlasBuilt = false;
     bool rayRefitDue = false;                      // the objects changed since the latest refit was enqueued
     uint64_t rayBlasBytes = 0, rayTlasBytes = 0;
+    // chordvis_rebuild_ray_tlas (abi_raytlas.cpp; kernels_raytlas.hip): the rebuild's own buffers, sized by a capacity in
+    // objects, kept across object lists and let go with the ray scene.  While rayTlasRebuilt, the five TLAS pointers above ALIAS them.
+    chord::ray::Node* dRayRebuildNodes = nullptr;
+    uint32_t* dRayRebuildLeafRef = nullptr;
+    uint32_t* dRayRebuildCounters = nullptr;
+    float* dRayRebuildLeafBox = nullptr;
+    float* dRayRebuildRoot = nullptr;
+    uint32_t* dRayRebuildScratch = nullptr;        // ray::tlas_scratch(rayRebuildCapacity)
+    uint64_t rayRebuildCapacity = 0, rayRebuildBytes = 0;
+    bool rayTlasRebuilt = false;
     unsigned long long* dRayCounts = nullptr;      // CHORD_RAY_COUNTERS builds only: the traversal sums, made with the BLASes, never cleared
     // what chordvis_build_ray_scene reads back of the resident scene: the lengths of the three streams the context did not keep
     uint32_t groupIndexWords = 0, meshletDataWords = 0, vertexTotal = 0;
@@ -799,6 +809,8 @@ void launch_group_refs_build(ChordCtx* c);
 // each on the context's stream.
 void launch_ray_refit(ChordCtx* c);
 void launch_ray_trace(ChordCtx* c, const ChordRay* rays, uint32_t count, bool anyHit, ChordRayHit* hits);
+namespace ray { struct TlasShape; }
+void launch_ray_tlas_rebuild(ChordCtx* c, const ray::TlasShape& shape);     // kernels_raytlas.hip: everything before the refit
 // kernels_rayshade.hip: chordvis_shade_ray_hits' launch (arguments checked by the entry point; count > 0).  One launch on the context's
 // stream, of the kernel for the texel store or -- some chain kept as blocks -- the one that reads both stores.
 void launch_ray_shade(ChordCtx* c, const ChordRayHit* hits, uint32_t count, float lod, const float* lods, ChordRayHitSurface* surfaces);

@@ -61,6 +61,7 @@ int flush_pending_tail(ChordCtx* c);
 void drop_world_transforms(ChordCtx* c);        // chordvis_abi.cpp
 void drop_ray_tlas(ChordCtx* c, bool park);     // abi_rays.cpp
 void drop_ray_scene(ChordCtx* c);
+void drop_ray_rebuild_buffers(ChordCtx* c);     // abi_raytlas.cpp (the caller has let the stream run empty)
 void drop_material_textures(ChordCtx* c);       // abi_textures.cpp
 
 // ---- textures (abi_textures.cpp; the alpha plane of chordvis_upload_scene is made with the same code) ----

@@ -158,6 +158,8 @@ class RaySceneInfo(C.Structure):
 RAY_ANY_HIT = 1                                    # chordvis_trace_rays flags
 RAY_HIT, RAY_BACK_FACE = 1, 2                      # ChordRayHit::status bits
 RAY_MAX_DEPTH = 12
+RAY_TLAS_GROUP_MAX = 4096                          # CHORD_RAY_TLAS_GROUP_MAX: up to this many objects one workgroup rebuilds the TLAS
+RAY_TLAS_NODE, RAY_TLAS_LEAF, RAY_NO_CHILD = 0, 1, 0xFFFFFFFF      # ChordRayNode child words: tag << 30 | index
 RAYSURF_VALID, RAYSURF_BACK_FACE, RAYSURF_TWO_SIDED, RAYSURF_PBR = 1, 2, 4, 8      # ChordRayHitSurface::flags (chordvis_shade_ray_hits)
 
 
@@ -266,6 +268,8 @@ def _load():
         "chordvis_refit_ray_scene": (i32, [vp]),
         "chordvis_trace_rays": (i32, [vp, vp, u32, u32, vp]),
         "chordvis_ray_scene_info": (i32, [vp, P(RaySceneInfo)]),
+        "chordvis_rebuild_ray_tlas": (i32, [vp]),
+        "chordvis_readback_ray_tlas": (i32, [vp, vp, u32, vp, u32]),
         # (ctx, deviceHits, count, lod, deviceLods, deviceSurfaces): the float travels as a float, every pointer as a void pointer
         "chordvis_shade_ray_hits": (i32, [vp, vp, u32, C.c_float, vp, vp]),
         # (ctx, desc, devicePosition, deviceNormal, deviceZ, deviceTable, deviceOut, deviceHits)

@@ -110,6 +110,9 @@ BOUNDS_TILES_NEAR, BOUNDS_TILES_FAR = 1, 2
 RAY = np.dtype([("origin", f32, 3), ("tMin", f32), ("direction", f32, 3), ("tMax", f32)])
 RAY_HIT = np.dtype([("t", f32), ("u", f32), ("v", f32), ("object", u32), ("meshlet", u32), ("triangle", u32), ("primitive", u32), ("status", u32)])
 assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32
+# chordvis_readback_ray_tlas (ChordRayNode): a 4-wide TLAS node, the boxes of its children axis by axis
+RAY_NODE = np.dtype([("lo", f32, (3, 4)), ("hi", f32, (3, 4)), ("child", u32, 4), ("parentRef", u32), ("childCount", u32), ("pad", u32, 2)])
+assert RAY_NODE.itemsize == 128
 # chordvis_shade_ray_hits (ChordRayHitSurface): sixteen words per hit, an invalid hit all zero
 RAY_HIT_SURFACE = np.dtype([("baseColor", f32, 4), ("emissive", f32, 3), ("roughness", f32), ("normal", f32, 3), ("metallic", f32),
                             ("uv", f32, 2), ("material", u32), ("flags", u32)])

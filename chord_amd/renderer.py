@@ -420,6 +420,21 @@ class VisibilityRenderer:
         self._check(L.lib.chordvis_ray_scene_info(self._ctx, C.byref(info)), "ray_scene_info")
         return info
 
+    def rebuild_ray_tlas(self):
+        """chordvis_rebuild_ray_tlas: the TLAS topology of the current object list built on the device, in stream order, and refitted.
+        Needs one build_ray_scene since the last upload_scene.  Waits only for a list longer than every list rebuilt before."""
+        self._check(L.lib.chordvis_rebuild_ray_tlas(self._ctx), "rebuild_ray_tlas")
+
+    def read_ray_tlas(self, count=None):
+        """(records.RAY_NODE array of tlasNodes nodes, uint32 leafRef per object) of the TLAS, whichever builder made it
+        (chordvis_readback_ray_tlas).  count: the current list's object count (None: self.scene's).  Synchronises."""
+        info = self.ray_scene_info()
+        count = len(self.scene.objects) if count is None else int(count)
+        nodes = np.zeros(info.tlasNodes, dtype=R.RAY_NODE)
+        leaf_ref = np.zeros(count, dtype=np.uint32)
+        self._check(L.lib.chordvis_readback_ray_tlas(self._ctx, nodes.ctypes.data, len(nodes), leaf_ref.ctypes.data, len(leaf_ref)), "readback_ray_tlas")
+        return nodes, leaf_ref
+
     def trace_rays(self, rays, any_hit=False, out=None):
         """chordvis_trace_rays, one launch that never waits.  rays: a contiguous CUDA tensor of records.RAY records (32 bytes each, e.g.
         float32 (n, 8)) on the context's device, or a numpy array of records.RAY, which is copied there.  Returns an int32 CUDA tensor

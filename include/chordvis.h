@@ -432,6 +432,55 @@ int chordvis_refit_ray_scene(ChordCtx* ctx);
 int chordvis_trace_rays(ChordCtx* ctx, const ChordRay* deviceRays, uint32_t count, uint32_t flags, ChordRayHit* deviceHits);
 int chordvis_ray_scene_info(ChordCtx* ctx, ChordRaySceneInfo* outInfo);
 
+/* REBUILDING THE TLAS.  chordvis_rebuild_ray_tlas builds the TLAS topology for the current object list ON THE DEVICE,
+ * in stream order, from the object array the frames read now (the bound one after chordvis_bind_objects), and ends with the refit:
+ * tracing is valid straight after it and a pending refit is done.  It needs the BLASes -- one chordvis_build_ray_scene since the last
+ * chordvis_upload_scene -- and is valid whether a TLAS exists (objects have travelled: a refit keeps the old topology, whose boxes
+ * overlap more and more) or was dropped by chordvis_set_object_list (objects came and went).  It never synchronises, copies or
+ * allocates, but for a list LONGER than every list rebuilt before on this scene: then new buffers are made first and the old ones
+ * let go afterwards, and the call may wait, as a growing chordvis_set_object_list may.  The rebuild owns its buffers and keeps them
+ * across object lists until the next chordvis_upload_scene.  Launches: two (one workgroup, then the refit) up to
+ * CHORD_RAY_TLAS_GROUP_MAX objects, 15 above (centres, four radix passes of three launches, node table, refit): a function of the
+ * count alone.  Not inside a captured graph.
+ *   THE TREE is a pure function of the object boxes (tests/spec_ray_tlas_np.py states it in numpy; chord_amd/csrc/ray_tlas_shape.h is
+ *   the code), binary32, one rounding per operation, no contraction, correctly rounded divide:
+ *     box        of object i: the refit's (RAY QUERIES above)
+ *     centre     c[a] = lo[a] * 0.5f + hi[a] * 0.5f
+ *     bounds     Blo[a], Bhi[a]: min and max of c[a] over all objects under the total order of the float's bits made monotone
+ *                (u & 0x80000000 ? ~u : u | 0x80000000): -0 sorts below +0, a NaN goes to an end
+ *     quantised  extent = Bhi[a] - Blo[a]; !(extent > 0) || !(extent < 3.0e38f): q[a] = 0; otherwise scale = 1024.0f / extent,
+ *                f = (c[a] - Blo[a]) * scale, q[a] = f > 0 ? (f < 1024.0f ? (uint32) f : 1023) : 0 (a NaN gives 0)
+ *     key        30 bits: bit 3 k + a of m is bit k of q[a]
+ *     order      ascending (m, i): the pairs are unique
+ *     levels     cnt[0] = n, cnt[j] = ceil(cnt[j-1] / 4) up to the first j >= 1 with cnt[j] == 1: that j is the depth D (n == 1:
+ *                D = 1).  D > CHORD_RAY_MAX_DEPTH (n > 4^12) is CHORDVIS_E_CAPACITY, nothing changed or launched
+ *     numbering  base[D] = 0, base[j-1] = base[j] + cnt[j]; node (j, i) is base[j] + i, the root is node 0; tlasNodes = cnt[1] + ..
+ *                + cnt[D], tlasDepth = D
+ *     words      of node (j, i): childCount = min(4, cnt[j-1] - 4 i); child k is CHORD_RAY_TLAS_LEAF << 30 | order[4 i + k] for
+ *                j == 1, else CHORD_RAY_TLAS_NODE << 30 | (base[j-1] + 4 i + k); an unused slot holds CHORD_RAY_NO_CHILD, lo = +inf,
+ *                hi = -inf; parentRef is CHORD_RAY_NO_CHILD for the root, else (base[j+1] + (i >> 2)) * 4 + (i & 3); pad is 0
+ *     leafRef    leafRef[order[p]] = (base[1] + (p >> 2)) * 4 + (p & 3)
+ *     boxes      of used slots: the refit's exact unions
+ *   The answer of a trace does not depend on the tree, so hits are the specification's whichever builder made the TLAS.  WHICH TO
+ *   PREFER: chordvis_build_ray_scene's host builder splits by surface area and its tree is the cheaper one to walk; a host with time
+ *   to spare -- a static list, a loading screen -- should build there and refit.  Measured on an MI355X (profiles/ray_tlas_time.txt;
+ *   DESIGN.md 4.19): the rebuild takes 0.039 ms of device time for 352 objects and 0.146 ms for 22 528, against 0.26 ms and 9.8 ms of
+ *   host wall time for the host's TLAS rebuild with its wait; a 4K pass of closest-hit pixel rays on the rebuilt tree takes 1.5 and
+ *   2.06 times as long as on the host-built tree (AO: 1.43 and 1.95 times), because a Morton-order complete tree puts large boxes
+ *   among small ones into the same nodes.  The rebuild is for the frame loop, where the list changes or the wait is what hurts.
+ *   chordvis_set_object_list and chordvis_build_ray_scene behave as before: after a new list the refit, the trace and the info are
+ *   refused until a build OR a rebuild; the build still makes the surface-area TLAS on the host.
+ *   CHORDVIS_E_INVALID, chordvis_last_error naming the remedy, nothing changed or launched: a NULL context (no message); a depth-view
+ *   child context; no scene; no BLASes since the last chordvis_upload_scene.  A refused rebuild leaves the TLAS it found.
+ * chordvis_readback_ray_tlas SYNCHRONISES and copies the TLAS's node table (chordvis_ray_scene_info's tlasNodes records) and leaf
+ * references (one per object) to the host, whichever builder made them; either pointer may be NULL; a capacity below the count is
+ * CHORDVIS_E_INVALID, and so is a context without a TLAS.
+ * tests/test_ray_tlas_spec.py holds the specification to a scalar evaluation, tests/test_ray_tlas_host.py runs ray_tlas_shape.h on
+ * the host under the address and undefined-behaviour sanitizers, tests/test_gpu_ray_tlas.py holds the statements above on the GPU but
+ * the refusal on a depth-view child context, which no entry point hands out (read from the code). */
+int chordvis_rebuild_ray_tlas(ChordCtx* ctx);
+int chordvis_readback_ray_tlas(ChordCtx* ctx, ChordRayNode* hostNodes, uint32_t nodeCapacity, uint32_t* hostLeafRef, uint32_t objectCapacity);
+
 /* SHADING A HIT (RayHitMaterialInfo::init, raytrace_shared.hlsli: what ddgi_probe_trace.hlsl, gi_screen_probe_*.hlsl and
  * gi_specular_trace.hlsl do with a hit).  chordvis_shade_ray_hits writes one ChordRayHitSurface per ChordRayHit --
  * material, normal and uv at the hit point -- in ONE launch on the context's stream that never waits; count == 0 succeeds without

@@ -343,6 +343,20 @@ typedef struct ChordRayHit {                    /* 32 bytes; a miss is eight zer
 #define CHORD_RAY_ANY_HIT    1u    /* chordvis_trace_rays flags: only status bit 0 is written, the other seven words are zero */
 #define CHORD_RAY_MAX_DEPTH  12u   /* interior levels of one tree (BLAS or TLAS) the traversal stack is sized for */
 
+/* chordvis_rebuild_ray_tlas / chordvis_readback_ray_tlas (chordvis.h RAY QUERIES, "rebuilding the TLAS"). */
+#define CHORD_RAY_TLAS_GROUP_MAX 4096u   /* object lists up to this long are rebuilt by one workgroup (two launches, the refit included) */
+#define CHORD_RAY_TLAS_NODE  0u    /* bits 31..30 of a ChordRayNode child word: bits 29..0 index a TLAS node ...  */
+#define CHORD_RAY_TLAS_LEAF  1u    /* ... or an object of the current list                                        */
+#define CHORD_RAY_NO_CHILD   0xFFFFFFFFu
+typedef struct ChordRayNode {                   /* 128 bytes: a 4-wide node holds the boxes of its children, axis by axis */
+    float    lo[3][4];         /* [axis][child]; an unused slot: +inf                                               */
+    float    hi[3][4];         /* an unused slot: -inf                                                              */
+    uint32_t child[4];         /* tag << 30 | index; an unused slot: CHORD_RAY_NO_CHILD                             */
+    uint32_t parentRef;        /* parent node * 4 + the slot this node's box lives in; CHORD_RAY_NO_CHILD: the root */
+    uint32_t childCount;       /* 1..4: slots 0 .. childCount - 1 are used                                          */
+    uint32_t pad[2];
+} ChordRayNode;
+
 /* chordvis_shade_ray_hits (chordvis.h RAY QUERIES, "shading a hit"): one record per ChordRayHit. */
 #define CHORD_RAYSURF_VALID      1u   /* ChordRayHitSurface::flags bit 0: the record is filled (an invalid hit: sixteen zero words)  */
 #define CHORD_RAYSURF_BACK_FACE  2u   /* copied from the hit's CHORD_RAY_BACK_FACE                                                */
@@ -393,6 +407,7 @@ typedef struct ChordRaySceneInfo {              /* 64 bytes */
 }
 static_assert(sizeof(ChordRay) == 32 && sizeof(ChordRayHit) == 32 && sizeof(ChordRaySceneInfo) == 64, "ray records");
 static_assert(sizeof(ChordRayHitSurface) == 64, "ChordRayHitSurface");
+static_assert(sizeof(ChordRayNode) == 128, "ChordRayNode");
 static_assert(sizeof(ChordPixelRaysDesc) == 64, "ChordPixelRaysDesc");
 static_assert(sizeof(ChordBoundsTilesDesc) == 16, "ChordBoundsTilesDesc");
 static_assert(sizeof(ChordBoundsQuery) == 160, "ChordBoundsQuery");
