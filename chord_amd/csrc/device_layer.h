@@ -16,7 +16,7 @@
 #include "chordvis.h"
 #include "ray_scene.h"
 
-// Build switches of the measurement code in the raster kernels (kernels_raster.hip): per-phase clocks (chordvis_set_debug
+// Build switches of the measurement code in the raster kernels (kernels_raster_setup.hip, kernels_raster.hip; the bits: raster_params.h): per-phase clocks (chordvis_set_debug
 // bits 16 and 512) and ablation switches (bits 1, 2, 32, 64, 128, 256, 1024, 2048, 4096, 8192, 16384).  Off in the product
 // library; python chord_amd/build.py --tag NAME -DRASTER_PROFILE=1 / -DRASTER_ABLATION=1 builds a measuring one.
 #ifndef RASTER_PROFILE
@@ -317,7 +317,7 @@ struct TriRecC {
     uint32_t payload;
 };
 #define CHORD_REC_WIDE 0x80000000u
-// Pixel blocks (kernels_raster.hip "small clusters"): a cluster whose emitted triangles all fall into a window of
+// Pixel blocks (kernels_raster_setup.hip "small clusters"): a cluster whose emitted triangles all fall into a window of
 // CHORD_BLOCK_WIN x CHORD_BLOCK_WIN pixels is resolved by its setup wave in LDS and leaves the kernel as one dense block of
 // packed visibility words per tile it touches instead of one record + bin entry per triangle.  A block lives in the
 // block pool at a 16-byte granule offset: word 0 = header (x0 | y0 << 6 | (w-1) << 12 | (h-1) << 16, tile-local, and
@@ -576,7 +576,7 @@ struct ChordCtx {
     uint8_t* dTileOwner = nullptr;     // sharded: owner of every tile (what the rank masks are made from)
     bool cullPhaseDone = false;        // this frame's chordvis_frame_phase_cull ran: phase a unpacks the exchanged words instead of culling
     bool exchangeSlotsFresh = false;   // this frame's fused tile kernel wrote the rank's slots of the end-of-frame exchange buffer (phase c needs them)
-    ChordDrawCmd* dLeftCmds = nullptr; // dense launches: the clusters the block kernel left to the record kernel (kernels_raster.hip)
+    ChordDrawCmd* dLeftCmds = nullptr; // dense launches: the clusters the block kernel left to the record kernel (kernels_raster_setup.hip)
     uint32_t* dCounts = nullptr;      // 4 x u32 backing the list counts
 
     // gbuffer

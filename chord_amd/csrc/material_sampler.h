@@ -24,7 +24,7 @@ __device__ __forceinline__ float4 decode_texel(uint32_t w, const float* srgb)
                        (float)((w >> 16) & 255u) * (1.0f / 255.0f), (float)(w >> 24) * (1.0f / 255.0f));
 }
 
-// one level, per channel sample_alpha's arithmetic (kernels_raster.hip)
+// one level, per channel sample_alpha's arithmetic (raster_device.h)
 template <bool kSrgb>
 __device__ __forceinline__ float4 sample_level(const uint32_t* __restrict__ texels, const DMatLevel& L, uint32_t wrapS, uint32_t wrapT, bool linear,
                                                float u, float v, const float* srgb)

@@ -1,4 +1,4 @@
-// Texel addressing shared by the raster's alpha test (kernels_raster.hip sample_alpha) and the material resolve
+// Texel addressing shared by the raster's alpha test (raster_device.h sample_alpha) and the material resolve
 // (kernels_resolve.hip): floor of a texel coordinate with the +-1e9 guard, and the three wrap modes with the level's
 // precomputed remainder constants (DMatLevel).  One definition, so the two samplers address texels identically.
 #pragma once

@@ -1375,7 +1375,7 @@ int chordvis_upload_history_hzb(ChordCtx* ctx, const uint16_t* hostMin);
  * hipEventRecord between two kernels costs ~5 us of stream idle time on MI355X. */
 int chordvis_enable_timers(ChordCtx* ctx, int mode);
 int chordvis_stats(ChordCtx* ctx, ChordStats* out);
-/* Measurement-only switches of the raster kernels (kernels_raster.hip DBG_*).  The clocks (16, 512) and the ablation switches
+/* Measurement-only switches of the raster kernels (raster_params.h DBG_*).  The clocks (16, 512) and the ablation switches
  * are compiled into the kernels only with -DRASTER_PROFILE=1 / -DRASTER_ABLATION=1 (python chord_amd/build.py --tag NAME -D...;
  * load it with CHORDVIS_LIB): the product library REFUSES them (CHORDVIS_E_INVALID), because testing them at run time costs the
  * register-bound kernels 3-5 %.  1 no pixel writes, 2 setup

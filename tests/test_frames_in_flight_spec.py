@@ -8,7 +8,7 @@ import pytest
 
 import inflight as F
 
-TILE_DIRECT_MAX_CLUSTERS = 1024            # chord_amd/csrc/kernels_raster.hip
+TILE_DIRECT_MAX_CLUSTERS = 1024            # chord_amd/csrc/raster_params.h
 
 
 def _differ(a, b):

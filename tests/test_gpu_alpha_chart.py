@@ -1,4 +1,4 @@
-"""GPU: the raster's alpha test (kernels_raster.hip mask_level_filter / write_mask_ext / alpha_level / sample_alpha, texel_wrap.h,
+"""GPU: the raster's alpha test (raster_device.h mask_level_filter / write_mask_ext / alpha_level / sample_alpha, texel_wrap.h,
 the DMatLevel table of chordvis_upload_scene) on the sampler charts of tests/alpha_chart.py: every (wrapS, wrapT) pair under both
 filter pairs, at the levels, level shapes and periods the charts name, at the level boundaries, at equality with the cut-off and
 at wild texture coordinates.  One 256 x 192 frame per chart, bit for bit against the oracle; tests/test_alpha_chart_spec.py shows

@@ -7,7 +7,7 @@ orc.frame (or the oracle call of its entry point: orc.visibility_mark, orc.shadi
 replay of test_depth_views.py, spec_bounds_tiles_np), never only with a second HIP context.
 
 Carried state, read from the source before anything was run.  abi = the host layer, chord_amd/csrc/abi_*.cpp and chordvis_abi.cpp (the scene), dv = csrc/depth_views.cpp,
-lr = launch_raster in csrc/kernels_raster.hip, ct = configure_targets (abi_context.cpp), the shared tail of allocate_gbuffer and set_shard.
+lr = launch_raster in csrc/raster_launch.cpp, ct = configure_targets (abi_context.cpp), the shared tail of allocate_gbuffer and set_shard.
 Tests: T1 resizing, T2a templates_and_forms, T2b block_kernel_leftovers, T2c refused_upload, T2d hot_tiles, T3 mode_switches,
 T4 bind_objects, T5 sharded_and_unsharded, T6 cascade_cache.
 
@@ -93,7 +93,7 @@ from test_gpu_cull_paths import MOVES, _check_frame
 pytestmark = pytest.mark.gpu
 
 FORCE_BLOCKS, FORCE_HOT = 65536, 262144                 # chordvis_set_debug switches that change no result (tests/test_gpu_parity.py)
-TILE_DIRECT_MAX_CLUSTERS = 1024                         # kernels_raster.hip: a later pass that set up more reports heavy
+TILE_DIRECT_MAX_CLUSTERS = 1024                         # raster_params.h: a later pass that set up more reports heavy
 NEAR_FAR = R.BOUNDS_TILES_NEAR | R.BOUNDS_TILES_FAR
 NO_HZB_FLAGS = R.FLAG_FRUSTUM_CULL | R.FLAG_CONE_CULL
 
